@@ -1,16 +1,20 @@
 """Registration-pairs/sec benchmark (BASELINE.json config #2: 30k-pt x 32-d synthetic FCGF pairs,
 mutual-NN + 50k-iteration RANSAC + LS refit) on N GPUs of one node.
 
-    python bench.py [--gpus N --steps K --warmup W]            # N > 1 without a launcher: spawns one process per GPU itself
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]      # N > 1 without a launcher: spawns one process per GPU itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the hot path over `--pairs` DISTINCT resident pairs per GPU (inputs in HBM before the timed region),
 registered as pair-batched launches (lr_register_batch, `--batch` pairs per call, round-robin over `--streams` streams), the
 4x4 transforms copied back to pinned host memory inside the timed region.  Pairs shard over ranks with no data-path
-collective (weak scaling); one RCCL all_gather per step returns the result rows.  Prints ONE JSON line on rank 0 with
-`roofline` for the dominant kernel (nn16_passb_kernel, the f16 matrix-core filter pass), `pair_roofline` (whole pair against
-the blended matrix / vector floor) and `cpu_baseline` (the reference's torch-einsum NN + numpy filter + OpenMP RANSAC on the
-host cores, rank 0, N=1).
+collective (weak scaling); one RCCL all_gather per step returns the result rows.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps, checks the last step's transforms against the planted motions (recall),
+writes that step's results with --dump-outputs and prints the line.  --full adds the legs that take runs of their own:
+`sustained` (the step loop for --sustain-s more seconds), `roofline` for the dominant kernel (nn16_passb_kernel, the f16
+matrix-core filter pass) and `pair_roofline` (whole pair against the blended matrix / vector floor), `cpu_baseline` (the
+reference's torch-einsum NN + numpy filter + OpenMP RANSAC on the host cores, rank 0, N=1) and `extra` (--extra-list).
+Without --full those keys are null.
 """
 import argparse
 import ctypes
@@ -47,7 +51,13 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=0, help="pairs per batched call (0: 32, or 8 for clouds above 60k points)")
     ap.add_argument("--streams", type=int, default=0, help="batched calls in flight per GPU (0: 2 for the headline workload, 3 with --mode GPF, 4 with --codebase GC whose "
                                                             "one-block-per-pair local optimisation leaves most CUs to the other calls; 6 with --list)")
-    ap.add_argument("--sustain-s", type=float, default=None, help="after the K timed steps, run the same step loop for at least this many seconds and report it as "
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the sustained leg (--sustain-s), the roofline calls, the CPU baseline "
+                         "(--no-cpu-baseline, --cpu-*) and the list run after the headline (--extra-list).  Off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed for rank 0's pairs as DIR/<name>.npy (float64, one row per pair): "
+                         "T, T_ransac and the per-pair counts of lr_pair_result")
+    ap.add_argument("--sustain-s", type=float, default=None, help="with --full: after the K timed steps, run the same step loop for at least this many seconds and report it as "
                                                                   "`sustained` (outside `value`; 0: skip) -- the timed region of the contract is a fraction of a second.  "
                                                                   "Default 10, or 0 under rocprofv3 (ROCPROF* in the environment): ~600 untimed steps would otherwise dominate "
                                                                   "every counter pass and kernel summary")
@@ -69,7 +79,7 @@ def parse(argv=None):
                          "codebase GC defaults).  Prints its own JSON line (recall, pairs/s, whole-path and reference-style time per pair)")
     ap.add_argument("--list-stride", type=int, default=1, help="with --list: every k-th row only")
     ap.add_argument("--extra-list", choices=["A", "B", "none"], default="A",
-                    help="the default run (N = 1, headline workload) also registers every --extra-list-stride-th row of this balanced test list with the reference's "
+                    help="with --full, the run (N = 1, headline workload) also registers every --extra-list-stride-th row of this balanced test list with the reference's "
                          "README command (configs[2] / [3], list-driven surrogate) after everything else and reports it under `extra.list_<X>`: a driver-run "
                          "record of a list workload next to the headline (outside `value`)")
     ap.add_argument("--extra-list-stride", type=int, default=8)
@@ -78,6 +88,8 @@ def parse(argv=None):
     ap.add_argument("--traffic-key", action="store_true", help="print the key this command's PMC traffic is filed under in profiles/pmc_traffic.json and exit (tools/pmc_traffic.sh)")
     ap.add_argument("--dry-run", action="store_true", help="test hook: no GPU work, gloo collectives, fake result rows (exercises the launcher, the gather and the JSON line on CPU)")
     args = ap.parse_args(argv)
+    if args.list and args.dump_outputs:
+        ap.error("--dump-outputs writes the results of the headline step loop; --list has none")
     if args.sustain_s is None:
         args.sustain_s = 0.0 if any(k.startswith("ROCPROF") for k in os.environ) else 10.0
     if any(k.startswith("ROCPROF") for k in os.environ):
@@ -131,6 +143,21 @@ def lookup_traffic(tdoc, key):
 def transform_errors(T, G):
     re = np.degrees(np.arccos(np.clip((np.trace(T[:3, :3].T @ G[:3, :3]) - 1) / 2, -1, 1)))
     return re, np.linalg.norm(T[:3, 3] - G[:3, 3])
+
+
+def dump_outputs(path, T, res):
+    """--dump-outputs: the last timed step's results, one float64 .npy per field, row i = pair i (seed 51 + i on rank 0).
+    T: [P, 16] host copy of the transforms; res: the PairResult of every pair (None in a dry run)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"T": np.asarray(T).reshape(-1, 4, 4)}
+    if res is not None:
+        arrays["T_ransac"] = np.array([r.T_ransac[:] for r in res]).reshape(-1, 4, 4)
+        for name, get in (("n_corr", lambda r: r.n_corr), ("n_refit", lambda r: r.n_refit), ("status", lambda r: r.status),
+                          ("ransac_best_h", lambda r: r.ransac.best_h), ("ransac_best_count", lambda r: r.ransac.best_count),
+                          ("ransac_n_valid", lambda r: r.ransac.n_valid)):
+            arrays[name] = np.array([get(r) for r in res])
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(args, seed0):
@@ -493,11 +520,40 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
 
+    enq_timed = enq[0]                    # host time spent enqueueing the K timed steps (the sustained leg below keeps adding to enq[0])
+
+    # ---- sanity of what was timed: every distinct pair of the last step registered correctly (from the host copy of T).  Before
+    #      the --full legs, which overwrite `outs` and `host_T`
+    recall = recall5 = res = None
+    nn_fallback_rows = None
+    score_frac = None
+    n_corr_mean = n_valid_mean = 0.0
+    if not dry:
+        ok = ok5 = 0
+        Th = host_T.numpy().reshape(-1, 4, 4)
+        for i in range(args.pairs):
+            re, te = transform_errors(Th[i], T_gt[i])
+            ok += int(re < 2 and te < 0.6)           # BASELINE.json metric: recall@(2 deg, 0.6 m)
+            ok5 += int(re < 5 and te < 0.6)
+        recall, recall5 = ok / args.pairs, ok5 / args.pairs
+        ob = outs.cpu().numpy()
+        res = [_ext.PairResult.from_buffer_copy(ob[i].tobytes()) for i in range(args.pairs)]
+        n_corr_mean = float(np.mean([r.n_corr for r in res])); n_valid_mean = float(np.mean([r.ransac.n_valid for r in res]))
+        nn_fallback_rows = float(np.mean([r.n_nn_fixed for r in res]))
+        score_frac = float(np.mean([r.reserved[0] for r in res])) / 1e6      # (model, correspondence) evaluations done / V*M (pilot-ordered scoring)
+        if use_dist:      # the gathered table holds this rank's rows where the shard order says
+            mine = gathered.view(world, args.pairs, shard.ROW)[rank, :, 22:38].cpu().numpy()
+            assert np.array_equal(mine, host_T.numpy()), "gather order"
+    elif use_dist:
+        g = gathered.view(world, args.pairs, shard.ROW)[:, 0, 22]
+        assert [float(v) for v in g] == [float(np.frombuffer(bytes([r + 1] * 8), np.float64)[0]) for r in range(world)], "gather order"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, host_T.numpy(), res)
+
     # ---- sustained rate: the same step loop for >= --sustain-s seconds (the K timed steps above last a fraction of a second; a
     #      power-limited kernel may settle at a lower clock over seconds).  Reported next to `value`, never instead of it.
-    enq_timed = enq[0]                    # host time spent enqueueing the K timed steps (the sustained leg below keeps adding to enq[0])
     sustained = None
-    if args.sustain_s > 0 and not dry:
+    if args.full and args.sustain_s > 0 and not dry:
         k2 = max(args.steps, int(np.ceil(args.sustain_s / (dt / args.steps))))
         if use_dist:      # every rank runs the same number of steps
             kt = torch.tensor([k2], dtype=torch.int64, device="cpu" if host_coll else dev)
@@ -517,36 +573,12 @@ def main():
                      "ratio_to_value": round((world * args.pairs * k2 / dt2) / (world * args.pairs * args.steps / dt), 4),
                      "note": "same step loop, same barrier + synchronize bracket, run right after the K timed steps"}
 
-    # ---- sanity of what was timed: every distinct pair of the last step registered correctly (from the host copy of T)
-    recall = recall5 = None
-    nn_fallback_rows = None
-    score_frac = None
-    n_corr_mean = n_valid_mean = 0.0
-    if not dry:
-        ok = ok5 = 0
-        Th = host_T.numpy().reshape(-1, 4, 4)
-        for i in range(args.pairs):
-            re, te = transform_errors(Th[i], T_gt[i])
-            ok += int(re < 2 and te < 0.6)           # BASELINE.json metric: recall@(2 deg, 0.6 m)
-            ok5 += int(re < 5 and te < 0.6)
-        recall, recall5 = ok / args.pairs, ok5 / args.pairs
-        res = [_ext.PairResult.from_buffer_copy(outs[i].cpu().numpy().tobytes()) for i in range(args.pairs)]
-        n_corr_mean = float(np.mean([r.n_corr for r in res])); n_valid_mean = float(np.mean([r.ransac.n_valid for r in res]))
-        nn_fallback_rows = float(np.mean([r.n_nn_fixed for r in res]))
-        score_frac = float(np.mean([r.reserved[0] for r in res])) / 1e6      # (model, correspondence) evaluations done / V*M (pilot-ordered scoring)
-        if use_dist:      # the gathered table holds this rank's rows where the shard order says
-            mine = gathered.view(world, args.pairs, shard.ROW)[rank, :, 22:38].cpu().numpy()
-            assert np.array_equal(mine, host_T.numpy()), "gather order"
-    elif use_dist:
-        g = gathered.view(world, args.pairs, shard.ROW)[:, 0, 22]
-        assert [float(v) for v in g] == [float(np.frombuffer(bytes([r + 1] * 8), np.float64)[0]) for r in range(world)], "gather order"
-
     # ---- roofline of the dominant kernel (pass B of the f16 filter): HIP events recorded by the library on the launch
     #      stream around the batched forward and reverse launches, averaged over `reps` batched calls
     roof = pair_roof = None
     total_pairs = world * args.pairs * args.steps
     value = total_pairs / dt
-    if rank == 0 and not dry:
+    if args.full and rank == 0 and not dry:
         ws = wss[0]
         reps = 10
         chunk = pairs[:B]
@@ -597,11 +629,11 @@ def main():
                      "V": round(n_valid_mean, 1), "M": round(n_corr_mean, 1)}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not dry and args.codebase == "open3D":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not dry and args.codebase == "open3D":
         cpu = cpu_baseline(args, seed0=51)
 
     extra = None
-    if rank == 0 and world == 1 and not dry and not use_dist and args.extra_list != "none" and args.codebase == "open3D" and args.n == 30000 and args.mode in ("MNN", "MMN"):
+    if args.full and rank == 0 and world == 1 and not dry and not use_dist and args.extra_list != "none" and args.codebase == "open3D" and args.n == 30000 and args.mode in ("MNN", "MMN"):
         # configs[2] (or [3]) in front of the driver: the reference's README command over every 8th row of the balanced list, surrogate data
         for w in wss:
             w.close()

@@ -38,6 +38,18 @@ def test_single_rank_line_has_the_contract_keys():
         assert k in line and line[k] is None, k
 
 
+def test_dump_outputs_and_full_flag(tmp_path):
+    """--dump-outputs DIR writes the last timed step's transforms as float64 .npy (one row per pair); --full is accepted and
+    changes nothing the dry run measures."""
+    import numpy as np
+    line = _run(["--steps", "3", "--dump-outputs", str(tmp_path / "out"), "--full"])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    T = np.load(tmp_path / "out" / "T.npy")
+    assert T.shape == (8, 4, 4) and T.dtype == np.float64
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--list", "A", "--dump-outputs", str(tmp_path / "x")], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr and not (tmp_path / "x").exists()
+
+
 def test_process_parallel_cpu_baseline_worker_protocol():
     """bench.py's cpu_baseline also runs the reference-style path as P processes side by side (the reference's own sharding,
     test_parallel.sh:18-20): oracle/cpu_worker.py says READY after its untimed warm-up, starts on GO and reports DONE <pairs> <seconds>."""

@@ -22,7 +22,7 @@ def _bench(extra):
 
 
 def test_bench_line_small_workload():
-    line = _bench(["--cpu-pairs", "2", "--cpu-budget-s", "5"])
+    line = _bench(["--full", "--cpu-pairs", "2", "--cpu-budget-s", "5"])
     assert line["n_gpus"] == 1 and line["unit"] == "pairs/s" and line["value"] > 0 and line["scaling"] == "weak" and line["dtype"] == "f32"
     assert line["recall_2deg_0.6m"] == 1.0 and line["nn_rows_redone_by_full_scan_per_pair"] == 0.0
     assert line["config"]["pairs_per_batched_call"] == 4 and "workload" in line["config"]
@@ -45,6 +45,26 @@ def test_bench_line_small_workload():
     assert 0 < lo <= med <= hi and 500 < line["clock_MHz"] < 3000 and abs(line["value_at_2.0GHz"] - line["value"] * 2000 / line["clock_MHz"]) < 0.02 * line["value"]
     assert line["extra"] is None          # (the list-A leg belongs to the headline workload only)
     assert 0 < roof["whole_call_frac"] <= roof["nn_stage_frac"] <= roof["forward_launch_frac"] < 1 and roof["forward_launch_ms"] > roof["reverse_launch_ms"] > 0
+
+
+def test_plain_run_is_lean_and_dumps_the_timed_step(tmp_path):
+    """Without --full the line carries the headline only (the legs that take runs of their own are null, --sustain-s included), and
+    --dump-outputs holds the last timed step's results: pair i is the pair seeded 51 + i, registered onto its planted motion."""
+    import numpy as np
+    from lidarregistration_amd import synth
+    line = _bench(["--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["recall_2deg_0.6m"] == 1.0
+    for k in ("sustained", "roofline", "pair_roofline", "cpu_baseline", "extra"):
+        assert line[k] is None, k
+    T, Tr = np.load(tmp_path / "T.npy"), np.load(tmp_path / "T_ransac.npy")
+    assert T.shape == Tr.shape == (12, 4, 4) and T.dtype == np.float64
+    for name in ("n_corr", "n_refit", "status", "ransac_best_h", "ransac_best_count", "ransac_n_valid"):
+        a = np.load(tmp_path / (name + ".npy"))
+        assert a.shape == (12,) and a.dtype == np.float64, name
+    assert (np.load(tmp_path / "status.npy") == 0).all() and (np.load(tmp_path / "n_corr.npy") > 0).all()
+    for i in range(12):
+        G = synth.random_motion(np.random.default_rng(51 + i + 1000003))      # make_pair_dev's planted motion for seed 51 + i
+        assert np.linalg.norm(T[i, :3, 3] - G[:3, 3]) < 0.6 and np.linalg.norm(T[i, :3, :3] - G[:3, :3]) < 0.05, i
 
 
 def test_bench_gc_codebase_workload():
@@ -79,7 +99,7 @@ def test_two_ranks_share_this_gpu_through_the_self_launcher():
     parent that never touches HIP, they rendezvous on 127.0.0.1, register their own (differently seeded) pairs on device 0, gather the
     result rows with one collective per step (host tensors: gloo) and take the max-over-ranks time.  The launch shape of the reference's
     test_parallel.sh:18-24; the same code runs with --dist-backend nccl at 8 GPUs."""
-    line = _bench(["--gpus", "2", "--dist-backend", "gloo", "--devices", "0,0", "--no-cpu-baseline"])
+    line = _bench(["--gpus", "2", "--dist-backend", "gloo", "--devices", "0,0", "--no-cpu-baseline", "--full"])
     assert line["n_gpus"] == 2 and line["value"] > 0 and line["recall_2deg_0.6m"] == 1.0 and line["scaling"] == "weak"
     assert line["config"]["parallelism"] == "pair-sharded x2"
     roof = line["roofline"]

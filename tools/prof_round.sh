@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/round
 mkdir -p $O
 cd $R
-python bench.py > $O/bench_line.json 2> $O/bench_stderr.log
+python bench.py --full > $O/bench_line.json 2> $O/bench_stderr.log
 tail -1 $O/bench_line.json | cut -c1-200
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_s1 -o s1 -- python3 $R/bench.py --streams 1 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline > /tmp/p_s1.log 2>&1

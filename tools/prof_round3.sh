@@ -6,11 +6,11 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/round3
 mkdir -p $O
 cd $R
-python bench.py > $O/bench_line.json 2> $O/bench_stderr.log
+python bench.py --full > $O/bench_line.json 2> $O/bench_stderr.log
 tail -1 $O/bench_line.json | cut -c1-160
-python bench.py --n 100000 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_line_n100k.json 2>> $O/bench_stderr.log
-python bench.py --mode GPF --no-cpu-baseline > $O/bench_line_gpf.json 2>> $O/bench_stderr.log
-python bench.py --codebase GC --no-cpu-baseline > $O/bench_line_gc.json 2>> $O/bench_stderr.log
+python bench.py --full --n 100000 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_line_n100k.json 2>> $O/bench_stderr.log
+python bench.py --full --mode GPF --no-cpu-baseline > $O/bench_line_gpf.json 2>> $O/bench_stderr.log
+python bench.py --full --codebase GC --no-cpu-baseline > $O/bench_line_gc.json 2>> $O/bench_stderr.log
 cd /tmp
 prof() {   # tag, then bench args
   tag=$1; shift

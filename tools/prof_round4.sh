@@ -8,11 +8,11 @@ O=$R/gpurun_out/round4
 mkdir -p $O
 cd $R
 echo "commit $C" > $O/commit.txt
-python bench.py > $O/bench_line.json 2> $O/bench_stderr.log
+python bench.py --full > $O/bench_line.json 2> $O/bench_stderr.log
 tail -1 $O/bench_line.json | cut -c1-200
-python bench.py --n 100000 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline --sustain-s 0 > $O/bench_line_n100k.json 2>> $O/bench_stderr.log
-python bench.py --mode GPF --no-cpu-baseline --sustain-s 0 > $O/bench_line_gpf.json 2>> $O/bench_stderr.log
-python bench.py --codebase GC --no-cpu-baseline --sustain-s 0 > $O/bench_line_gc.json 2>> $O/bench_stderr.log
+python bench.py --full --n 100000 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline --sustain-s 0 > $O/bench_line_n100k.json 2>> $O/bench_stderr.log
+python bench.py --full --mode GPF --no-cpu-baseline --sustain-s 0 > $O/bench_line_gpf.json 2>> $O/bench_stderr.log
+python bench.py --full --codebase GC --no-cpu-baseline --sustain-s 0 > $O/bench_line_gc.json 2>> $O/bench_stderr.log
 cd /tmp
 prof() {   # tag, then bench args
   tag=$1; shift
@@ -22,7 +22,7 @@ prof() {   # tag, then bench args
 }
 prof bench_streams1 --streams 1 --pairs 64 --steps 3 --warmup 1 --sustain-s 0
 prof bench_default --steps 3 --warmup 1 --sustain-s 0
-prof bench_sustained --steps 10 --warmup 2 --sustain-s 10          # the >= 10 s run: AverageNs of the filter pass over ~600 steps
+prof bench_sustained --steps 10 --warmup 2 --sustain-s 10 --full          # the >= 10 s run: AverageNs of the filter pass over ~600 steps
 grep -o '"sustained": {[^}]*}' /tmp/p_bench_sustained.log > $O/bench_sustained_under_profiler.txt
 prof bench_gpf_streams1 --mode GPF --streams 1 --pairs 64 --steps 3 --warmup 1 --sustain-s 0
 prof bench_n100k_streams1 --n 100000 --streams 1 --pairs 16 --batch 8 --steps 3 --warmup 1 --sustain-s 0

@@ -9,11 +9,11 @@ O=$R/gpurun_out/round5
 mkdir -p $O
 cd $R
 echo "commit $C" > $O/commit.txt
-python bench.py > $O/bench_line.json 2> $O/bench_stderr.log
+python bench.py --full > $O/bench_line.json 2> $O/bench_stderr.log
 tail -1 $O/bench_line.json | cut -c1-200
-python bench.py --n 100000 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline --sustain-s 0 > $O/bench_line_n100k.json 2>> $O/bench_stderr.log
-python bench.py --mode GPF --no-cpu-baseline --sustain-s 0 > $O/bench_line_gpf.json 2>> $O/bench_stderr.log
-python bench.py --codebase GC --no-cpu-baseline --sustain-s 0 > $O/bench_line_gc.json 2>> $O/bench_stderr.log
+python bench.py --full --n 100000 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline --sustain-s 0 > $O/bench_line_n100k.json 2>> $O/bench_stderr.log
+python bench.py --full --mode GPF --no-cpu-baseline --sustain-s 0 > $O/bench_line_gpf.json 2>> $O/bench_stderr.log
+python bench.py --full --codebase GC --no-cpu-baseline --sustain-s 0 > $O/bench_line_gc.json 2>> $O/bench_stderr.log
 cd /tmp
 prof() {   # tag, then bench args
   tag=$1; shift
@@ -23,7 +23,7 @@ prof() {   # tag, then bench args
 }
 prof bench_streams1 --streams 1 --pairs 64 --steps 3 --warmup 1 --sustain-s 0
 prof bench_default --steps 3 --warmup 1 --sustain-s 0
-prof bench_sustained --steps 10 --warmup 2 --sustain-s 10          # the >= 10 s run: AverageNs of the filter pass over ~600 steps
+prof bench_sustained --steps 10 --warmup 2 --sustain-s 10 --full          # the >= 10 s run: AverageNs of the filter pass over ~600 steps
 grep -o '"sustained": {[^}]*}' /tmp/p_bench_sustained.log > $O/bench_sustained_under_profiler.txt
 prof bench_gpf_streams1 --mode GPF --streams 1 --pairs 64 --steps 3 --warmup 1 --sustain-s 0
 prof bench_n100k_streams1 --n 100000 --streams 1 --pairs 16 --batch 8 --steps 3 --warmup 1 --sustain-s 0
@@ -32,9 +32,9 @@ cp $R/profiles/pmc_traffic.json $O/pmc_traffic.json
 ( cd $R; for f in "" "--n 100000" "--mode GPF" "--codebase GC"; do timeout 900 tools/pmc_traffic.sh $C $O/pmc_traffic.json $f; done ) > $O/pmc_traffic.txt 2>&1
 # the workloads other than the headline again, now that their traffic entries exist in profiles/ (bench.py reads them from there)
 cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json
-( cd $R; python bench.py --n 100000 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline --sustain-s 0 > $O/bench_line_n100k.json 2>> $O/bench_stderr.log
-  python bench.py --mode GPF --no-cpu-baseline --sustain-s 0 > $O/bench_line_gpf.json 2>> $O/bench_stderr.log
-  python bench.py --codebase GC --no-cpu-baseline --sustain-s 0 > $O/bench_line_gc.json 2>> $O/bench_stderr.log )
+( cd $R; python bench.py --full --n 100000 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline --sustain-s 0 > $O/bench_line_n100k.json 2>> $O/bench_stderr.log
+  python bench.py --full --mode GPF --no-cpu-baseline --sustain-s 0 > $O/bench_line_gpf.json 2>> $O/bench_stderr.log
+  python bench.py --full --codebase GC --no-cpu-baseline --sustain-s 0 > $O/bench_line_gc.json 2>> $O/bench_stderr.log )
 bash $R/tools/pmc_bench.sh --sustain-s 0 > $O/pmc_sq_summary.txt 2>&1
 bash $R/tools/pmc_passb.sh > $O/pmc_passb_summary.txt 2>&1
 for l in A B; do python $R/bench.py --list $l --no-cpu-baseline > $O/list_${l}_bench_line.json 2>> $O/bench_stderr.log; done

@@ -13,7 +13,7 @@ cd $R
 bash tools/single_pair_prof.sh 2>&1 | grep -v "^$\|rocprim\|at::" | tee $O/single_pair.txt
 python tools/fr_latency.py 2>/dev/null | tee $O/fr_latency.txt
 for b in r5 r6; do echo "== pb_micro_$b"; timeout 300 tools/bin/pb_micro_$b 30000 32 1 | grep -E "need=2 sample stride 16|walk only"; done 2>&1 | tee $O/pb_micro.txt
-python bench.py > $O/bench_line.json 2> $O/bench_stderr.log; python - $O/bench_line.json <<'PY' | tee $O/bench_fields.txt
+python bench.py --full > $O/bench_line.json 2> $O/bench_stderr.log; python - $O/bench_line.json <<'PY' | tee $O/bench_fields.txt
 import json, sys
 d = json.load(open(sys.argv[1]))
 print({k: d.get(k) for k in ("value", "ms_per_step", "ms_per_step_minmedmax", "clock_MHz", "value_at_2.0GHz", "sustained")})

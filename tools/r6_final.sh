@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/r6_final; mkdir -p $O; cd $R
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" 2>&1 | tail -2 | tee $O/smoke.txt
 timeout 1500 python -m pytest tests -q -m gpu 2>&1 | tail -6 | tee $O/gpu_suite.txt
-( time python bench.py > $O/bench_line.json 2> $O/bench_stderr.log ) 2>&1 | tail -3 | tee $O/bench_time.txt
+( time python bench.py --full > $O/bench_line.json 2> $O/bench_stderr.log ) 2>&1 | tail -3 | tee $O/bench_time.txt
 python - $O/bench_line.json <<'PY' | tee $O/bench_fields.txt
 import json, sys
 d = json.load(open(sys.argv[1]))

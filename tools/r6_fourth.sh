@@ -12,7 +12,7 @@ cd $R
 bash tools/single_pair_prof.sh 2>&1 | grep -v "^$" | head -16 | tee $O/single_pair.txt
 timeout 900 tools/pmc_traffic.sh r6-strips2 $O/pmc_100k_strips2.json --n 100000 --opt nn_blocks_batch=6256 2>&1 | tail -5 | tee $O/pmc_100k_strips2.txt
 timeout 900 tools/pmc_traffic.sh r6-strips1 $O/pmc_100k_strips1.json --n 100000 2>&1 | tail -5 | tee $O/pmc_100k_strips1.txt
-python bench.py > $O/bench_line.json 2> $O/bench_stderr.log; python - $O/bench_line.json <<'PY' | tee $O/bench_fields.txt
+python bench.py --full > $O/bench_line.json 2> $O/bench_stderr.log; python - $O/bench_line.json <<'PY' | tee $O/bench_fields.txt
 import json, sys
 d = json.load(open(sys.argv[1]))
 print({k: d.get(k) for k in ("value", "ms_per_step", "ms_per_step_minmedmax", "clock_MHz", "value_at_2.0GHz", "sustained")})

@@ -11,14 +11,14 @@ rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_s1 -o s1 -- pytho
 cp "$(find /tmp/p_s1 -name '*kernel_stats.csv' | head -1)" $O/bench_streams1_kernel_stats.csv
 cd $R
 for nb in 0 6256 9384 12512; do
-  python bench.py --n 100000 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline --sustain-s 0 --opt nn_blocks_batch=$nb > $O/n100k_$nb.json 2>/dev/null
+  python bench.py --full --n 100000 --pairs 32 --steps 3 --warmup 1 --no-cpu-baseline --sustain-s 0 --opt nn_blocks_batch=$nb > $O/n100k_$nb.json 2>/dev/null
   python - $O/n100k_$nb.json $nb <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]
 print(f"100k nn_blocks_batch={sys.argv[2]:6s} pairs/s {d['value']:8.1f} fwd {r['forward_launch_ms']:.3f} rev {r['reverse_launch_ms']:.3f} call {r['call_ms']:.3f} frac {r['frac']:.4f} clock {d.get('clock_MHz')}")
 PY
 done 2>&1 | tee $O/n100k_strips.txt
-python bench.py > $O/bench_line.json 2> $O/bench_stderr.log; python - $O/bench_line.json <<'PY' | tee $O/bench_fields.txt
+python bench.py --full > $O/bench_line.json 2> $O/bench_stderr.log; python - $O/bench_line.json <<'PY' | tee $O/bench_fields.txt
 import json, sys
 d = json.load(open(sys.argv[1]))
 print({k: d.get(k) for k in ("value", "ms_per_step", "ms_per_step_minmedmax", "clock_MHz", "value_at_2.0GHz", "sustained")})

@@ -4,7 +4,7 @@
 # lr_workspace_ransac_stream) against whole calls in flight -- its test, then alternating runs
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/r6_stages; mkdir -p $O; cd $R
 timeout 900 python -m pytest tests/test_gpu_batch.py -x -q 2>&1 | tail -5 | tee $O/tests.txt
-run() { python bench.py --no-cpu-baseline --sustain-s ${SUS:-0} --extra-list none "$@" > $O/l.json 2>$O/err.txt || tail -3 $O/err.txt
+run() { python bench.py --full --no-cpu-baseline --sustain-s ${SUS:-0} --extra-list none "$@" > $O/l.json 2>$O/err.txt || tail -3 $O/err.txt
   python - $O/l.json "$*" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]; s = d.get("sustained") or {}

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/r6_sweep; mkdir -p $O; cd $R
 for rep in 1 2; do
 for cfg in "32 3" "48 2" "48 3" "48 4" "64 2" "64 3" "24 4" "32 4" "32 2"; do set -- $cfg
-  python bench.py --no-cpu-baseline --sustain-s 0 --extra-list none --batch $1 --streams $2 > $O/l.json 2>/dev/null
+  python bench.py --full --no-cpu-baseline --sustain-s 0 --extra-list none --batch $1 --streams $2 > $O/l.json 2>/dev/null
   python - $O/l.json $1 $2 $rep <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]

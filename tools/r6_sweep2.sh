@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box, round 6: calls in flight (streams) for the headline workload, alternating, four repetitions; then the same for the GPF / GC variants
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/r6_sweep2; mkdir -p $O; cd $R
-run() { python bench.py --no-cpu-baseline --sustain-s ${SUS:-0} --extra-list none "$@" > $O/l.json 2>/dev/null
+run() { python bench.py --full --no-cpu-baseline --sustain-s ${SUS:-0} --extra-list none "$@" > $O/l.json 2>/dev/null
   python - $O/l.json "$*" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); r = d["roofline"]; s = d.get("sustained") or {}

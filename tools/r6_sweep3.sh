@@ -6,7 +6,7 @@ for rep in 1 2; do for L in A B; do for s in 6 4 5 8; do
   v=$(python bench.py --list $L --streams $s --hard 0 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; print(json.loads(sys.stdin.read().strip().splitlines()[-1])['value'])")
   echo "rep $rep list $L calls in flight $s: $v"
 done; done; done 2>&1 | tee $O/lists_inflight.txt
-python bench.py > $O/bench_line.json 2>/dev/null; python - $O/bench_line.json <<'PY' | tee $O/bench_fields.txt
+python bench.py --full > $O/bench_line.json 2>/dev/null; python - $O/bench_line.json <<'PY' | tee $O/bench_fields.txt
 import json, sys
 d = json.load(open(sys.argv[1]))
 print({k: d.get(k) for k in ("value", "ms_per_step", "ms_per_step_minmedmax", "clock_MHz", "value_at_2.0GHz", "sustained")}, d["config"]["batched_calls_in_flight_per_gpu"], d["roofline"]["frac"])
