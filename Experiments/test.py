@@ -46,9 +46,9 @@ def get_args(argv=None):
         world_size, rank, do_analysis = 1, 0, True
     p = argparse.ArgumentParser()
     p.add_argument("--dataset", type=str, default="synthetic", help="A, B, S, K, L (balanced sets) or synthetic")
-    p.add_argument("--algo", type=str, default="RANSAC", choices=["RANSAC"])
+    p.add_argument("--algo", type=str, default="RANSAC", choices=["RANSAC", "TEASER"])
     p.add_argument("--codebase", type=str, default="GC", choices=["open3D", "GC"])
-    p.add_argument("--mode", type=str, default="MNN", help="MNN (alias MMN), GPF or no_filter")
+    p.add_argument("--mode", type=str, default="MNN", help="MNN (alias MMN), GPF or no_filter; with --algo TEASER: FAIL_TOLERANT or anything else")
     p.add_argument("--max_samples", type=int, default=None)
     p.add_argument("--iters", type=int, default=None)
     p.add_argument("--phase", type=str, default="test", choices=["train", "validation", "test"])
@@ -108,21 +108,27 @@ def test_subset(args):
     idx = shard.shard_indices(P, args.world_size, args.rank)
     print("process %d, GPU: cuda:%d, %d pairs" % (args.rank, torch.cuda.current_device(), len(idx)))
     t0 = time.time()
-    if args.serial:
+    exact = None
+    if args.algo == "TEASER":
+        from lidarregistration_amd import teaser
+        stats, T, exact = teaser.eval_pairs(source, idx, args, batch=args.batch, nstreams=args.streams or 3, verbose=False)
+    elif args.serial:
         stats, T = harness.eval_pairs_serial(source, idx, args, in_flight=min(args.in_flight, 4), verbose=args.rank == 0)
     else:
         stats, T = harness.eval_pairs(source, idx, args, batch=args.batch, in_flight=args.in_flight, nstreams=args.streams or 3, verbose=False, workers=args.num_workers)
     wall = time.time() - t0
     msg = "process %d: %d pairs in %.2f s end to end (data source + registration + ICP + statistics): %.1f pairs/s" % (args.rank, len(idx), wall, len(idx) / max(wall, 1e-9))
-    if not args.serial:
+    if not args.serial or args.algo == "TEASER":
         r = harness.LAST_RUN
         msg += "; registration region %.3f s = %.1f pairs/s (data %.2f s, ICP %.2f s, statistics %.2f s)" % (
             r["registration_s"], len(idx) / max(r["registration_s"], 1e-9), r["data_s"], r["icp_s"], r["stats_s"])
     print(msg, flush=True)
     with open(f"{args.tmp_file_base}_throughput_{args.world_size}_{args.rank}.txt", "w") as fid:
         fid.write(msg + "\n")
-    np.save(f"{args.tmp_file_base}_res_{args.world_size}_{args.rank}.npy",
-            np.concatenate([stats, T.reshape(-1, 16), harness.LAST_WHOLE_PATH[:, None], np.asarray(idx, np.float64)[:, None]], 1))
+    cols = [stats, T.reshape(-1, 16), harness.LAST_WHOLE_PATH[:, None]]
+    if exact is not None:             # --algo TEASER: did the clique search finish inside its budgets (TEASER_success_or_failure.txt)
+        cols.append(np.asarray(exact, np.float64)[:, None])
+    np.save(f"{args.tmp_file_base}_res_{args.world_size}_{args.rank}.npy", np.concatenate(cols + [np.asarray(idx, np.float64)[:, None]], 1))
 
 
 def analyze_stats(args):
@@ -136,6 +142,10 @@ def analyze_stats(args):
     from lidarregistration_amd import harness
     with open(args.outdir + "raw_stats.columns.txt", "w") as fid:      # (the batched engine's time columns are window shares: say so next to the file)
         fid.write(harness.stats_columns(args.serial))
+    if args.algo == "TEASER" and args.mode == "FAIL_TOLERANT":
+        # TEASER_plus_plus.py:34-49: 1 when the solve finished, 0 when it was cut off (the pair then got the identity), list order
+        with open(args.outdir + "TEASER_success_or_failure.txt", "w") as fid:
+            fid.write("".join("%d\n" % int(v) for v in allrows[:, 39]))
     s = metrics.summarize(stats, args.algo)
     # the reference bills filter + RANSAC + the second neighbour's surcharge (FR.py:117; column 9 above); the whole device path of a
     # call additionally contains the first nearest-neighbour search

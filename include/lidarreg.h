@@ -290,6 +290,73 @@ LR_API size_t lr_voxel_dedup_scratch_bytes(int n);
 LR_API int    lr_voxel_dedup(const double *coords, int n, int32_t *sel, int32_t *n_sel, int32_t *cells, void *scratch,
                              size_t scratch_bytes, void *stream);
 
+/* ---- t1: TEASER++ global registration over M correspondences src[i] <-> tgt[i]  ([M,3] float32 device arrays) ----------------
+ * Replaces the reference's TEASER++ back end (Experiments/algorithms/TEASER_plus_plus.py:78-126, --algo TEASER; TEASER++ is not
+ * vendored, so parity with it is unpinned and the following is the contract, restated in tests/teaser_cpu.py):
+ *  1. consistency graph: i ~ j (i != j) iff | |a_i - a_j| - |b_i - b_j| | <= 2 noise_bound sqrt(cbar2), in fp64 on the promoted
+ *     inputs (differences, (dx*dx + dy*dy) + dz*dz, no FMA, correctly rounded sqrt); the device adjacency is bit-identical to it;
+ *  2. a maximum clique, ascending indices, the same set on every run.  K-core shortcut: when the maximum core number exceeds
+ *     kcore_threshold * M the vertices of maximum core number are returned instead (1.0 disables it).  The search is bounded by
+ *     node_budget branch nodes and time_budget_ms of device clock; when either runs out the best clique found so far is
+ *     returned with exact = 0 (the GPU form of the reference's 10 s kill, TEASER_plus_plus.py:14-59);
+ *  3. rotation: GNC-TLS on the K chain TIMs A_k = a[c_(k+1) mod K] - a[c_k] (B_k on b), noise bound 2 noise_bound (nb2 =
+ *     4 noise_bound^2 cbar2), gnc_factor, max_iterations, cost_threshold; the weighted uncentred fit R = V diag(1,1,det(VU^T)) U^T
+ *     of H = sum w A B^T = U S V^T; TIM k is a rotation inlier iff its final weight >= 0.5;
+ *  4. translation: per axis adaptive voting over x = b - R a of the rotation-inlier clique points with range noise_bound (endpoints
+ *     sorted by value, entries before exits, then index; first minimum of sum_in (x - mean)^2 + noise_bound |out|); a point is a
+ *     translation inlier iff it lies within noise_bound of the estimate on all three axes;
+ *  5. K < 3 or fewer than 3 rotation inliers: status 1 and T = identity (GC_RANSAC.py:51-52).
+ * Other TEASER++ modes (scale estimation, other TIM graphs / rotation solvers / clique modes) are not built and refused.          */
+typedef struct lr_teaser_params {
+    uint32_t struct_size;        /* = sizeof(lr_teaser_params), checked like lr_ransac_params.struct_size                        */
+    int32_t  max_iterations;     /* GNC iterations, 10000 (TEASER_plus_plus.py)                                                   */
+    double   noise_bound;        /* beta, VOXEL_SIZE = 0.3                                                                        */
+    double   cbar2;              /* 1                                                                                             */
+    double   kcore_threshold;    /* 0.5 (upstream default, recalled); in (0, 1], 1.0 disables the shortcut                      */
+    double   gnc_factor;         /* 1.4, > 1                                                                                      */
+    double   cost_threshold;     /* 1e-16                                                                                         */
+    int64_t  node_budget;        /* branch nodes of the exact search, >= 1                                                        */
+    double   time_budget_ms;     /* device-clock budget of the exact search, (0, 3.6e6]                                           */
+    int32_t  rotation_tim_graph; /* 0 = CHAIN (the only graph built)                                                              */
+    int32_t  estimate_scaling;   /* 0 (scale estimation is not built)                                                             */
+} lr_teaser_params;
+
+/* Written to device memory by lr_teaser / lr_teaser_batch (176 bytes). */
+typedef struct lr_teaser_result {
+    double   T[16];              /* cloud 0 -> cloud 1, row-major; identity when status = 1                                      */
+    int32_t  status;             /* 0 ok, 1 = fewer than 3 clique points or rotation inliers                                      */
+    int32_t  K;                  /* clique size                                                                                   */
+    int32_t  exact;              /* 1: the search was not cut by a budget (also with the k-core shortcut); 0: it was              */
+    int32_t  max_core;           /* maximum core number of the graph                                                              */
+    int32_t  lb;                 /* size of the best greedy clique (0 when the shortcut fired)                                   */
+    int32_t  pad0;
+    uint64_t nodes;              /* branch nodes of the exact search                                                              */
+    int32_t  gnc_iters;          /* GNC iterations run (0: all residuals below nb2 / 2 at the start)                              */
+    int32_t  n_rot_inliers;
+    int32_t  n_trans_inliers;
+    int32_t  pad1;
+} lr_teaser_result;
+
+/* Caller-owned device scratch per pair for up to max_m correspondences (0 when max_m is outside 0..32768).  Test hook: after a
+ * call, the consistency graph of pair k is readable at byte 256 of its arena (scratch + k * lr_teaser_scratch_bytes(max m)): row
+ * i < M is ceil(max m / 64) uint64 words apart, bit j of word j / 64 set iff i ~ j (words past ceil(M / 64) are not written).     */
+LR_API size_t lr_teaser_scratch_bytes(int max_m);
+/* m_dev, if not NULL, is a device int32 holding the live M (clamped to 0..m).  clique_out (nullable, room for m int32) receives the
+ * clique, ascending; result->K entries are live.  scratch: >= lr_teaser_scratch_bytes(m) bytes, 256-byte aligned.              */
+LR_API int lr_teaser(const float *src, const float *tgt, int m, const int32_t *m_dev, const lr_teaser_params *p,
+                     lr_teaser_result *result, int32_t *clique_out, void *scratch, size_t scratch_bytes, void *stream);
+/* npairs (1..64) independent problems in one sequence of launches (the pair is a grid dimension); src/tgt/m/m_dev/clique_out are
+ * HOST arrays of length npairs (m_dev and clique_out, and their entries, may be NULL), carried by value into a setup kernel (no
+ * copy: graph-capturable); results is a DEVICE array of npairs blocks; scratch >= npairs * lr_teaser_scratch_bytes(max m).  The
+ * result of pair k is bit-identical to lr_teaser on that pair.                                                                   */
+LR_API int lr_teaser_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
+                           const lr_teaser_params *p, lr_teaser_result *results, int32_t *const *clique_out, void *scratch,
+                           size_t scratch_bytes, void *stream);
+/* Measurement hook: with timing on, every lr_teaser / _batch call records events between its four stages (graph, clique, rotation,
+ * translation); lr_teaser_stage_times gives those of the last call in ms (after synchronising its stream).  Process-wide.        */
+LR_API int lr_teaser_timing(int enable);
+LR_API int lr_teaser_stage_times(float out[4]);
+
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */
 LR_API int lr_workspace_timing(lr_workspace *ws, int enable);

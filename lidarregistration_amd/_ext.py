@@ -20,6 +20,7 @@ SYMBOLS = [
     "lr_workspace_create_batch", "lr_register_batch", "lr_workspace_lists_at", "lr_inlier_mask", "lr_workspace_mask_at",
     "lr_voxel_dedup_scratch_bytes", "lr_voxel_dedup", "lr_workspace_option", "lr_workspace_stage_times", "lr_icp_batch", "lr_workspace_lists_batch",
     "lr_workspace_clock", "lr_debug_fake_current_device",
+    "lr_teaser_scratch_bytes", "lr_teaser", "lr_teaser_batch", "lr_teaser_timing", "lr_teaser_stage_times",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -78,6 +79,28 @@ class PairParams(ctypes.Structure):
             self.ransac.struct_size = ctypes.sizeof(RansacParams)
 
 
+class TeaserParams(ctypes.Structure):
+    """lr_teaser_params with the reference's settings (TEASER_plus_plus.py:78-93) as defaults; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_iterations", ctypes.c_int32), ("noise_bound", ctypes.c_double),
+                ("cbar2", ctypes.c_double), ("kcore_threshold", ctypes.c_double), ("gnc_factor", ctypes.c_double),
+                ("cost_threshold", ctypes.c_double), ("node_budget", ctypes.c_int64), ("time_budget_ms", ctypes.c_double),
+                ("rotation_tim_graph", ctypes.c_int32), ("estimate_scaling", ctypes.c_int32)]
+    DEFAULTS = dict(max_iterations=10000, noise_bound=0.3, cbar2=1.0, kcore_threshold=0.5, gnc_factor=1.4, cost_threshold=1e-16,
+                    node_budget=10 ** 7, time_budget_ms=10000.0)
+
+    def __init__(self, **kw):
+        kw.pop("struct_size", None)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
+
+
+class TeaserResult(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_double * 16), ("status", ctypes.c_int32), ("K", ctypes.c_int32), ("exact", ctypes.c_int32),
+                ("max_core", ctypes.c_int32), ("lb", ctypes.c_int32), ("pad0", ctypes.c_int32), ("nodes", ctypes.c_uint64),
+                ("gnc_iters", ctypes.c_int32), ("n_rot_inliers", ctypes.c_int32), ("n_trans_inliers", ctypes.c_int32),
+                ("pad1", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(TeaserParams) == 72 and ctypes.sizeof(TeaserResult) == 176
 assert ctypes.sizeof(PairResult) == 496 and ctypes.sizeof(RansacParams) == 72 and ctypes.sizeof(PairParams) == 112
 
 _lib = None
@@ -142,6 +165,12 @@ def lib():
         L.lr_workspace_timing.argtypes = [vp, ci]
         if hasattr(L, "lr_workspace_clock"):      # (absent only from older builds loaded through the LIDARREG_LIB development hook)
             L.lr_workspace_clock.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong), ci]
+        L.lr_teaser_scratch_bytes.restype = ctypes.c_size_t
+        L.lr_teaser_scratch_bytes.argtypes = [ci]
+        L.lr_teaser.argtypes = [vp, vp, ci, vp, ctypes.POINTER(TeaserParams), vp, vp, vp, ctypes.c_size_t, vp]
+        L.lr_teaser_batch.argtypes = [ci, pp, pp, ip, pp, ctypes.POINTER(TeaserParams), vp, pp, vp, ctypes.c_size_t, vp]
+        L.lr_teaser_timing.argtypes = [ci]
+        L.lr_teaser_stage_times.argtypes = [ctypes.POINTER(ctypes.c_float * 4)]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib
