@@ -108,26 +108,25 @@ def test_subset(args):
     idx = shard.shard_indices(P, args.world_size, args.rank)
     print("process %d, GPU: cuda:%d, %d pairs" % (args.rank, torch.cuda.current_device(), len(idx)))
     t0 = time.time()
-    exact = None
     if args.algo == "TEASER":
         from lidarregistration_amd import teaser
-        stats, T, exact = teaser.eval_pairs(source, idx, args, batch=args.batch, nstreams=args.streams or 3, verbose=False)
+        run = teaser.eval_pairs(source, idx, args, batch=args.batch, nstreams=args.streams or 3, verbose=False)
     elif args.serial:
-        stats, T = harness.eval_pairs_serial(source, idx, args, in_flight=min(args.in_flight, 4), verbose=args.rank == 0)
+        run = harness.eval_pairs_serial(source, idx, args, in_flight=min(args.in_flight, 4), verbose=args.rank == 0)
     else:
-        stats, T = harness.eval_pairs(source, idx, args, batch=args.batch, in_flight=args.in_flight, nstreams=args.streams or 3, verbose=False, workers=args.num_workers)
+        run = harness.eval_pairs(source, idx, args, batch=args.batch, in_flight=args.in_flight, nstreams=args.streams or 3, verbose=False, workers=args.num_workers)
     wall = time.time() - t0
     msg = "process %d: %d pairs in %.2f s end to end (data source + registration + ICP + statistics): %.1f pairs/s" % (args.rank, len(idx), wall, len(idx) / max(wall, 1e-9))
-    if not args.serial or args.algo == "TEASER":
-        r = harness.LAST_RUN
+    if run.totals is not None:
+        r = run.totals
         msg += "; registration region %.3f s = %.1f pairs/s (data %.2f s, ICP %.2f s, statistics %.2f s)" % (
             r["registration_s"], len(idx) / max(r["registration_s"], 1e-9), r["data_s"], r["icp_s"], r["stats_s"])
     print(msg, flush=True)
     with open(f"{args.tmp_file_base}_throughput_{args.world_size}_{args.rank}.txt", "w") as fid:
         fid.write(msg + "\n")
-    cols = [stats, T.reshape(-1, 16), harness.LAST_WHOLE_PATH[:, None]]
-    if exact is not None:             # --algo TEASER: did the clique search finish inside its budgets (TEASER_success_or_failure.txt)
-        cols.append(np.asarray(exact, np.float64)[:, None])
+    cols = [run.stats, run.T.reshape(-1, 16), run.whole_path[:, None]]
+    if run.exact is not None:         # --algo TEASER: did the clique search finish inside its budgets (TEASER_success_or_failure.txt)
+        cols.append(np.asarray(run.exact, np.float64)[:, None])
     np.save(f"{args.tmp_file_base}_res_{args.world_size}_{args.rank}.npy", np.concatenate(cols + [np.asarray(idx, np.float64)[:, None]], 1))
 
 

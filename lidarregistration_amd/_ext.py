@@ -218,8 +218,8 @@ class Workspace:
     def handle(self):
         return self._h
 
-    def fits(self, n0, n1, iters):
-        return n0 <= self.max_n0 and n1 <= self.max_n1 and iters <= self.max_iters
+    def fits(self, n0, n1, dim, iters):
+        return n0 <= self.max_n0 and n1 <= self.max_n1 and dim == self.dim and iters <= self.max_iters
 
     @property
     def nbytes(self):

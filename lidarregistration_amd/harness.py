@@ -6,6 +6,8 @@ Stats row layout = Experiments/test.py:98-100 (22 columns); the 4x4 transforms a
 """
 import ctypes
 import time
+from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 import torch
@@ -179,14 +181,16 @@ def eval_list_batched(pair_list, indices, args, n=30000, s=1.2, batch=32, nstrea
     size = ctypes.sizeof(_ext.PairResult)
     Ts = np.tile(np.eye(4), (P, 1, 1)); re = np.zeros(P); te = np.zeros(P); n_corr = np.zeros(P, np.int64); n_ids = np.zeros(P, np.int64)
     status = np.zeros(P, np.int64)
+    source = SyntheticSource(len(pair_list["session"]), n=n, s=s, seed=seed, pair_list=pair_list, rho_scale=rho_scale, noise=noise)
+
+    def draw(rows):
+        ps = [source.get_dev(k, dev) for k in rows]
+        return [(p["xyz0"], p["xyz1"], p["feats0"], p["feats1"]) for p in ps], [p["T_gt"] for p in ps]
+
     seconds = 0.0
     for lo in range(0, P, resident):
         rows = indices[lo:lo + resident]
-        pairs, gts = [], []
-        for k in rows:
-            rho = float(np.clip(pair_list["overlap"][k], 0.05, 0.95)) * rho_scale
-            p = synth.make_pair_dev(N=n, rho=rho, s=s, seed=seed + int(k), device=dev, T_gt=pair_list["T_gt"][k], noise=noise)
-            pairs.append((p["xyz0"], p["xyz1"], p["feats0"], p["feats1"])); gts.append(p["T_gt"])
+        pairs, gts = draw(rows)
         outs = torch.zeros((len(rows), size), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
         for st in streams:
@@ -203,7 +207,7 @@ def eval_list_batched(pair_list, indices, args, n=30000, s=1.2, batch=32, nstrea
         hb = host.numpy()
         for j, k in enumerate(rows):
             r = _ext.PairResult.from_buffer_copy(hb[j].tobytes())
-            T = np.array(r.T[:], np.float64).reshape(4, 4) if r.status == 0 else np.eye(4)
+            T = pair_transform(r)
             Ts[lo + j] = T
             re[lo + j] = metrics.rotation_error_deg(T, gts[j]); te[lo + j] = metrics.translation_error_cm(T, gts[j]) / 100.0
             n_corr[lo + j] = r.n_corr; n_ids[lo + j] = r.ransac.n_ids; status[lo + j] = r.status
@@ -214,11 +218,7 @@ def eval_list_batched(pair_list, indices, args, n=30000, s=1.2, batch=32, nstrea
     # each call) -- the throughput loop above keeps several calls in flight and cannot attribute time to stages
     sample = indices[:min(P, 4 * batch)]
     stage = np.zeros(6); timed_pairs = 0
-    pairs = []
-    for k in sample:
-        rho = float(np.clip(pair_list["overlap"][k], 0.05, 0.95)) * rho_scale
-        p = synth.make_pair_dev(N=n, rho=rho, s=s, seed=seed + int(k), device=dev, T_gt=pair_list["T_gt"][k], noise=noise)
-        pairs.append((p["xyz0"], p["xyz1"], p["feats0"], p["feats1"]))
+    pairs, _ = draw(sample)
     outs = torch.zeros((len(sample), size), dtype=torch.uint8, device=dev)
     for rep in range(2):                               # first pass warms up, second is read
         wss[0].timing(True)
@@ -287,6 +287,53 @@ def inlier_ratios_dev(xyz0, xyz1, nn1, c0, c1, n0, n_corr, T_gt):
 _NCORR_OFF = _ext.PairResult.n_corr.offset
 
 
+@dataclass(frozen=True)
+class EvalRun:
+    """What an evaluation engine (eval_pairs, eval_pairs_serial, teaser.eval_pairs) returns.  It unpacks as (stats, T), the
+    engines' return value before the record existed, so `stats, T = eval_pairs(...)` keeps working."""
+    stats: np.ndarray                 # [n,22] float64, the reference's layout (write_row)
+    T: np.ndarray                     # [n,4,4] float64
+    whole_path: np.ndarray            # [n] whole-call device seconds per row (incl. the forward NN, which column 9 does not bill)
+    totals: Optional[dict] = None     # seconds in the data / registration / ICP / statistics phases, pairs (None: --serial)
+    exact: Optional[np.ndarray] = None    # --algo TEASER: 1 when the clique search finished inside its budgets
+
+    def __iter__(self):
+        return iter((self.stats, self.T))
+
+
+def pair_transform(r, field="T"):
+    """A PairResult's 4x4 transform `field` (T or T_icp) in float64: the identity unless the call succeeded (status 0)."""
+    return np.array(getattr(r, field)[:], np.float64).reshape(4, 4) if r.status == 0 else np.eye(4)
+
+
+def write_row(stats, row, T, T_gt, reg_s, data_s, n0, n_corr, ids, ratios=(np.nan, np.nan), icp=None):
+    """Row `row` of a 22-column stats array (Experiments/test.py:96-100) from what an engine decided: success / RE / TE of T
+    (columns 0-2), the billed and the data seconds (9, 10), n0 / n_corr (15, 17) with the inlier ratios (init, filtered) next to
+    them (16, 18), source.ids() (19-21).  icp = (T_icp, seconds) fills columns 11-14; without it column 11 is 0.0 and 12-14 stay NaN."""
+    stats[row, 0] = float(metrics.is_success(T, T_gt))
+    stats[row, 1], stats[row, 2] = metrics.rotation_error_deg(T, T_gt), metrics.translation_error_cm(T, T_gt)
+    stats[row, 9], stats[row, 10], stats[row, 11] = reg_s, data_s, 0.0
+    if icp is not None:                                        # the harness' ICP stage (test.py:183-193)
+        T_icp, stats[row, 11] = icp
+        stats[row, 12] = float(metrics.is_success(T_icp, T_gt))
+        stats[row, 13], stats[row, 14] = metrics.rotation_error_deg(T_icp, T_gt), metrics.translation_error_cm(T_icp, T_gt)
+    stats[row, 15], stats[row, 16], stats[row, 17], stats[row, 18] = n0, ratios[0], n_corr, ratios[1]
+    stats[row, 19], stats[row, 20], stats[row, 21] = ids
+
+
+def slot_workspace(wss, i, n0, n1, dim, iters, headroom=1.0, max_pairs=1, sync=None):
+    """Workspace slot i of an engine: kept while it fits (n0, n1, dim, iters), else closed -- after torch.cuda.synchronize(sync) when
+    a device is given -- and replaced by one with `headroom` x (n0, n1).  Returns True when the slot got a new workspace."""
+    if wss[i] is not None and wss[i].fits(n0, n1, dim, iters):
+        return False
+    if wss[i] is not None:
+        if sync is not None:
+            torch.cuda.synchronize(sync)
+        wss[i].close()
+    wss[i] = _ext.Workspace(int(n0 * headroom), int(n1 * headroom), dim, iters, max_pairs=max_pairs)
+    return True
+
+
 def eval_pairs(source, indices, args, device=None, batch=32, in_flight=6, nstreams=3, verbose=False, workers=8):
     """Register source[k] for k in indices through the BATCHED engine -- what Experiments/test.py:108-234 does pair by pair.
     The list is taken in windows of `in_flight` batches of `batch` rows; per window:
@@ -298,12 +345,12 @@ def eval_pairs(source, indices, args, device=None, batch=32, in_flight=6, nstrea
          its wall time is the window's registration time                                                        -> column 9
       C  ICP (args.icp): one lr_icp_batch per batch on the same workspaces, timed the same way (test.py:183-193) -> column 11
       D  statistics: ground-truth inlier ratios on the device, RE / TE on the host                               -> the rest
-    Returns (stats [n,22] float64, T [n,4,4] float64) in the reference's 22-column layout (test.py:98-100).  Time columns are
+    Returns an EvalRun: stats [n,22] float64 in the reference's 22-column layout (test.py:98-100), T [n,4,4].  Time columns are
     ATTRIBUTED shares of a window (attribute_window_time): the window's registration wall time goes to its calls by their device
     time and to a call's pairs by n0 x n1 (NN stages) and ids examined x correspondences (the rest); column 9 takes off the first
     neighbour's part of the forward NN, which the reference treats as given (matching.py:7-11; the second neighbour's share is
-    calibrated once per cloud-size class, FR.second_nn_share); the whole path is kept in LAST_WHOLE_PATH.  LAST_RUN holds the run's totals (seconds in A, B, C, D; pairs).
-    Results are bit-identical to the one-pair-at-a-time path (eval_pairs_serial; tests/test_gpu_cli.py)."""
+    calibrated once per cloud-size class, FR.second_nn_share); the whole path is returned next to it, with the run's totals (seconds in
+    A, B, C, D; pairs).  Results are bit-identical to the one-pair-at-a-time path (eval_pairs_serial; tests/test_gpu_cli.py)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     params = registration_params(args)
     n = len(indices)
@@ -349,11 +396,8 @@ def eval_pairs(source, indices, args, device=None, batch=32, in_flight=6, nstrea
                 gp = ps[sl]
                 n0s = [int(p["feats0"].shape[0]) for p in gp]; n1s = [int(p["feats1"].shape[0]) for p in gp]
                 d = int(gp[0]["feats0"].shape[1])
-                if wss[i] is None or not wss[i].fits(max(n0s), max(n1s), params.ransac.iters):
-                    if wss[i] is not None:
-                        wss[i].close()
-                    ragged = len(set(n0s + n1s)) > 1          # real data: leave headroom for the next windows
-                    wss[i] = _ext.Workspace(int(max(n0s) * (1.25 if ragged else 1)), int(max(n1s) * (1.25 if ragged else 1)), d, params.ransac.iters, max_pairs=batch)
+                ragged = len(set(n0s + n1s)) > 1          # real data: leave headroom for the next windows
+                if slot_workspace(wss, i, max(n0s), max(n1s), d, params.ransac.iters, headroom=1.25 if ragged else 1.0, max_pairs=batch):
                     seen[i] = None
                 k_big = int(np.argmax(n0s))
                 fresh = fr.share_key(n0s[k_big], n1s[k_big], dev) not in fr._SHARE
@@ -416,27 +460,10 @@ def eval_pairs(source, indices, args, device=None, batch=32, in_flight=6, nstrea
                                                           [r.ransac.n_ids for r in res_g], [r.n_corr for r in res_g])
                 for j, row in enumerate(g["rows"]):
                     r = res_g[j]
-                    T = np.array(r.T[:], np.float64).reshape(4, 4) if r.status == 0 else np.eye(4)
-                    gt = T_gt[j]
-                    re, te = metrics.rotation_error_deg(T, gt), metrics.translation_error_cm(T, gt)
-                    sess, si, ti = source.ids(indices[row])
-                    stats[row, 0] = float(re < metrics.RE_THRE_DEG and te < metrics.TE_THRE_CM)
-                    stats[row, 1], stats[row, 2] = re, te
-                    stats[row, 9] = billed_g[j]
+                    Ts[row] = pair_transform(r)
                     whole_path[row] = whole_g[j]
-                    stats[row, 10], stats[row, 11] = t_data / len(rows_w), 0.0
-                    if want_icp:
-                        T_icp = np.array(r.T_icp[:], np.float64).reshape(4, 4) if r.status == 0 else np.eye(4)
-                        re_i, te_i = metrics.rotation_error_deg(T_icp, gt), metrics.translation_error_cm(T_icp, gt)
-                        stats[row, 11] = t_icp / len(rows_w)
-                        stats[row, 12] = float(re_i < metrics.RE_THRE_DEG and te_i < metrics.TE_THRE_CM)
-                        stats[row, 13], stats[row, 14] = re_i, te_i
-                    stats[row, 15] = g["n0"][j]
-                    stats[row, 16] = ri[j]
-                    stats[row, 17] = int(r.n_corr)
-                    stats[row, 18] = rf[j]
-                    stats[row, 19], stats[row, 20], stats[row, 21] = sess, si, ti
-                    Ts[row] = T
+                    write_row(stats, row, Ts[row], T_gt[j], billed_g[j], t_data / len(rows_w), g["n0"][j], int(r.n_corr), source.ids(indices[row]),
+                              ratios=(ri[j], rf[j]), icp=(pair_transform(r, "T_icp"), t_icp / len(rows_w)) if want_icp else None)
             totals["stats_s"] += time.time() - t0
             if verbose:
                 print(f"{time.strftime('%m/%d %H:%M:%S')} Finished pair:{rows_w[-1]}/{n}  ({len(rows_w) / max(t_reg, 1e-9):.0f} pairs/s in the registration region)", flush=True)
@@ -450,10 +477,7 @@ def eval_pairs(source, indices, args, device=None, batch=32, in_flight=6, nstrea
         for w in wss:
             if w is not None:
                 w.close()
-    global LAST_WHOLE_PATH, LAST_RUN
-    LAST_WHOLE_PATH = whole_path
-    LAST_RUN = totals
-    return stats, Ts
+    return EvalRun(stats, Ts, whole_path, totals)
 
 
 def attribute_window_time(t_window, call_ms, all_calls_ms, fwd_ms, rev_ms, share, n0, n1, n_ids, n_corr):
@@ -489,8 +513,8 @@ def stats_columns(serial):
 
 def eval_pairs_serial(source, indices, args, device=None, in_flight=4, verbose=False):
     """The one-pair-at-a-time call pattern of the reference harness (one lr_register_pair per list row, `in_flight` pairs on
-    separate streams): kept as the cross-check of eval_pairs (same data source, same statistics code) and for latency
-    measurements.  Returns (stats [n,22] float64, T [n,4,4] float64)."""
+    separate streams): kept as the cross-check of eval_pairs (same data source, same row writer) and for latency
+    measurements.  Returns an EvalRun without totals."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     params = registration_params(args)
     n = len(indices)
@@ -506,32 +530,19 @@ def eval_pairs_serial(source, indices, args, device=None, in_flight=4, verbose=F
         row, out, ev0, ev1, p, t_data, n0, icp_buf, ev2 = slots[s]
         p["_end"].synchronize()
         r = fr.read_result(out)
-        T = np.array(r.T[:], np.float64).reshape(4, 4) if r.status == 0 else np.eye(4)
+        Ts[row] = pair_transform(r)
         ri, rf = (float(v.cpu()[0]) for v in p["_ratios"])
-        re, te = metrics.rotation_error_deg(T, p["T_gt"]), metrics.translation_error_cm(T, p["T_gt"])
-        sess, si, ti = source.ids(indices[row])
-        stats[row, 0] = float(re < metrics.RE_THRE_DEG and te < metrics.TE_THRE_CM)
-        stats[row, 1], stats[row, 2] = re, te
         # column 9 = what FR.py:117 bills: filter + RANSAC (+ refit) + the second neighbour's surcharge, from the library's own stage
-        # events of this call; the whole device path (forward NN included) is kept next to it (LAST_WHOLE_PATH)
+        # events of this call; the whole device path (forward NN included) is kept next to it
         ms, _ = wss[s].stage_times()
         d_call, d_fwd = ms[0] - seen[s][0], ms[1] - seen[s][1]
         seen[s] = ms
         whole_path[row] = ev0.elapsed_time(ev1) * 1e-3
-        stats[row, 9] = max(whole_path[row] - d_fwd * 1e-3 * (1.0 - p["_share"]), 0.0)
-        stats[row, 10], stats[row, 11] = t_data, 0.0
-        if icp_buf is not None:                                # stats columns 11-14 = the harness' ICP stage (test.py:183-193)
-            T_icp = icp_buf[0].cpu().numpy().reshape(4, 4) if r.status == 0 else np.eye(4)
-            re_i, te_i = metrics.rotation_error_deg(T_icp, p["T_gt"]), metrics.translation_error_cm(T_icp, p["T_gt"])
-            stats[row, 11] = ev1.elapsed_time(ev2) * 1e-3
-            stats[row, 12] = float(re_i < metrics.RE_THRE_DEG and te_i < metrics.TE_THRE_CM)
-            stats[row, 13], stats[row, 14] = re_i, te_i
-        stats[row, 15] = n0
-        stats[row, 16] = ri
-        stats[row, 17] = int(r.n_corr)
-        stats[row, 18] = rf
-        stats[row, 19], stats[row, 20], stats[row, 21] = sess, si, ti
-        Ts[row] = T
+        icp = None
+        if icp_buf is not None:
+            icp = (icp_buf[0].cpu().numpy().reshape(4, 4) if r.status == 0 else np.eye(4), ev1.elapsed_time(ev2) * 1e-3)
+        write_row(stats, row, Ts[row], p["T_gt"], max(whole_path[row] - d_fwd * 1e-3 * (1.0 - p["_share"]), 0.0), t_data, n0, int(r.n_corr),
+                  source.ids(indices[row]), ratios=(ri, rf), icp=icp)
         slots[s] = None
         if verbose:
             print(f"{time.strftime('%m/%d %H:%M:%S')} Finished pair:{row}/{n}", flush=True)
@@ -545,11 +556,7 @@ def eval_pairs_serial(source, indices, args, device=None, in_flight=4, verbose=F
             p = source.get_dev(k, dev)
         t_data = time.time() - t0
         n0, n1, d = p["feats0"].shape[0], p["feats1"].shape[0], p["feats0"].shape[1]
-        if wss[s] is None or not wss[s].fits(n0, n1, params.ransac.iters):
-            if wss[s] is not None:
-                torch.cuda.synchronize(dev)
-                wss[s].close()
-            wss[s] = _ext.Workspace(int(n0 * 1.25), int(n1 * 1.25), d, params.ransac.iters)
+        if slot_workspace(wss, s, n0, n1, d, params.ransac.iters, headroom=1.25, sync=dev):
             seen[s] = None
         with torch.cuda.stream(streams[s]):
             x0, x1, f0, f1 = p["xyz0"], p["xyz1"], p["feats0"], p["feats1"]
@@ -589,10 +596,4 @@ def eval_pairs_serial(source, indices, args, device=None, in_flight=4, verbose=F
     for w in wss:
         if w is not None:
             w.close()
-    global LAST_WHOLE_PATH
-    LAST_WHOLE_PATH = whole_path
-    return stats, Ts
-
-
-LAST_WHOLE_PATH = None      # eval_pairs: whole-call device seconds per row of its last run
-LAST_RUN = None             # eval_pairs: totals of its last run (seconds in the data / registration / ICP / statistics phases, pairs)
+    return EvalRun(stats, Ts, whole_path)

@@ -30,7 +30,7 @@ def workspace(n0, n1, iters=0, dim=32):
     """Cached per-device workspace large enough for (n0, n1, iters)."""
     dev = torch.cuda.current_device()
     ws = _WS.get(dev)
-    if ws is None or not ws.handle or not ws.fits(n0, n1, iters) or ws.dim != dim:
+    if ws is None or not ws.handle or not ws.fits(n0, n1, dim, iters):
         grow = (ws.max_n0, ws.max_n1, ws.max_iters) if ws is not None else (0, 0, 0)
         if ws is not None:
             _WS.pop(dev, None)

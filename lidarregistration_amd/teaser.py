@@ -11,7 +11,7 @@ import time
 import numpy as np
 import torch
 
-from . import _ext, metrics
+from . import _ext, harness
 from .matching import _f32, _stream
 
 RESULT_BYTES = ctypes.sizeof(_ext.TeaserResult)
@@ -130,10 +130,9 @@ def _budget_ms(args):
 
 
 def eval_pairs(source, indices, args, device=None, batch=32, nstreams=3, verbose=False):
-    """--algo TEASER over `indices` of `source`.  Returns (stats [n,22], T [n,4,4], exact [n]); sets harness.LAST_WHOLE_PATH /
-    LAST_RUN like harness.eval_pairs.  Column 9 = the pair's share of its window's solve (device time of the lr_teaser_batch call
-    split evenly) + the second neighbour's surcharge (0); the NN / GPF time is not billed (TEASER_plus_plus.py:109-123)."""
-    from . import harness
+    """--algo TEASER over `indices` of `source`.  Returns a harness.EvalRun with totals and `exact`.  Column 9 = the pair's share of
+    its window's solve (device time of the lr_teaser_batch call split evenly) + the second neighbour's surcharge (0); the NN / GPF
+    time is not billed (TEASER_plus_plus.py:109-123)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     n = len(indices)
     stats = np.full((n, 22), np.nan)
@@ -141,73 +140,58 @@ def eval_pairs(source, indices, args, device=None, batch=32, nstreams=3, verbose
     exact = np.ones(n, np.int32)
     whole = np.zeros(n)
     streams = [torch.cuda.Stream(device=dev) for _ in range(max(1, nstreams))]
-    wss = {}
+    wss = [None] * batch
     tot = dict(data_s=0.0, registration_s=0.0, icp_s=0.0, stats_s=0.0, pairs=n)
     use_icp = getattr(args, "icp", True)
-    for w0 in range(0, n, batch):
-        rows = list(range(w0, min(n, w0 + batch)))
-        t0 = time.time()
-        pairs = [source.get_dev(indices[r], dev) for r in rows]
-        torch.cuda.synchronize(dev)
-        t1 = time.time()
-        corr = []
-        for j, p in enumerate(pairs):
-            s = streams[j % len(streams)]
-            n0, n1, d = p["feats0"].shape[0], p["feats1"].shape[0], p["feats0"].shape[1]
-            ws = wss.get(j)
-            if ws is None or not ws.fits(n0, n1, 1) or ws.dim != d:
-                if ws is not None:
-                    torch.cuda.synchronize(dev); ws.close()
-                ws = wss[j] = _ext.Workspace(int(n0 * 1.25), int(n1 * 1.25), d, 1)
-            with torch.cuda.stream(s):
-                corr.append(correspondences_dev(p["xyz0"], p["xyz1"], p["feats0"], p["feats1"], args, ws, s.cuda_stream))
-        torch.cuda.synchronize(dev)
-        counts = [int(v) for v in torch.stack([c[2][0] for c in corr]).cpu()]
-        srcs = [p["xyz0"][c[0][:m].long()] for p, c, m in zip(pairs, corr, counts)]
-        tgts = [p["xyz1"][c[1][:m].long()] for p, c, m in zip(pairs, corr, counts)]
-        out, ms = teaser_batch_dev(srcs, tgts, time_budget_ms=_budget_ms(args))
-        t2 = time.time()
-        for j, r in enumerate(rows):
-            T, info, _ = out[j]
-            exact[r] = info["exact"]
-            if getattr(args, "mode", None) == "FAIL_TOLERANT" and not info["exact"]:
-                T = np.eye(4)
-            Ts[r] = T
-            T_gt = pairs[j]["T_gt"]
-            re, te = metrics.rotation_error_deg(T, T_gt), metrics.translation_error_cm(T, T_gt)
-            stats[r, 0] = float(re < metrics.RE_THRE_DEG and te < metrics.TE_THRE_CM)
-            stats[r, 1], stats[r, 2] = re, te
-            stats[r, 9] = ms * 1e-3 / len(rows)
-            whole[r] = stats[r, 9]
-            stats[r, 10] = (t1 - t0) / len(rows)
-            stats[r, 15], stats[r, 17] = pairs[j]["feats0"].shape[0], counts[j]
-            stats[r, 19], stats[r, 20], stats[r, 21] = source.ids(indices[r])
-        if use_icp:
+    # whatever ends the loop, every workspace is released on the way out (harness.eval_pairs)
+    try:
+        for w0 in range(0, n, batch):
+            rows = list(range(w0, min(n, w0 + batch)))
+            t0 = time.time()
+            pairs = [source.get_dev(indices[r], dev) for r in rows]
+            torch.cuda.synchronize(dev)
+            t1 = time.time()
+            corr = []
+            for j, p in enumerate(pairs):
+                s = streams[j % len(streams)]
+                harness.slot_workspace(wss, j, p["feats0"].shape[0], p["feats1"].shape[0], p["feats0"].shape[1], 1, headroom=1.25, sync=dev)
+                with torch.cuda.stream(s):
+                    corr.append(correspondences_dev(p["xyz0"], p["xyz1"], p["feats0"], p["feats1"], args, wss[j], s.cuda_stream))
+            torch.cuda.synchronize(dev)
+            counts = [int(v) for v in torch.stack([c[2][0] for c in corr]).cpu()]
+            srcs = [p["xyz0"][c[0][:m].long()] for p, c, m in zip(pairs, corr, counts)]
+            tgts = [p["xyz1"][c[1][:m].long()] for p, c, m in zip(pairs, corr, counts)]
+            out, ms = teaser_batch_dev(srcs, tgts, time_budget_ms=_budget_ms(args))
+            t2 = time.time()
             for j, r in enumerate(rows):
+                T, info, _ = out[j]
+                exact[r] = info["exact"]
+                if getattr(args, "mode", None) == "FAIL_TOLERANT" and not info["exact"]:
+                    T = np.eye(4)
+                Ts[r] = T
+                whole[r] = ms * 1e-3 / len(rows)
                 p = pairs[j]
-                n0, n1 = p["xyz0"].shape[0], p["xyz1"].shape[0]
-                Tin = torch.from_numpy(np.ascontiguousarray(Ts[r].reshape(16))).to(dev)
-                T_icp = torch.empty(16, dtype=torch.float64, device=dev)
-                res_icp = torch.empty(ctypes.sizeof(_ext.IcpResult), dtype=torch.uint8, device=dev)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                _ext.check(_ext.lib().lr_icp(wss[j].handle, p["xyz0"].data_ptr(), n0, p["xyz1"].data_ptr(), n1, Tin.data_ptr(),
-                                             2 * VOXEL_SIZE, 30, 1e-6, 1e-6, T_icp.data_ptr(), res_icp.data_ptr(), _stream()))
-                e1.record(); e1.synchronize()
-                Ti = T_icp.cpu().numpy().reshape(4, 4)
-                re_i, te_i = metrics.rotation_error_deg(Ti, p["T_gt"]), metrics.translation_error_cm(Ti, p["T_gt"])
-                stats[r, 11] = e0.elapsed_time(e1) * 1e-3
-                stats[r, 12] = float(re_i < metrics.RE_THRE_DEG and te_i < metrics.TE_THRE_CM)
-                stats[r, 13], stats[r, 14] = re_i, te_i
-        else:
-            stats[rows, 11] = 0.0
-        t3 = time.time()
-        tot["data_s"] += t1 - t0; tot["registration_s"] += t2 - t1; tot["icp_s"] += t3 - t2
-        if verbose:
-            print(f"{time.strftime('%m/%d %H:%M:%S')} Finished pair:{rows[-1]}/{n}", flush=True)
-    torch.cuda.synchronize(dev)
-    for ws in wss.values():
-        ws.close()
-    harness.LAST_WHOLE_PATH = whole
-    harness.LAST_RUN = tot
-    return stats, Ts, exact
+                harness.write_row(stats, r, T, p["T_gt"], whole[r], (t1 - t0) / len(rows), p["feats0"].shape[0], counts[j], source.ids(indices[r]),
+                                  icp=_icp(wss[j], p, Ts[r], dev) if use_icp else None)
+            tot["data_s"] += t1 - t0; tot["registration_s"] += t2 - t1; tot["icp_s"] += time.time() - t2
+            if verbose:
+                print(f"{time.strftime('%m/%d %H:%M:%S')} Finished pair:{rows[-1]}/{n}", flush=True)
+        torch.cuda.synchronize(dev)
+    finally:
+        for ws in wss:
+            if ws is not None:
+                ws.close()
+    return harness.EvalRun(stats, Ts, whole, tot, exact)
+
+
+def _icp(ws, p, T, dev):
+    """lr_icp from T on the current stream, timed by its own events: (T_icp 4x4, seconds)."""
+    Tin = torch.from_numpy(np.ascontiguousarray(T.reshape(16))).to(dev)
+    T_icp = torch.empty(16, dtype=torch.float64, device=dev)
+    res_icp = torch.empty(ctypes.sizeof(_ext.IcpResult), dtype=torch.uint8, device=dev)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    _ext.check(_ext.lib().lr_icp(ws.handle, p["xyz0"].data_ptr(), p["xyz0"].shape[0], p["xyz1"].data_ptr(), p["xyz1"].shape[0], Tin.data_ptr(),
+                                 2 * VOXEL_SIZE, 30, 1e-6, 1e-6, T_icp.data_ptr(), res_icp.data_ptr(), _stream()))
+    e1.record(); e1.synchronize()
+    return T_icp.cpu().numpy().reshape(4, 4), e0.elapsed_time(e1) * 1e-3
