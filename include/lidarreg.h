@@ -301,7 +301,8 @@ LR_API int    lr_voxel_dedup(const double *coords, int n, int32_t *sel, int32_t 
  *     returned with exact = 0 (the GPU form of the reference's 10 s kill, TEASER_plus_plus.py:14-59);
  *  3. rotation: GNC-TLS on the K chain TIMs A_k = a[c_(k+1) mod K] - a[c_k] (B_k on b), noise bound 2 noise_bound (nb2 =
  *     4 noise_bound^2 cbar2), gnc_factor, max_iterations, cost_threshold; the weighted uncentred fit R = V diag(1,1,det(VU^T)) U^T
- *     of H = sum w A B^T = U S V^T; TIM k is a rotation inlier iff its final weight >= 0.5;
+ *     of H = sum w A B^T = U S V^T; where H has rank <= 1 (collinear or coincident points, s2 <= 1e-14 s1) the optimum is not unique
+ *     and R is any proper rotation attaining it (R = I for H = 0); TIM k is a rotation inlier iff its final weight >= 0.5;
  *  4. translation: per axis adaptive voting over x = b - R a of the rotation-inlier clique points with range noise_bound (endpoints
  *     sorted by value, entries before exits, then index; first minimum of sum_in (x - mean)^2 + noise_bound |out|); a point is a
  *     translation inlier iff it lies within noise_bound of the estimate on all three axes;

@@ -85,8 +85,9 @@ __device__ __forceinline__ void lr_jacobi4_maxvec(double A[4][4], double q[4])
 }
 
 // Largest-eigenvalue eigenvector in closed form: Newton on the characteristic polynomial from Gershgorin's bound + the adjugate column with the
-// largest diagonal cofactor (oracle/oracle.c, horn4_maxvec_newton: same text, same bits; derivation and accuracy there).  0: the caller runs
-// Jacobi (zero / non-finite matrix, or a double largest eigenvalue).
+// largest diagonal cofactor, recomputed once at the Rayleigh quotient of that vector (oracle/oracle.c, horn4_maxvec_newton: same text, same
+// bits; derivation and accuracy there: <= 32 eps kappa, tests/test_rigid_hp_cpu.py).  0: the caller runs Jacobi (zero / non-finite matrix, or
+// a double largest eigenvalue).
 __device__ __forceinline__ double lr_det3_(double a, double b, double c, double d, double e, double f, double g, double h, double i)
 {
     return (a * (e * i - f * h) - b * (d * i - f * g)) + c * (d * h - e * g);
@@ -123,26 +124,37 @@ __device__ __forceinline__ int lr_horn4_maxvec_newton(const double N[4][4], doub
         if (!(nl < lam)) break;
         lam = nl;
     }
-    /* B = N - lam I; its adjugate is (a multiple of) v v^T */
-    const double A = a - lam, B = b - lam, C = c - lam, D = d - lam;
-    const double c00 = lr_det3_(B, n12, n13, n12, C, n23, n13, n23, D);
-    const double c11 = lr_det3_(A, n02, n03, n02, C, n23, n03, n23, D);
-    const double c22 = lr_det3_(A, n01, n03, n01, B, n13, n03, n13, D);
-    const double c33 = lr_det3_(A, n01, n02, n01, B, n12, n02, n12, C);
-    const double c01 = -lr_det3_(n01, n12, n13, n02, C, n23, n03, n23, D);
-    const double c02 = lr_det3_(n01, B, n13, n02, n12, n23, n03, n13, D);
-    const double c03 = -lr_det3_(n01, B, n12, n02, n12, C, n03, n13, n23);
-    const double c12 = -lr_det3_(A, n01, n03, n02, n12, n23, n03, n13, D);
-    const double c13 = lr_det3_(A, n01, n02, n02, n12, C, n03, n13, n23);
-    const double c23 = -lr_det3_(A, n01, n02, n01, B, n12, n03, n13, n23);
-    double w = c00, x = c01, y = c02, z = c03, best = fabs(c00);
-    if (fabs(c11) > best) { best = fabs(c11); w = c01; x = c11; y = c12; z = c13; }
-    if (fabs(c22) > best) { best = fabs(c22); w = c02; x = c12; y = c22; z = c23; }
-    if (fabs(c33) > best) { best = fabs(c33); w = c03; x = c13; y = c23; z = c33; }
-    if (!(best > 1.0e-6 * ((bound * bound) * bound))) return 0;
-    const double nn = sqrt(((w * w + x * x) + y * y) + z * z);
-    if (!(nn > 0.0)) return 0;
-    q[0] = w / nn; q[1] = x / nn; q[2] = y / nn; q[3] = z / nn;
+    /* B = N - lam I; its adjugate is (a multiple of) v v^T.  Pass 0 takes lam from Newton, pass 1 the Rayleigh quotient of pass 0's
+     * vector (oracle.c) */
+    double w = 0.0, x = 0.0, y = 0.0, z = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1) {
+            const double y0 = ((a * w + n01 * x) + n02 * y) + n03 * z, y1 = ((n01 * w + b * x) + n12 * y) + n13 * z;
+            const double y2 = ((n02 * w + n12 * x) + c * y) + n23 * z, y3 = ((n03 * w + n13 * x) + n23 * y) + d * z;
+            lam = ((w * y0 + x * y1) + y * y2) + z * y3;
+        }
+        const double A = a - lam, B = b - lam, C = c - lam, D = d - lam;
+        const double c00 = lr_det3_(B, n12, n13, n12, C, n23, n13, n23, D);
+        const double c11 = lr_det3_(A, n02, n03, n02, C, n23, n03, n23, D);
+        const double c22 = lr_det3_(A, n01, n03, n01, B, n13, n03, n13, D);
+        const double c33 = lr_det3_(A, n01, n02, n01, B, n12, n02, n12, C);
+        const double c01 = -lr_det3_(n01, n12, n13, n02, C, n23, n03, n23, D);
+        const double c02 = lr_det3_(n01, B, n13, n02, n12, n23, n03, n13, D);
+        const double c03 = -lr_det3_(n01, B, n12, n02, n12, C, n03, n13, n23);
+        const double c12 = -lr_det3_(A, n01, n03, n02, n12, n23, n03, n13, D);
+        const double c13 = lr_det3_(A, n01, n02, n02, n12, C, n03, n13, n23);
+        const double c23 = -lr_det3_(A, n01, n02, n01, B, n12, n03, n13, n23);
+        double best = fabs(c00);
+        w = c00; x = c01; y = c02; z = c03;
+        if (fabs(c11) > best) { best = fabs(c11); w = c01; x = c11; y = c12; z = c13; }
+        if (fabs(c22) > best) { best = fabs(c22); w = c02; x = c12; y = c22; z = c23; }
+        if (fabs(c33) > best) { best = fabs(c33); w = c03; x = c13; y = c23; z = c33; }
+        if (!(best > 1.0e-6 * ((bound * bound) * bound))) return 0;
+        const double nn = sqrt(((w * w + x * x) + y * y) + z * z);
+        if (!(nn > 0.0)) return 0;
+        w = w / nn; x = x / nn; y = y / nn; z = z / nn;
+    }
+    q[0] = w; q[1] = x; q[2] = y; q[3] = z;
     return 1;
 }
 

@@ -509,8 +509,9 @@ __global__ void __launch_bounds__(64) tz_search_kernel(tz_args g, long long node
 
 // ---- 3. rotation: GNC-TLS on the chain TIMs --------------------------------------------------------------------------------
 // R = argmin sum w |B - R A|^2 from H = sum w A B^T = U S V^T: R = V diag(1, 1, det(V U^T)) U^T.  One-sided Jacobi on H (columns of
-// H V orthogonalised), singular values sorted descending; a vanishing third column of U is completed by a cross product.  Its own
-// routine: lr_kabsch.h (which RANSAC's results depend on) is not touched.
+// H V orthogonalised), singular values sorted descending.  Rank-deficient H (collinear or coincident points) has no unique optimum; any
+// proper rotation attaining it is returned: s2 <= 1e-14 s1 (zero or rounding noise) completes u2 by an axis orthogonal to u1, s3 <= 1e-14
+// s1 completes u3 = u1 x u2, and H = 0 gives R = I.  Its own routine: lr_kabsch.h (which RANSAC's results depend on) is not touched.
 __device__ void tz_svd_rot(const double H[9], double R[9])
 {
     double M[9], V[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };
@@ -540,12 +541,29 @@ __device__ void tz_svd_rot(const double H[9], double R[9])
     for (int j = 0; j < 3; ++j) s[j] = sqrt(M[j] * M[j] + M[3 + j] * M[3 + j] + M[6 + j] * M[6 + j]);
     for (int i = 0; i < 3; ++i)
         for (int j = i + 1; j < 3; ++j) if (s[ord[j]] > s[ord[i]]) { const int tmp = ord[i]; ord[i] = ord[j]; ord[j] = tmp; }
+    const double s1 = s[ord[0]];
+    if (!(s1 > 0.0)) {                              // rank 0 (H = 0): every rotation attains the optimum 0
+        for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+        return;
+    }
     double U[9], Vs[9];
     for (int j = 0; j < 3; ++j) {
         const int o = ord[j];
         for (int r = 0; r < 3; ++r) { Vs[3 * r + j] = V[3 * r + o]; U[3 * r + j] = s[o] > 0 ? M[3 * r + o] / s[o] : 0.0; }
     }
-    if (!(s[ord[2]] > 1e-14 * s[ord[0]])) {        // rank <= 2: u3 = u1 x u2
+    if (!(s[ord[1]] > 1e-14 * s1)) {                // rank 1: the second column of H V is zero or rounding noise along u1; u2 = any unit
+        int k = 0;                                  // vector orthogonal to u1, from the axis where u1 is smallest
+        if (fabs(U[3]) < fabs(U[3 * k])) k = 1;
+        if (fabs(U[6]) < fabs(U[3 * k])) k = 2;
+        double e[3] = { 0.0, 0.0, 0.0 };
+        e[k] = 1.0;
+        const double dot = U[3 * k];
+        double nn = 0.0;
+        for (int r = 0; r < 3; ++r) { U[3 * r + 1] = e[r] - dot * U[3 * r]; nn += U[3 * r + 1] * U[3 * r + 1]; }
+        nn = sqrt(nn);
+        for (int r = 0; r < 3; ++r) U[3 * r + 1] /= nn;
+    }
+    if (!(s[ord[2]] > 1e-14 * s1)) {               // rank <= 2: u3 = u1 x u2
         U[2] = U[3] * U[7] - U[6] * U[4];
         U[5] = U[6] * U[1] - U[0] * U[7];
         U[8] = U[0] * U[4] - U[3] * U[1];

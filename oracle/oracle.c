@@ -281,12 +281,14 @@ static void jacobi4_maxvec(double A[4][4], double q[4])
  *   2. its largest root by Newton's iteration from Gershgorin's upper bound: beyond the largest root the polynomial is positive, increasing
  *      and convex, so the iterates decrease monotonically and the loop ends when one no longer does (6-8 steps of one division; a close
  *      second eigenvalue -- near-collinear points -- takes 20-30);
- *   3. the eigenvector as the column of adj(N - lambda I) = prod(lambda_k - lambda) v v^T with the largest diagonal cofactor.
+ *   3. the eigenvector as the column of adj(N - lambda I) = prod(lambda_k - lambda) v v^T with the largest diagonal cofactor;
+ *   4. step 3 once more at the Rayleigh quotient lambda' = q^T N q of that vector.
  * Only + - * / sqrt in a fixed order: bit-identical here and in lidarregistration_amd/csrc/lr_kabsch.h (same text).  Returns 0 -- the caller
- * runs Jacobi -- when the matrix is zero / not finite or the adjugate is at rounding level (a double largest eigenvalue: collinear points).
- * Accuracy: the root carries eps |N| (|N| / gap), the vector eps (|N| / gap)^2, gap = distance to the second eigenvalue: 1e-15 rad for
- * the refit's thousands of points, <= 2e-6 rad over 200 000 random three-point samples, and where it is worse the rotation about the
- * points' common line is not determined by float32 coordinates either (tests/test_oracle_ransac.py). */
+ * runs Jacobi -- when the matrix is zero / not finite or either adjugate is at rounding level (a double largest eigenvalue: collinear points).
+ * Accuracy: the root of the characteristic polynomial carries eps |N| kappa (kappa = |N| / gap, gap = distance to the second eigenvalue),
+ * so step 3's vector is off by delta ~ eps kappa^2 -- up to 1e5 times what the conditioning allows for near-collinear samples.  The
+ * Rayleigh quotient is accurate to |N| (delta^2 / kappa + eps), so step 4's vector is off by eps kappa + delta^2: the backward-stable
+ * bound that Jacobi attains.  tests/test_rigid_hp_cpu.py holds both paths to angle <= 32 eps kappa against a 40-digit SVD Kabsch. */
 static inline double det3_(double a, double b, double c, double d, double e, double f, double g, double h, double i)
 {
     return (a * (e * i - f * h) - b * (d * i - f * g)) + c * (d * h - e * g);
@@ -323,26 +325,37 @@ static int horn4_maxvec_newton(const double N[4][4], double q[4])
         if (!(nl < lam)) break;
         lam = nl;
     }
-    /* B = N - lam I; its adjugate is (a multiple of) v v^T */
-    const double A = a - lam, B = b - lam, C = c - lam, D = d - lam;
-    const double c00 = det3_(B, n12, n13, n12, C, n23, n13, n23, D);
-    const double c11 = det3_(A, n02, n03, n02, C, n23, n03, n23, D);
-    const double c22 = det3_(A, n01, n03, n01, B, n13, n03, n13, D);
-    const double c33 = det3_(A, n01, n02, n01, B, n12, n02, n12, C);
-    const double c01 = -det3_(n01, n12, n13, n02, C, n23, n03, n23, D);
-    const double c02 = det3_(n01, B, n13, n02, n12, n23, n03, n13, D);
-    const double c03 = -det3_(n01, B, n12, n02, n12, C, n03, n13, n23);
-    const double c12 = -det3_(A, n01, n03, n02, n12, n23, n03, n13, D);
-    const double c13 = det3_(A, n01, n02, n02, n12, C, n03, n13, n23);
-    const double c23 = -det3_(A, n01, n02, n01, B, n12, n03, n13, n23);
-    double w = c00, x = c01, y = c02, z = c03, best = fabs(c00);
-    if (fabs(c11) > best) { best = fabs(c11); w = c01; x = c11; y = c12; z = c13; }
-    if (fabs(c22) > best) { best = fabs(c22); w = c02; x = c12; y = c22; z = c23; }
-    if (fabs(c33) > best) { best = fabs(c33); w = c03; x = c13; y = c23; z = c33; }
-    if (!(best > 1.0e-6 * ((bound * bound) * bound))) return 0;
-    const double nn = sqrt(((w * w + x * x) + y * y) + z * z);
-    if (!(nn > 0.0)) return 0;
-    q[0] = w / nn; q[1] = x / nn; q[2] = y / nn; q[3] = z / nn;
+    /* B = N - lam I; its adjugate is (a multiple of) v v^T.  Pass 0 takes lam from Newton, pass 1 the Rayleigh quotient of pass 0's
+     * vector (see above) */
+    double w = 0.0, x = 0.0, y = 0.0, z = 0.0;
+    for (int pass = 0; pass < 2; ++pass) {
+        if (pass == 1) {
+            const double y0 = ((a * w + n01 * x) + n02 * y) + n03 * z, y1 = ((n01 * w + b * x) + n12 * y) + n13 * z;
+            const double y2 = ((n02 * w + n12 * x) + c * y) + n23 * z, y3 = ((n03 * w + n13 * x) + n23 * y) + d * z;
+            lam = ((w * y0 + x * y1) + y * y2) + z * y3;
+        }
+        const double A = a - lam, B = b - lam, C = c - lam, D = d - lam;
+        const double c00 = det3_(B, n12, n13, n12, C, n23, n13, n23, D);
+        const double c11 = det3_(A, n02, n03, n02, C, n23, n03, n23, D);
+        const double c22 = det3_(A, n01, n03, n01, B, n13, n03, n13, D);
+        const double c33 = det3_(A, n01, n02, n01, B, n12, n02, n12, C);
+        const double c01 = -det3_(n01, n12, n13, n02, C, n23, n03, n23, D);
+        const double c02 = det3_(n01, B, n13, n02, n12, n23, n03, n13, D);
+        const double c03 = -det3_(n01, B, n12, n02, n12, C, n03, n13, n23);
+        const double c12 = -det3_(A, n01, n03, n02, n12, n23, n03, n13, D);
+        const double c13 = det3_(A, n01, n02, n02, n12, C, n03, n13, n23);
+        const double c23 = -det3_(A, n01, n02, n01, B, n12, n03, n13, n23);
+        double best = fabs(c00);
+        w = c00; x = c01; y = c02; z = c03;
+        if (fabs(c11) > best) { best = fabs(c11); w = c01; x = c11; y = c12; z = c13; }
+        if (fabs(c22) > best) { best = fabs(c22); w = c02; x = c12; y = c22; z = c23; }
+        if (fabs(c33) > best) { best = fabs(c33); w = c03; x = c13; y = c23; z = c33; }
+        if (!(best > 1.0e-6 * ((bound * bound) * bound))) return 0;
+        const double nn = sqrt(((w * w + x * x) + y * y) + z * z);
+        if (!(nn > 0.0)) return 0;
+        w = w / nn; x = x / nn; y = y / nn; z = z / nn;
+    }
+    q[0] = w; q[1] = x; q[2] = y; q[3] = z;
     return 1;
 }
 
