@@ -191,3 +191,62 @@ def planted(m, n_in, seed, noise=0.02, outlier_scale=10.0, beta=0.3):
     perm = rng.permutation(m)
     T = np.eye(4); T[:3, :3], T[:3, 3] = R, t
     return a[perm].astype(np.float32), b[perm].astype(np.float32), T, perm
+
+
+GREEDY_WAVES = 16
+
+
+def greedy_clique(A, seed, first):
+    """The greedy clique of DESIGN §10 from `seed`: candidates of the boolean mask `first` (the max-core vertices) in ascending order,
+    then any vertex in ascending order; a vertex joins when it is adjacent to every member so far.  Ascending list."""
+    P = A[seed].copy()
+    C = [int(seed)]
+    for mask in (first, np.ones(len(P), bool)):
+        last = -1
+        while True:
+            cand = np.nonzero(P & mask)[0]
+            cand = cand[cand > last]
+            if len(cand) == 0:
+                break
+            last = int(cand[0])
+            C.append(last)
+            P &= A[last]
+    return sorted(C)
+
+
+def reduction_model(A, kcore_threshold=0.5):
+    """Plain model of the clique stage's reduction as DESIGN §10 states it.  A: boolean adjacency (tc.graph).  Returns
+    (max_core, LB, nU, nR, exit):
+      core numbers from networkx; 'shortcut' when max_core > kcore_threshold * M (LB, nU, nR = 0);
+      otherwise LB = the largest of 16 greedy cliques (clique j seeded at the (j mod nmax)-th max-core vertex, first maximum kept),
+      S = vertices of core number >= LB, U = those of S adjacent to every other vertex of S (nU), R = S \\ U (nR);
+      nR = 0: 'empty_universal' when nU > LB else 'empty_incumbent';
+      nR > 0: the search runs with target LB - nU: 'search_target_nonpositive' when that is <= 0, else 'search'.
+    'empty_universal' cannot happen: with nR = 0, S is a clique of nU vertices; a vertex outside S has core number < LB <= nU - 1, so
+    no k-core with k >= nU - 1 holds one, every vertex of S has core number exactly nU - 1 = max_core, the max-core set is S, and the
+    first greedy pass collects all of it: LB >= nU.  'search_target_nonpositive' cannot happen either: a vertex of U is adjacent to all
+    of the max-core subgraph, so it belongs to it (U lies in the max-core set) and is adjacent to every seed; the first pass of every
+    greedy clique therefore collects all of U, and the clique ends with at least one more vertex (the seed when it is not in U, else a
+    vertex adjacent to all of U, of which R holds at least one): LB >= nU + 1.  Both labels are kept so that a model run would show
+    them if an argument were wrong."""
+    m = A.shape[0]
+    if m == 0:
+        return 0, 0, 0, 0, "empty_graph"
+    core = nx.core_number(to_nx(A))
+    core = np.array([core[v] for v in range(m)])
+    maxcore = int(core.max())
+    if float(maxcore) > kcore_threshold * float(m):
+        return maxcore, 0, 0, 0, "shortcut"
+    first = core == maxcore
+    top = np.nonzero(first)[0]
+    LB = 0
+    for j in range(GREEDY_WAVES):
+        LB = max(LB, len(greedy_clique(A, top[j % len(top)], first)))
+    S = core >= LB
+    nr = int(S.sum())
+    deg = A[np.ix_(S, S)].sum(1) if nr else np.zeros(0, int)
+    nU = int((deg == nr - 1).sum())
+    nR = nr - nU
+    if nR == 0:
+        return maxcore, LB, nU, 0, "empty_universal" if nU > LB else "empty_incumbent"
+    return maxcore, LB, nU, nR, "search_target_nonpositive" if LB - nU <= 0 else "search"
