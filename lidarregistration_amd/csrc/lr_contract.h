@@ -1,16 +1,43 @@
-// fp64 Kabsch through Horn's quaternion form (largest eigenvector in closed form; cyclic Jacobi for degenerate input), written with + - * / sqrt only and an explicit op order so
-// that the device result is bit-identical to oracle/oracle.c (both compiled with -ffp-contract=off).
-// Reference semantics: R = V diag(1,1,det) U^T, t = mu_B - R mu_A (Experiments/models/common.py:7-45).
-#pragma once
-#include <hip/hip_runtime.h>
+/*
+ * lr_contract.h -- the fp64 arithmetic contract, one text for the HIP kernels and the CPU oracle.
+ *
+ * Plain C99 that is also valid HIP C++: the .hip files next to it compile it with hipcc for gfx950, oracle/oracle.c with gcc.
+ * Everything here is written with + - * / sqrt only and an explicit operation order, and both sides build with
+ * -ffp-contract=off, so the device and the oracle produce the same bits.  The GPU-against-oracle tests check for these routines that two compilers and two
+ * machines turn this one text into the same bits; the mathematics is verified independently (tests/rigid_hp.py: 40-digit SVD
+ * Kabsch; the numpy-SVD test of tests/test_oracle_golden.py; goldens G7 / G11).
+ * The dependency points from the test infrastructure to the product: oracle/ includes this file, nothing under
+ * lidarregistration_amd/ includes anything from oracle/.
+ *
+ * What deliberately stays as two texts, one per side:
+ *   - Philox, sampling, ELC, the PROSAC table: the device forms are different algorithms (__umulhi; the squared-length ELC that
+ *     takes square roots only inside a 1e-13 band; a parallel prefix sum for the growth table).  There the oracle is an
+ *     independent restatement.
+ *   - the point-form moment loops (kabsch_sample<NS>, the LO trial fit over sh.pts, kabsch_points_kernel, orc_kabsch_points,
+ *     hypothesis_T): they read different types (fp64 arrays, fp32 LDS records, weights), and the LO loop is rolled on purpose to
+ *     avoid spills; a shared template would be new machinery in a kernel at its register limits.
+ *   - eff_params: the structs differ (orc_ransac_params has no struct_size) and the device entry refuses lo_trials > 20 where the
+ *     oracle clamps it.  Same rule, two texts.
+ */
+#ifndef LR_CONTRACT_H
+#define LR_CONTRACT_H
+
+#if defined(__HIPCC__)
+#  include <hip/hip_runtime.h>
+#  define LRC_FN     __host__ __device__ __forceinline__
+#  define LRC_UNROLL _Pragma("unroll")
+#else
+#  define LRC_FN     static inline
+#  define LRC_UNROLL
+#endif
 #include <math.h>
 #include <string.h>
 
-// ------------------------------------------------------------------ logarithm for the decisions (fp64, + - * / only)
-// The confidence exit and the SPRT design compare against values made of logarithms; libm's and ocml's log differ in the last
-// place, which can flip such a comparison on one side only (found by tools/soak_gc.py).  Same text as oracle.c (det_log):
-// x = m 2^e with m in [sqrt(1/2), sqrt(2)), log x = e ln 2 + 2 atanh((m - 1) / (m + 1)), the odd series up to t^25.
-__host__ __device__ __forceinline__ double lr_det_log(double x)
+/* ------------------------------------------------------------------ logarithm for the decisions (fp64, + - * / only) */
+/* The confidence exit and the SPRT design compare against values made of logarithms; libm's and ocml's log differ in the last
+ * place, which can flip such a comparison on one side only (found by tools/soak_gc.py).
+ * x = m 2^e with m in [sqrt(1/2), sqrt(2)), log x = e ln 2 + 2 atanh((m - 1) / (m + 1)), the odd series up to t^25. */
+LRC_FN double lr_det_log(double x)
 {
     if (!(x > 0.0)) return x == 0.0 ? -HUGE_VAL : NAN;
     if (x > 1.7976931348623157e308) return HUGE_VAL;      /* +inf */
@@ -31,19 +58,43 @@ __host__ __device__ __forceinline__ double lr_det_log(double x)
     return (double)e * 0.6931471805599453 + (2.0 * t) * s;
 }
 
-// ------------------------------------------------------------------ Kabsch (fp64, + - * / sqrt only)
-#define LR_JACOBI_SWEEPS 10      // upper bound; sweeps stop once the off-diagonal mass is below 1e-15 of the diagonal
+/* ------------------------------------------------------------------ SPRT design (sources and the test itself: oracle.c, sprt_test) */
+#define LR_SPRT_HORIZON 256      /* the test runs over the first LR_SPRT_HORIZON correspondences in list order */
+#define LR_SPRT_EPS0 0.1
+#define LR_SPRT_DELTA0 0.01
 
-__device__ __forceinline__ void lr_jacobi4_maxvec(double A[4][4], double q[4])
+/* A solves A = K + ln A,  K = t_M C / m_S + 1 (t_M = 200 verifications per model estimate, m_S = 1 model per sample) */
+LRC_FN double lr_sprt_threshold(double eps, double delta)
+{
+    const double C = (1.0 - delta) * lr_det_log((1.0 - delta) / (1.0 - eps)) + delta * lr_det_log(delta / eps);
+    const double K = (200.0 * C) / 1.0 + 1.0;
+    double A = K;
+    for (int i = 0; i < 10; ++i) A = K + lr_det_log(A);
+    return A;
+}
+
+/* ------------------------------------------------------------------ local optimisation (algorithm and sources: oracle.c, lo_optimise / lo_polish) */
+#define LR_LO_ROUNDS 10          /* rounds of one local optimisation (default of lo_rounds) */
+#define LR_LO_TRIALS 20          /* least-squares fits per round (default and upper bound of lo_trials) */
+#define LR_LO_SAMPLE 21          /* points per fit: 7 x the minimal sample */
+#define LR_LO_POLISH 10          /* fits of the final iterated least squares */
+
+/* ------------------------------------------------------------------ Kabsch (fp64, + - * / sqrt only) */
+/* Kabsch through Horn's quaternion form.  Reference semantics: R = V diag(1,1,det) U^T, t = mu_B - R mu_A
+ * (Experiments/models/common.py:7-45). */
+#define LR_JACOBI_SWEEPS 10      /* upper bound; sweeps stop once the off-diagonal mass is below 1e-15 of the diagonal */
+
+/* Largest-eigenvalue eigenvector of a symmetric 4x4 by cyclic Jacobi: the path for degenerate input. */
+LRC_FN void lr_jacobi4_maxvec(double A[4][4], double q[4])
 {
     double V[4][4] = { { 1, 0, 0, 0 }, { 0, 1, 0, 0 }, { 0, 0, 1, 0 }, { 0, 0, 0, 1 } };
     for (int sweep = 0; sweep < LR_JACOBI_SWEEPS; ++sweep) {
         double off2 = ((((A[0][1] * A[0][1] + A[0][2] * A[0][2]) + A[0][3] * A[0][3]) + A[1][2] * A[1][2]) + A[1][3] * A[1][3]) + A[2][3] * A[2][3];
         double dia2 = ((A[0][0] * A[0][0] + A[1][1] * A[1][1]) + A[2][2] * A[2][2]) + A[3][3] * A[3][3];
         if (off2 <= 1e-30 * dia2) break;
-#pragma unroll
+LRC_UNROLL
         for (int p = 0; p < 3; ++p)
-#pragma unroll
+LRC_UNROLL
             for (int r = p + 1; r < 4; ++r) {
                 double apq = A[p][r];
                 if (apq != 0.0) {
@@ -58,7 +109,7 @@ __device__ __forceinline__ void lr_jacobi4_maxvec(double A[4][4], double q[4])
                     A[p][p] = A[p][p] - h;
                     A[r][r] = A[r][r] + h;
                     A[p][r] = 0.0; A[r][p] = 0.0;
-#pragma unroll
+LRC_UNROLL
                     for (int k = 0; k < 4; ++k) {
                         if (k == p || k == r) continue;
                         double g = A[k][p], f = A[k][r];
@@ -67,7 +118,7 @@ __device__ __forceinline__ void lr_jacobi4_maxvec(double A[4][4], double q[4])
                         A[k][p] = gn; A[p][k] = gn;
                         A[k][r] = fn; A[r][k] = fn;
                     }
-#pragma unroll
+LRC_UNROLL
                     for (int k = 0; k < 4; ++k) {
                         double g = V[k][p], f = V[k][r];
                         V[k][p] = g - s * (f + g * tau);
@@ -77,22 +128,32 @@ __device__ __forceinline__ void lr_jacobi4_maxvec(double A[4][4], double q[4])
             }
     }
     double w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0], best = A[0][0];
-#pragma unroll
+LRC_UNROLL
     for (int k = 1; k < 4; ++k)
         if (A[k][k] > best) { best = A[k][k]; w = V[0][k]; x = V[1][k]; y = V[2][k]; z = V[3][k]; }
     double nn = sqrt(((w * w + x * x) + y * y) + z * z);
     q[0] = w / nn; q[1] = x / nn; q[2] = y / nn; q[3] = z / nn;
 }
 
-// Largest-eigenvalue eigenvector in closed form: Newton on the characteristic polynomial from Gershgorin's bound + the adjugate column with the
-// largest diagonal cofactor, recomputed once at the Rayleigh quotient of that vector (oracle/oracle.c, horn4_maxvec_newton: same text, same
-// bits; derivation and accuracy there: <= 32 eps kappa, tests/test_rigid_hp_cpu.py).  0: the caller runs Jacobi (zero / non-finite matrix, or
-// a double largest eigenvalue).
-__device__ __forceinline__ double lr_det3_(double a, double b, double c, double d, double e, double f, double g, double h, double i)
+/* Largest-eigenvalue eigenvector of a symmetric 4x4 in closed form (the cyclic Jacobi above is a chain of 36-48 dependent rotations of 4
+ * divisions and 2 square roots -- 60 us of one lane for the hypothesis fits, 50 for the refit).
+ *   1. the characteristic polynomial from the trace, the principal 2x2 / 3x3 minors and the determinant;
+ *   2. its largest root by Newton's iteration from Gershgorin's upper bound: beyond the largest root the polynomial is positive, increasing
+ *      and convex, so the iterates decrease monotonically and the loop ends when one no longer does (6-8 steps of one division; a close
+ *      second eigenvalue -- near-collinear points -- takes 20-30);
+ *   3. the eigenvector as the column of adj(N - lambda I) = prod(lambda_k - lambda) v v^T with the largest diagonal cofactor;
+ *   4. step 3 once more at the Rayleigh quotient lambda' = q^T N q of that vector.
+ * Returns 0 -- the caller runs Jacobi -- when the matrix is zero / not finite or either adjugate is at rounding level (a double largest
+ * eigenvalue: collinear points).
+ * Accuracy: the root of the characteristic polynomial carries eps |N| kappa (kappa = |N| / gap, gap = distance to the second eigenvalue),
+ * so step 3's vector is off by delta ~ eps kappa^2 -- up to 1e5 times what the conditioning allows for near-collinear samples.  The
+ * Rayleigh quotient is accurate to |N| (delta^2 / kappa + eps), so step 4's vector is off by eps kappa + delta^2: the backward-stable
+ * bound that Jacobi attains.  tests/test_rigid_hp_cpu.py holds both paths to angle <= 32 eps kappa against a 40-digit SVD Kabsch. */
+LRC_FN double lr_det3_(double a, double b, double c, double d, double e, double f, double g, double h, double i)
 {
     return (a * (e * i - f * h) - b * (d * i - f * g)) + c * (d * h - e * g);
 }
-__device__ __forceinline__ int lr_horn4_maxvec_newton(const double N[4][4], double q[4])
+LRC_FN int lr_horn4_maxvec_newton(const double N[4][4], double q[4])
 {
     const double a = N[0][0], b = N[1][1], c = N[2][2], d = N[3][3];
     const double n01 = N[0][1], n02 = N[0][2], n03 = N[0][3], n12 = N[1][2], n13 = N[1][3], n23 = N[2][3];
@@ -125,7 +186,7 @@ __device__ __forceinline__ int lr_horn4_maxvec_newton(const double N[4][4], doub
         lam = nl;
     }
     /* B = N - lam I; its adjugate is (a multiple of) v v^T.  Pass 0 takes lam from Newton, pass 1 the Rayleigh quotient of pass 0's
-     * vector (oracle.c) */
+     * vector (see above) */
     double w = 0.0, x = 0.0, y = 0.0, z = 0.0;
     for (int pass = 0; pass < 2; ++pass) {
         if (pass == 1) {
@@ -158,8 +219,8 @@ __device__ __forceinline__ int lr_horn4_maxvec_newton(const double N[4][4], doub
     return 1;
 }
 
-// H[a][b] = sum (p-cp)_a (q-cq)_b  ->  T (row-major 4x4, q ~ R p + t)
-__device__ __forceinline__ void lr_rt_from_cov(const double H[3][3], const double cp[3], const double cq[3], double T[16])
+/* H = sum (p - cp)(q - cq)^T  (3x3, row = source axis, col = target axis)  ->  T (row-major 4x4, q ~ R p + t) */
+LRC_FN void lr_rt_from_cov(const double H[3][3], const double cp[3], const double cq[3], double T[16])
 {
     double Sxx = H[0][0], Sxy = H[0][1], Sxz = H[0][2];
     double Syx = H[1][0], Syy = H[1][1], Syz = H[1][2];
@@ -176,7 +237,7 @@ __device__ __forceinline__ void lr_rt_from_cov(const double H[3][3], const doubl
     R[0][0] = 1.0 - 2.0 * (y * y + z * z); R[0][1] = 2.0 * (x * y - w * z);       R[0][2] = 2.0 * (x * z + w * y);
     R[1][0] = 2.0 * (x * y + w * z);       R[1][1] = 1.0 - 2.0 * (x * x + z * z); R[1][2] = 2.0 * (y * z - w * x);
     R[2][0] = 2.0 * (x * z - w * y);       R[2][1] = 2.0 * (y * z + w * x);       R[2][2] = 1.0 - 2.0 * (x * x + y * y);
-#pragma unroll
+LRC_UNROLL
     for (int a = 0; a < 3; ++a) {
         double rc = (R[a][0] * cp[0] + R[a][1] * cp[1]) + R[a][2] * cp[2];
         T[4 * a + 0] = R[a][0]; T[4 * a + 1] = R[a][1]; T[4 * a + 2] = R[a][2];
@@ -185,3 +246,15 @@ __device__ __forceinline__ void lr_rt_from_cov(const double H[3][3], const doubl
     T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
 }
 
+/* Raw moments mom = { n, sum p [3], sum q [3], sum p q^T [9] } (what the refit, ICP and all-inlier LO fits accumulate)  ->  T */
+LRC_FN void lr_rt_from_moments(const double mom[16], double T[16])
+{
+    const double n = mom[0];
+    double cp[3], cq[3], H[3][3];
+    for (int a = 0; a < 3; ++a) { cp[a] = mom[1 + a] / n; cq[a] = mom[4 + a] / n; }
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) H[a][b] = mom[7 + 3 * a + b] - (n * cp[a]) * cq[b];
+    lr_rt_from_cov(H, cp, cq, T);
+}
+
+#endif /* LR_CONTRACT_H */

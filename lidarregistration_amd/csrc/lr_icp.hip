@@ -12,7 +12,7 @@
 // acquire around a ticket counter) sums the partials in fixed order, solves Kabsch, composes the transform and decides
 // convergence.  Later launches of a converged pair return at their first instruction.
 #include "lr_internal.h"
-#include "lr_kabsch.h"
+#include "lr_contract.h"
 #include <math.h>
 
 #define LR_ICP_NB 32768          // hash buckets (power of two)
@@ -201,11 +201,8 @@ icp_iter_kernel(const float *__restrict__ src, int n0, const float *__restrict__
     if (k >= max_iter || n < 3.0) done = true;
     state[20] = fitness; state[21] = rmse; state[22] = n;
     if (!done) {
-        double cp[3], cq[3], H[3][3], U[16];
-        for (int a = 0; a < 3; ++a) { cp[a] = mom[1 + a] / n; cq[a] = mom[4 + a] / n; }
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) H[a][b] = mom[7 + 3 * a + b] - (n * cp[a]) * cq[b];
-        lr_rt_from_cov(H, cp, cq, U);
+        double U[16];
+        lr_rt_from_moments(mom, U);
         // T <- U * T
         double Tn[12];
         for (int a = 0; a < 3; ++a) {

@@ -35,7 +35,7 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
     }
 }
 
-#include "lr_kabsch.h"
+#include "lr_contract.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -306,18 +306,6 @@ ransac_fit_kernel(const float *__restrict__ corr8, int m_max, const int32_t *__r
 // correspondences in list order as a wave-uniform stream (scalar loads); a wave leaves as soon as all its models are
 // decided.  Survivors are appended to a second dense model list (their order does not matter: the winner is chosen by
 // score and hypothesis id); the consistent / verified point counts of the rejected models feed the next batch's design.
-#define LR_SPRT_HORIZON 256
-#define LR_SPRT_EPS0 0.1
-#define LR_SPRT_DELTA0 0.01
-__device__ __forceinline__ double lr_sprt_threshold(double eps, double delta)
-{
-    const double C = (1.0 - delta) * lr_det_log((1.0 - delta) / (1.0 - eps)) + delta * lr_det_log(delta / eps);
-    const double K = (200.0 * C) / 1.0 + 1.0;
-    double A = K;
-    for (int i = 0; i < 10; ++i) A = K + lr_det_log(A);
-    return A;
-}
-
 __global__ void __launch_bounds__(256)
 ransac_sprt_kernel(const float *__restrict__ corr8, int m_max, const int32_t *__restrict__ m_dev, float thr2,
                    const float *__restrict__ models, const double *__restrict__ models64, const int32_t *__restrict__ model_h,
@@ -867,26 +855,22 @@ ransac_final_kernel(const uint32_t *__restrict__ score_cnt, const unsigned long 
 
 // ------------------------------------------------------------------ local optimisation (GC-RANSAC, --GC_LO) + final polish
 // One block of 1024 threads per pair; see oracle/oracle.c (lo_optimise / lo_polish) for the algorithm and its sources.
-//   mode 0 (after a batch whose winner became the best model): <= LO_ROUNDS rounds of { inlier list of the model; LO_TRIALS
-//          least-squares fits on LO_SAMPLE inliers each (all of them when there are no more: one fit); every fit scored over
+//   mode 0 (after a batch whose winner became the best model): <= LR_LO_ROUNDS rounds of { inlier list of the model; LR_LO_TRIALS
+//          least-squares fits on LR_LO_SAMPLE inliers each (all of them when there are no more: one fit); every fit scored over
 //          ALL correspondences by 1024 / trials threads; the best replaces the model if strictly better, else stop }, then the
 //          confidence test on the optimised model
 //   mode 1 (once, after the last batch): iterated least squares over all inliers
 // All sums that decide anything are integers (order independent); the fp64 moments of the all-inlier fits run as 1024 strided
 // partials + a fixed halving tree, the order oracle.c reproduces, so the models agree bit for bit.
-#define LO_ROUNDS 10
-#define LO_TRIALS 20
-#define LO_SAMPLE 21
-#define LO_POLISH 10
 #define LO_THREADS 1024
 
 #define LO_MAXIT 32              // records (two correspondences) per thread and pass of the list builder
 struct lo_shared {
-    double T[LO_TRIALS][12];         // candidate models of the round (fp64)
-    __attribute__((aligned(16))) float Rt[LO_TRIALS][12];         // ... rounded for the scoring arithmetic
-    float pts[LO_TRIALS][LO_SAMPLE][6];     // the sampled correspondences (fetched by one lane each, summed by one thread per trial)
-    unsigned cnt[LO_TRIALS];
-    unsigned long long ssq[LO_TRIALS];
+    double T[LR_LO_TRIALS][12];         // candidate models of the round (fp64)
+    __attribute__((aligned(16))) float Rt[LR_LO_TRIALS][12];         // ... rounded for the scoring arithmetic
+    float pts[LR_LO_TRIALS][LR_LO_SAMPLE][6];     // the sampled correspondences (fetched by one lane each, summed by one thread per trial)
+    unsigned cnt[LR_LO_TRIALS];
+    unsigned long long ssq[LR_LO_TRIALS];
     double red[4][LO_THREADS];       // block reduction of the fp64 moments, four components at a time
     double mom[16];
     double curT[12];                 // model under optimisation
@@ -900,7 +884,7 @@ struct lo_shared {
     float box[6];
     int box_state;                   // 0: not computed yet; 1: valid; -1: a non-finite coordinate (no bound)
     int nNear, near_ok;
-    double eps[LO_TRIALS];
+    double eps[LR_LO_TRIALS];
     double baseT[12];                // the model near8 was copied around
 };
 
@@ -1091,12 +1075,8 @@ __device__ bool lo_fit_all(lo_shared &sh, const float *__restrict__ corr8, const
     __syncthreads();
     const bool ok = sh.mom[0] >= 3.0;
     if (ok && tid == 0) {
-        const double nn = sh.mom[0];
-        double cp[3], cq[3], H[3][3], T[16];
-        for (int a = 0; a < 3; ++a) { cp[a] = sh.mom[1 + a] / nn; cq[a] = sh.mom[4 + a] / nn; }
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) H[a][b] = sh.mom[7 + 3 * a + b] - (nn * cp[a]) * cq[b];
-        lr_rt_from_cov(H, cp, cq, T);
+        double T[16];
+        lr_rt_from_moments(sh.mom, T);
         for (int k = 0; k < 12; ++k) { sh.T[0][k] = T[k]; sh.Rt[0][k] = (float)T[k]; }
     }
     __syncthreads();
@@ -1104,13 +1084,13 @@ __device__ bool lo_fit_all(lo_shared &sh, const float *__restrict__ corr8, const
 }
 
 // score sh.Rt[0 .. ntrial) over all m correspondences -> sh.cnt / sh.ssq (integer atomics in LDS): three forms.
-// One model (the polish, or a round with at most LO_SAMPLE inliers): one thread per 64-byte record (two correspondences), 32-bit sums
+// One model (the polish, or a round with at most LR_LO_SAMPLE inliers): one thread per 64-byte record (two correspondences), 32-bit sums
 // per thread (the caller guarantees that a thread's share of the correspondences cannot overflow them), one wave reduction and one
 // LDS atomic per wave at the end.
 __device__ void lo_score_one(lo_shared &sh, const float *__restrict__ corr8, int m, float thr2)
 {
     const int tid = threadIdx.x, lane = tid & 63;
-    if (tid < LO_TRIALS) { sh.cnt[tid] = 0u; sh.ssq[tid] = 0ull; }
+    if (tid < LR_LO_TRIALS) { sh.cnt[tid] = 0u; sh.ssq[tid] = 0ull; }
     __syncthreads();
     const float *Rt = sh.Rt[0];
     const f32x2 R00 = { Rt[0], Rt[0] }, R01 = { Rt[1], Rt[1] }, R02 = { Rt[2], Rt[2] }, TX = { Rt[3], Rt[3] };
@@ -1141,7 +1121,7 @@ __device__ void lo_score_one(lo_shared &sh, const float *__restrict__ corr8, int
     __syncthreads();
 }
 
-// all LO_TRIALS models of a round: the arithmetic of ransac_score_kernel (one LANE per model, two correspondences per packed
+// all LR_LO_TRIALS models of a round: the arithmetic of ransac_score_kernel (one LANE per model, two correspondences per packed
 // step), with three correspondence streams side by side in a wave -- lanes [20 s, 20 s + 20) apply the 20 models to the records
 // 3 w + s, 3 w + s + 48, ... of wave w -- so 60 of the 64 lanes work and a wave's three 64-byte records come in as three
 // broadcast global_load_dwordx4 per lane.  12 coefficient + 12 record registers, sums per lane, 48 LDS atomics per model at the end.
@@ -1149,9 +1129,9 @@ __device__ void lo_score_lanes_range(lo_shared &sh, const float *__restrict__ co
 {
     // (adds to sh.cnt / sh.ssq: the caller zeroes them; records [rec_begin, rec_end))
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int NS = 64 / LO_TRIALS;                 // streams per wave (3)
+    constexpr int NS = 64 / LR_LO_TRIALS;                 // streams per wave (3)
     constexpr int STRIDE = NS * (LO_THREADS / 64);     // records between two steps of a stream (48)
-    const int t = lane % LO_TRIALS, st = lane / LO_TRIALS;
+    const int t = lane % LR_LO_TRIALS, st = lane / LR_LO_TRIALS;
     const bool act = st < NS;
     const f32x4 *rp = reinterpret_cast<const f32x4 *>(sh.Rt[t]);
     const f32x4 r0 = rp[0], r1 = rp[1], r2 = rp[2];
@@ -1186,7 +1166,7 @@ __device__ void lo_score_lanes_range(lo_shared &sh, const float *__restrict__ co
 }
 __device__ void lo_score_lanes(lo_shared &sh, const float *__restrict__ corr8, int m, float thr2)
 {
-    if (threadIdx.x < LO_TRIALS) { sh.cnt[threadIdx.x] = 0u; sh.ssq[threadIdx.x] = 0ull; }
+    if (threadIdx.x < LR_LO_TRIALS) { sh.cnt[threadIdx.x] = 0u; sh.ssq[threadIdx.x] = 0ull; }
     __syncthreads();
     lo_score_lanes_range(sh, corr8, m, thr2, 0, (m + 1) >> 1);
 }
@@ -1205,7 +1185,7 @@ __device__ void lo_score_lanes(lo_shared &sh, const float *__restrict__ corr8, i
 #define LO_CHUNK_REC 384
 #define LO_JOBS 16
 struct lr_lo_job { int32_t next_chunk, done_chunks, nchunks, pad0;
-                   float Rt[LO_TRIALS][12]; unsigned cnt[LO_TRIALS]; unsigned long long ssq[LO_TRIALS]; };
+                   float Rt[LR_LO_TRIALS][12]; unsigned cnt[LR_LO_TRIALS]; unsigned long long ssq[LR_LO_TRIALS]; };
 struct lr_lo_ctl { int32_t phase, pad[3]; lr_lo_job job[LO_JOBS]; };      // phase: 0 nothing yet; k > 0: job k - 1 is published; -1: the master is done
 static_assert(sizeof(lr_lo_ctl) <= LR_LO_CTL_BYTES, "lr_lo_ctl does not fit its scratch block");
 
@@ -1215,7 +1195,7 @@ __device__ void lo_job_work(lo_shared &sh, lr_lo_job *jb, const float *__restric
     const int tid = threadIdx.x;
     const int nrec = (m + 1) >> 1;
     const int nchunks = (nrec + LO_CHUNK_REC - 1) / LO_CHUNK_REC;
-    if (tid < LO_TRIALS) { sh.cnt[tid] = 0u; sh.ssq[tid] = 0ull; }
+    if (tid < LR_LO_TRIALS) { sh.cnt[tid] = 0u; sh.ssq[tid] = 0ull; }
     __syncthreads();
     int mine = 0;
     for (;;) {
@@ -1228,7 +1208,7 @@ __device__ void lo_job_work(lo_shared &sh, lr_lo_job *jb, const float *__restric
         mine += 1;
     }
     if (mine > 0) {
-        if (tid < LO_TRIALS && sh.cnt[tid]) {
+        if (tid < LR_LO_TRIALS && sh.cnt[tid]) {
             __hip_atomic_fetch_add(&jb->cnt[tid], sh.cnt[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_fetch_add(&jb->ssq[tid], sh.ssq[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -1242,14 +1222,14 @@ __device__ void lo_job_work(lo_shared &sh, lr_lo_job *jb, const float *__restric
     __syncthreads();
 }
 
-// master: score sh.Rt[0 .. LO_TRIALS) over all correspondences with whoever helps -> sh.cnt / sh.ssq
+// master: score sh.Rt[0 .. LR_LO_TRIALS) over all correspondences with whoever helps -> sh.cnt / sh.ssq
 __device__ void lo_score_shared(lo_shared &sh, lr_lo_ctl *ctl, int job, const float *__restrict__ corr8, int m, float thr2, int32_t *timeouts)
 {
     const int tid = threadIdx.x;
     lr_lo_job *jb = &ctl->job[job];
     const int nrec = (m + 1) >> 1;
     const int nchunks = (nrec + LO_CHUNK_REC - 1) / LO_CHUNK_REC;
-    for (int k = tid; k < LO_TRIALS * 12; k += LO_THREADS) jb->Rt[k / 12][k % 12] = sh.Rt[k / 12][k % 12];
+    for (int k = tid; k < LR_LO_TRIALS * 12; k += LO_THREADS) jb->Rt[k / 12][k % 12] = sh.Rt[k / 12][k % 12];
     if (tid == 0) jb->nchunks = nchunks;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -1278,7 +1258,7 @@ __device__ void lo_score_shared(lo_shared &sh, lr_lo_ctl *ctl, int job, const fl
         lo_score_lanes(sh, corr8, m, thr2);
         return;
     }
-    if (tid < LO_TRIALS) {
+    if (tid < LR_LO_TRIALS) {
         sh.cnt[tid] = __hip_atomic_load(&jb->cnt[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         sh.ssq[tid] = __hip_atomic_load(&jb->ssq[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -1308,7 +1288,7 @@ __device__ void lo_helper_loop(lo_shared &sh, lr_lo_ctl *ctl, const float *__res
         if (p <= 0) return;                       // -1: done (0 cannot be observed as a change)
         seen = p;
         lr_lo_job *jb = &ctl->job[p - 1];
-        for (int k = tid; k < LO_TRIALS * 12; k += LO_THREADS) sh.Rt[k / 12][k % 12] = jb->Rt[k / 12][k % 12];
+        for (int k = tid; k < LR_LO_TRIALS * 12; k += LO_THREADS) sh.Rt[k / 12][k % 12] = jb->Rt[k / 12][k % 12];
         __syncthreads();
         lo_job_work(sh, jb, corr8, m, thr2);      // (always the full list: the near-inlier copy only exists in launches without helper blocks)
     }
@@ -1318,7 +1298,7 @@ __device__ void lo_helper_loop(lo_shared &sh, lr_lo_ctl *ctl, const float *__res
 __device__ void lo_score_wide(lo_shared &sh, const float *__restrict__ corr8, int m, float thr2, int ntrial)
 {
     const int tid = threadIdx.x;
-    if (tid < LO_TRIALS) { sh.cnt[tid] = 0u; sh.ssq[tid] = 0ull; }
+    if (tid < LR_LO_TRIALS) { sh.cnt[tid] = 0u; sh.ssq[tid] = 0ull; }
     __syncthreads();
     const int per = LO_THREADS / ntrial;           // threads per model
     const int t = tid / per, l = tid % per;
@@ -1426,32 +1406,32 @@ ransac_lo_kernel(const float *__restrict__ corr8, int m_max, const int32_t *__re
             LO_TICK(0);
             const int nI = sh.nI;
             if (nI <= p.sample_size) break;
-            const int ntrial = nI > LO_SAMPLE ? p.lo_trials : 1;
-            if (nI > LO_SAMPLE) {
-                // LO_SAMPLE distinct positions per trial (word stream keyed by seed, call, round, trial; a word that repeats a position is
+            const int ntrial = nI > LR_LO_SAMPLE ? p.lo_trials : 1;
+            if (nI > LR_LO_SAMPLE) {
+                // LR_LO_SAMPLE distinct positions per trial (word stream keyed by seed, call, round, trial; a word that repeats a position is
                 // skipped): 32 lanes per trial, lane j keeps the j-th accepted position, so "already drawn?" is one ballot over the
                 // trial's half of the wave instead of a loop over LDS.  Lane j then fetches its correspondence (two dependent loads,
-                // all LO_TRIALS * LO_SAMPLE of them in flight at once).
+                // all LR_LO_TRIALS * LR_LO_SAMPLE of them in flight at once).
                 {
                     const int t = tid >> 5, j = tid & 31, half = (tid >> 5) & 1;
                     if (t < ntrial) {
                         int mine = -1, got = 0;
                         const uint64_t key = p.seed ^ 0x4c4f43414c4f5054ull;
-                        for (int blk = 0; blk < 32 && got < LO_SAMPLE; ++blk) {
+                        for (int blk = 0; blk < 32 && got < LR_LO_SAMPLE; ++blk) {
                             const uint64_t ctr = ((uint64_t)call << 40) | ((uint64_t)round << 32) | ((uint64_t)t << 8) | (uint64_t)blk;
                             uint32_t w[4] = { (uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u };
                             philox4x32_10(w, (uint32_t)key, (uint32_t)(key >> 32));
-                            for (int k = 0; k < 4 && got < LO_SAMPLE; ++k) {
+                            for (int k = 0; k < 4 && got < LR_LO_SAMPLE; ++k) {
                                 const int c = (int)__umulhi(w[k], (uint32_t)nI);
                                 const bool dup = (uint32_t)(__ballot(mine == c) >> (32 * half)) != 0u;
                                 if (!dup) { if (j == got) mine = c; ++got; }
                             }
                         }
-                        for (int c = 0; got < LO_SAMPLE; ++c) {
+                        for (int c = 0; got < LR_LO_SAMPLE; ++c) {
                             const bool dup = (uint32_t)(__ballot(mine == c) >> (32 * half)) != 0u;
                             if (!dup) { if (j == got) mine = c; ++got; }
                         }
-                        if (j < LO_SAMPLE) {
+                        if (j < LR_LO_SAMPLE) {
                             const int i = list[mine];
 #pragma unroll
                             for (int a = 0; a < 6; ++a) sh.pts[t][j][a] = cc[lr_corr_at(i, a)];
@@ -1463,14 +1443,14 @@ ransac_lo_kernel(const float *__restrict__ corr8, int m_max, const int32_t *__re
                 if (tid < ntrial) {
                     double cp[3] = { 0, 0, 0 }, cq[3] = { 0, 0, 0 }, W = 0.0;
 #pragma unroll 1
-                    for (int k = 0; k < LO_SAMPLE; ++k) {      // (rolled: unrolled, the 126 values of both loops are kept live and spill)
+                    for (int k = 0; k < LR_LO_SAMPLE; ++k) {      // (rolled: unrolled, the 126 values of both loops are kept live and spill)
                         W = W + 1.0;
                         for (int a = 0; a < 3; ++a) { cp[a] = cp[a] + 1.0 * (double)sh.pts[tid][k][a]; cq[a] = cq[a] + 1.0 * (double)sh.pts[tid][k][3 + a]; }
                     }
                     for (int a = 0; a < 3; ++a) { cp[a] = cp[a] / W; cq[a] = cq[a] / W; }
                     double H[3][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } };
 #pragma unroll 1
-                    for (int k = 0; k < LO_SAMPLE; ++k) {
+                    for (int k = 0; k < LR_LO_SAMPLE; ++k) {
                         double pc[3], qc[3];
                         for (int a = 0; a < 3; ++a) { pc[a] = (double)sh.pts[tid][k][a] - cp[a]; qc[a] = (double)sh.pts[tid][k][3 + a] - cq[a]; }
                         for (int a = 0; a < 3; ++a)
@@ -1531,7 +1511,7 @@ ransac_lo_kernel(const float *__restrict__ corr8, int m_max, const int32_t *__re
             have_near = have_near && sh.eps[sh.flag] <= (double)(LO_NEAR_CAP * thr);
         }
     } else {
-        for (int it = 0; it < LO_POLISH; ++it) {
+        for (int it = 0; it < LR_LO_POLISH; ++it) {
             LO_COUNT(11);
             lo_build_list<false>(sh, corr8, m, p.thr2, list);
             LO_TICK(4);
@@ -1619,11 +1599,11 @@ int lr_ransac_run(lr_workspace *ws, const float *corr8, int m_max, const int32_t
     LR_REQUIRE(p_in->scoring >= 0 && p_in->scoring <= 2, LR_EINVAL, "lr_ransac: scoring must be 0 (count, then error), 1 (MSAC) or 2 (MSAC at GC-RANSAC's truncated threshold)");
     LR_REQUIRE(p_in->lo_rounds >= 0 && p_in->lo_trials >= 0 && p_in->lo_trials <= 20 && p_in->lo_max_calls >= 0 && p_in->min_iters >= 0, LR_EINVAL,
                "lr_ransac: lo_rounds, lo_trials (<= 20), lo_max_calls and min_iters must be >= 0 (0 = default)");
-    // the parameters as the kernels use them: defaults resolved, the truncated threshold applied (same text as oracle.c eff_params)
+    // the parameters as the kernels use them: defaults resolved, the truncated threshold applied (same rule as oracle.c eff_params)
     lr_ransac_params pe = *p_in;
     if (pe.scoring == 2) { pe.thr2 = pe.thr2 * 2.25f; pe.scoring = 1; }
-    if (pe.lo_rounds <= 0) pe.lo_rounds = 10;
-    if (pe.lo_trials <= 0) pe.lo_trials = 20;
+    if (pe.lo_rounds <= 0) pe.lo_rounds = LR_LO_ROUNDS;
+    if (pe.lo_trials <= 0) pe.lo_trials = LR_LO_TRIALS;
     if (pe.lo_max_calls <= 0) pe.lo_max_calls = pe.use_elc ? 20 : 50;
     if (pe.min_iters <= 0) pe.min_iters = pe.use_elc ? 20 : 50;
     const lr_ransac_params *p = &pe;
@@ -1756,11 +1736,7 @@ __device__ void refit_solve_body(const double *__restrict__ partial, int nblocks
         for (int k = 0; k < 16; ++k) T[k] = T_in[k];
         n_used = have_model ? (int)n : 0;
     } else {
-        double cp[3], cq[3], H[3][3];
-        for (int a = 0; a < 3; ++a) { cp[a] = mom[1 + a] / n; cq[a] = mom[4 + a] / n; }
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) H[a][b] = mom[7 + 3 * a + b] - (n * cp[a]) * cq[b];
-        lr_rt_from_cov(H, cp, cq, T);
+        lr_rt_from_moments(mom, T);
         n_used = (int)n;
     }
     for (int k = 0; k < 16; ++k) T_out[k] = T[k];

@@ -511,7 +511,7 @@ __global__ void __launch_bounds__(64) tz_search_kernel(tz_args g, long long node
 // R = argmin sum w |B - R A|^2 from H = sum w A B^T = U S V^T: R = V diag(1, 1, det(V U^T)) U^T.  One-sided Jacobi on H (columns of
 // H V orthogonalised), singular values sorted descending.  Rank-deficient H (collinear or coincident points) has no unique optimum; any
 // proper rotation attaining it is returned: s2 <= 1e-14 s1 (zero or rounding noise) completes u2 by an axis orthogonal to u1, s3 <= 1e-14
-// s1 completes u3 = u1 x u2, and H = 0 gives R = I.  Its own routine: lr_kabsch.h (which RANSAC's results depend on) is not touched.
+// s1 completes u3 = u1 x u2, and H = 0 gives R = I.  Its own routine: lr_contract.h (which RANSAC's results depend on) is not touched.
 __device__ void tz_svd_rot(const double H[9], double R[9])
 {
     double M[9], V[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };

@@ -46,10 +46,10 @@ class RansacResult(ctypes.Structure):
 
 
 def build(force=False):
-    """Compile oracle.c -> liboracle.so (gcc)."""
+    """Compile oracle.c + the shared csrc/lr_contract.h -> liboracle.so (gcc)."""
     so = os.path.join(_HERE, "liboracle.so")
-    src = os.path.join(_HERE, "oracle.c")
-    if force or not os.path.exists(so) or os.path.getmtime(so) < os.path.getmtime(src):
+    srcs = [os.path.join(_HERE, "oracle.c"), os.path.join(_HERE, "..", "lidarregistration_amd", "csrc", "lr_contract.h")]
+    if force or not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-s", "liboracle.so"])
     return so
 

@@ -1,4 +1,4 @@
-"""High-precision reference for the fp64 rigid fits (lr_kabsch.h's Horn solver, lr_teaser.hip's SVD rotation) and the degenerate
+"""High-precision reference for the fp64 rigid fits (lr_contract.h's Horn solver, lr_teaser.hip's SVD rotation) and the degenerate
 inputs they must survive.
 
 The input is exact fp64 data -- float32 clouds up-cast, which is what the kernels see -- and the reference works in mpmath at DPS

@@ -102,8 +102,8 @@ def test_g7_kabsch(oracle, k):
 
 
 def test_kabsch_closed_form_eigenvector_against_numpy_svd(oracle):
-    """Round 6: Horn's largest eigenvector comes from Newton's iteration on the characteristic polynomial + an adjugate column (oracle.c
-    horn4_maxvec_newton, the same text as csrc/lr_kabsch.h) instead of 36-48 dependent Jacobi rotations.  Against the SVD solution of
+    """Round 6: Horn's largest eigenvector comes from Newton's iteration on the characteristic polynomial + an adjugate column
+    (lr_horn4_maxvec_newton in csrc/lr_contract.h, which oracle.c compiles too) instead of 36-48 dependent Jacobi rotations.  Against the SVD solution of
     models/common.py:7-45 / DGR/util/procrustes.py:34-56 in float64 (numpy): 1e-12 on well-conditioned sets of every size the path uses
     (3- and 4-point samples, the local optimisation's 21, thousands for the refit), reflections resolved the same way, and sane answers
     (a proper rotation, the least-squares residual of the SVD solution) where the points are collinear or coincide -- the Jacobi fallback."""

@@ -263,7 +263,7 @@ def test_sprt_preverification_properties(oracle):
 
 
 def test_deterministic_logarithm(oracle):
-    """det_log (+ - * / only; the same text runs on the device as lr_det_log) is the natural logarithm to within 2 ulp, exact at
+    """lr_det_log (+ - * / only; csrc/lr_contract.h, the text the device compiles too) is the natural logarithm to within 2 ulp, exact at
     1, and keeps libm's conventions at 0, below 0, inf and NaN -- the confidence exit and the SPRT design compare against it."""
     import ctypes, math
     f = oracle.lib().orc_det_log; f.restype = ctypes.c_double; f.argtypes = [ctypes.c_double]

@@ -1,4 +1,4 @@
-"""The oracle's fp64 Kabsch (the same text as csrc/lr_kabsch.h) against a 40-digit SVD Kabsch (tests/rigid_hp.py) over thin, flat,
+"""The oracle's fp64 Kabsch (csrc/lr_contract.h, the text the kernels compile too) against a 40-digit SVD Kabsch (tests/rigid_hp.py) over thin, flat,
 coincident, mirrored and far-offset geometry: the bit-identity of oracle and device cannot catch a flaw they share."""
 import ctypes
 
