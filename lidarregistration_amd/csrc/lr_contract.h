@@ -1,8 +1,9 @@
 /*
- * lr_contract.h -- the fp64 arithmetic contract, one text for the HIP kernels and the CPU oracle.
+ * lr_contract.h -- the arithmetic contract, one text for the HIP kernels and the CPU oracle: the fp64 solvers and decisions, and
+ * the fp32 scoring of a model (residual, fixed-point error term, MSAC threshold, winner ordering).
  *
  * Plain C99 that is also valid HIP C++: the .hip files next to it compile it with hipcc for gfx950, oracle/oracle.c with gcc.
- * Everything here is written with + - * / sqrt only and an explicit operation order, and both sides build with
+ * Everything here is written with + - * / sqrt and explicit fmaf only, in an explicit operation order, and both sides build with
  * -ffp-contract=off, so the device and the oracle produce the same bits.  The GPU-against-oracle tests check for these routines that two compilers and two
  * machines turn this one text into the same bits; the mathematics is verified independently (tests/rigid_hp.py: 40-digit SVD
  * Kabsch; the numpy-SVD test of tests/test_oracle_golden.py; goldens G7 / G11).
@@ -18,6 +19,11 @@
  *     avoid spills; a shared template would be new machinery in a kernel at its register limits.
  *   - eff_params: the structs differ (orc_ransac_params has no struct_size) and the device entry refuses lo_trials > 20 where the
  *     oracle clamps it.  Same rule, two texts.
+ *   - the fp64 residual of refit_moments_kernel / ICP (no fma, fp64 threshold): a different contract from the fp32 scoring below.
+ *   - the pruning radii eps of ransac_order_kernel (fp32) and of the LO near list (fp64): bounds on where inliers can lie, not
+ *     results; the oracle scores everything and has neither.
+ *   - the packed two-correspondence form of the scoring residual (lr_ransac.hip, lr_d2x2): ext_vector arithmetic has no C99
+ *     spelling; it applies lr_score_d2's fma order to each half.
  */
 #ifndef LR_CONTRACT_H
 #define LR_CONTRACT_H
@@ -31,6 +37,7 @@
 #  define LRC_UNROLL
 #endif
 #include <math.h>
+#include <stdint.h>
 #include <string.h>
 
 /* ------------------------------------------------------------------ logarithm for the decisions (fp64, + - * / only) */
@@ -255,6 +262,38 @@ LRC_FN void lr_rt_from_moments(const double mom[16], double T[16])
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) H[a][b] = mom[7 + 3 * a + b] - (n * cp[a]) * cq[b];
     lr_rt_from_cov(H, cp, cq, T);
+}
+
+/* ------------------------------------------------------------------ fp32 scoring (fmaf in this order, nothing else) */
+/* Counts and error sums are integers -- sums over the inliers of (uint32)(d2 * 2^20) -- so they do not depend on the order of
+ * summation; they are the same on both sides because every site evaluates d2 through this chain. */
+#define LR_SCORE_SCALE 1048576.0f      /* 2^20: fixed point of the squared residual */
+
+/* squared residual of the correspondence (p, q) under the model Rt = R | t, row-major 3x4 */
+LRC_FN float lr_score_d2(const float Rt[12], float px, float py, float pz, float qx, float qy, float qz)
+{
+    const float x = fmaf(Rt[0], px, fmaf(Rt[1], py, fmaf(Rt[2], pz, Rt[3])));
+    const float y = fmaf(Rt[4], px, fmaf(Rt[5], py, fmaf(Rt[6], pz, Rt[7])));
+    const float z = fmaf(Rt[8], px, fmaf(Rt[9], py, fmaf(Rt[10], pz, Rt[11])));
+    const float dx = x - qx, dy = y - qy, dz = z - qz;
+    return fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+}
+
+/* what an inlier (d2 < thr2) adds to the error sum */
+LRC_FN uint32_t lr_score_term(float d2) { return (uint32_t)(d2 * LR_SCORE_SCALE); }
+
+/* MSAC's threshold in the fixed point of the error sum; 0 selects the ordering by count (scoring: 0 count then error, 1 MSAC) */
+LRC_FN uint32_t lr_msac_T(int scoring, float thr2) { return scoring == 1 ? lr_score_term(thr2) : 0u; }
+
+/* is the model (inlier count c, error sum q, id h) better than (bc, bq, bh)?  More inliers, then lower error, then lower id. */
+LRC_FN int lr_score_better(uint32_t c, uint64_t q, long long h, uint32_t bc, uint64_t bq, long long bh, uint32_t msac_T)
+{
+    if (msac_T == 0u) return c > bc || (c == bc && (q < bq || (q == bq && h < bh)));
+    /* MSAC: larger sum over inliers of (thr2 - d2) in the fixed point of the error sum; a model without inliers never wins */
+    if (c == 0u) return 0;
+    if (bc == 0u) return 1;
+    const long long k = (long long)c * (long long)msac_T - (long long)q, bk = (long long)bc * (long long)msac_T - (long long)bq;
+    return k > bk || (k == bk && h < bh);
 }
 
 #endif /* LR_CONTRACT_H */

@@ -17,7 +17,8 @@
 //           the inlier noise is far below the threshold, so the error is accumulated for everyone)
 //   refit   fp64 moments of the inliers over the ORIGINAL NN pairs -> Kabsch
 //
-// Arithmetic is spelled out op by op and must stay identical to oracle/oracle.c (build: -ffp-contract=off).
+// Arithmetic is spelled out op by op and is the oracle's (build: -ffp-contract=off): what both sides compute is one text,
+// lr_contract.h; the packed form of its fp32 scoring is below.
 #include "lr_internal.h"
 #include <math.h>
 #define LR_INF_F __builtin_huge_valf()
@@ -39,6 +40,62 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// ------------------------------------------------------------------ the scoring arithmetic on the device (lr_contract.h, "fp32 scoring")
+// A model as lr_score_d2 takes it: R | t, row-major.  The model lists hold coefficient k of slot s at [k * stride + s].
+struct lr_model12 { float Rt[12]; };
+__device__ __forceinline__ lr_model12 lr_load_model(const float *__restrict__ mp, size_t ms)
+{
+    lr_model12 M;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) M.Rt[k] = mp[k * ms];
+    return M;
+}
+__device__ __forceinline__ void lr_store_model(float *__restrict__ mp, size_t ms, const lr_model12 &M)
+{
+#pragma unroll
+    for (int k = 0; k < 12; ++k) mp[k * ms] = M.Rt[k];
+}
+// correspondence i of a packed list (lr_corr_at) under the model
+__device__ __forceinline__ float lr_corr_d2(const float Rt[12], const float *__restrict__ corr8, int i)
+{
+    return lr_score_d2(Rt, corr8[lr_corr_at(i, 0)], corr8[lr_corr_at(i, 1)], corr8[lr_corr_at(i, 2)], corr8[lr_corr_at(i, 3)],
+                       corr8[lr_corr_at(i, 4)], corr8[lr_corr_at(i, 5)]);
+}
+
+// The packed form: the two correspondences of a 64-byte record per packed fp32 instruction, every half in lr_score_d2's fma order.
+// Device-only (ext_vector arithmetic has no C99 spelling), and the one place where it is written.
+struct lr_model12x2 {        // every coefficient in both halves; from a float[12] (lr_model12::Rt, an LDS row) or a double[12] rounded to float
+    f32x2 c[12];
+    template <class T>
+    __device__ __forceinline__ explicit lr_model12x2(const T *Rt)
+    {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) { const float v = (float)Rt[k]; c[k] = f32x2{ v, v }; }
+    }
+};
+__device__ __forceinline__ f32x2 lr_d2x2(const lr_model12x2 &S, const f32x2 px, const f32x2 py, const f32x2 pz, const f32x2 qx, const f32x2 qy, const f32x2 qz)
+{
+    const f32x2 x = __builtin_elementwise_fma(S.c[0], px, __builtin_elementwise_fma(S.c[1], py, __builtin_elementwise_fma(S.c[2], pz, S.c[3])));
+    const f32x2 y = __builtin_elementwise_fma(S.c[4], px, __builtin_elementwise_fma(S.c[5], py, __builtin_elementwise_fma(S.c[6], pz, S.c[7])));
+    const f32x2 z = __builtin_elementwise_fma(S.c[8], px, __builtin_elementwise_fma(S.c[9], py, __builtin_elementwise_fma(S.c[10], pz, S.c[11])));
+    const f32x2 dx = x - qx, dy = y - qy, dz = z - qz;
+    return __builtin_elementwise_fma(dx, dx, __builtin_elementwise_fma(dy, dy, dz * dz));
+}
+__device__ __forceinline__ f32x2 lr_d2x2(const lr_model12x2 &S, const f32x2 *o) { return lr_d2x2(S, o[0], o[1], o[2], o[3], o[4], o[5]); }
+// the three 16-byte loads of a record -> its six operands px py pz qx qy qz (x: correspondence 2 r, y: 2 r + 1)
+__device__ __forceinline__ void lr_record_operands(const f32x4 A, const f32x4 B, const f32x4 C, f32x2 (&o)[6])
+{
+    o[0] = f32x2{ A.x, A.y }; o[1] = f32x2{ A.z, A.w }; o[2] = f32x2{ B.x, B.y }; o[3] = f32x2{ B.z, B.w }; o[4] = f32x2{ C.x, C.y }; o[5] = f32x2{ C.z, C.w };
+}
+// count and error terms of the two halves, each under its own predicate (Q: 32-bit where the caller bounds the sum, else 64-bit)
+template <class Q>
+__device__ __forceinline__ void lr_add_pair(const f32x2 d2, bool in0, bool in1, uint32_t &cnt, Q &q)
+{
+    const f32x2 fx = d2 * f32x2{ LR_SCORE_SCALE, LR_SCORE_SCALE };
+    cnt += (in0 ? 1u : 0u) + (in1 ? 1u : 0u);
+    q += (Q)(in0 ? (uint32_t)fx.x : 0u) + (Q)(in1 ? (uint32_t)fx.y : 0u);
+}
 
 // unweighted Kabsch on NS (3 or 4) sample points held in registers
 template <int NS>
@@ -327,23 +384,15 @@ ransac_sprt_kernel(const float *__restrict__ corr8, int m_max, const int32_t *__
     const double A = lr_sprt_threshold(eps, delta), fin = delta / eps, fout = (1.0 - delta) / (1.0 - eps);
     const int slot = group * 64 + lane;
     const bool active = slot < V;
-    const float *mp = models + (active ? slot : 0);
     const size_t ms = (size_t)model_stride;
-    const float r00 = mp[0], r01 = mp[ms], r02 = mp[2 * ms], tx = mp[3 * ms];
-    const float r10 = mp[4 * ms], r11 = mp[5 * ms], r12 = mp[6 * ms], ty = mp[7 * ms];
-    const float r20 = mp[8 * ms], r21 = mp[9 * ms], r22 = mp[10 * ms], tz = mp[11 * ms];
+    const lr_model12 M = lr_load_model(models + (active ? slot : 0), ms);
     const int n = min(m, LR_SPRT_HORIZON);
     double lambda = 1.0;
     int inl = 0, k_rej = 0;
     bool rejected = !active;
     for (int i = 0; i < n; ++i) {
         if (__builtin_amdgcn_ballot_w64(!rejected) == 0ull) break;
-        const float px = corr8[lr_corr_at(i, 0)], py = corr8[lr_corr_at(i, 1)], pz = corr8[lr_corr_at(i, 2)];
-        const float x = __builtin_fmaf(r00, px, __builtin_fmaf(r01, py, __builtin_fmaf(r02, pz, tx)));
-        const float y = __builtin_fmaf(r10, px, __builtin_fmaf(r11, py, __builtin_fmaf(r12, pz, ty)));
-        const float zz = __builtin_fmaf(r20, px, __builtin_fmaf(r21, py, __builtin_fmaf(r22, pz, tz)));
-        const float dx = x - corr8[lr_corr_at(i, 3)], dy = y - corr8[lr_corr_at(i, 4)], dz = zz - corr8[lr_corr_at(i, 5)];
-        const float d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
+        const float d2 = lr_corr_d2(M.Rt, corr8, i);
         if (!rejected) {
             if (d2 < thr2) { inl += 1; lambda = lambda * fin; } else lambda = lambda * fout;
             if (lambda > A) { rejected = true; k_rej = i + 1; }
@@ -357,9 +406,7 @@ ransac_sprt_kernel(const float *__restrict__ corr8, int m_max, const int32_t *__
     base = __shfl(base, 0);
     if (keep) {
         const int dst = base + (int)__builtin_popcountll(kb & ((1ull << lane) - 1ull));
-        models2[dst] = r00; models2[ms + dst] = r01; models2[2 * ms + dst] = r02; models2[3 * ms + dst] = tx;
-        models2[4 * ms + dst] = r10; models2[5 * ms + dst] = r11; models2[6 * ms + dst] = r12; models2[7 * ms + dst] = ty;
-        models2[8 * ms + dst] = r20; models2[9 * ms + dst] = r21; models2[10 * ms + dst] = r22; models2[11 * ms + dst] = tz;
+        lr_store_model(models2 + dst, ms, M);
 #pragma unroll
         for (int k = 0; k < 12; ++k) models64_2[(size_t)dst * 12 + k] = models64[(size_t)slot * 12 + k];
         model_h2[dst] = model_h[slot];
@@ -398,24 +445,6 @@ ransac_sprt_kernel(const float *__restrict__ corr8, int m_max, const int32_t *__
 __device__ __forceinline__ int lr_sc_head(int m, int V) { return (m >= LR_SC_MIN_M && V >= LR_SC_MIN_V) ? LR_SC_HEAD : 0; }
 
 // one lane's model over the records [begin, end) of a stream (begin even; a trailing odd correspondence is taken alone)
-struct lr_model12 { float r00, r01, r02, tx, r10, r11, r12, ty, r20, r21, r22, tz; };
-__device__ __forceinline__ lr_model12 lr_load_model(const float *__restrict__ mp, size_t ms)
-{
-    lr_model12 M;
-    M.r00 = mp[0]; M.r01 = mp[ms]; M.r02 = mp[2 * ms]; M.tx = mp[3 * ms];
-    M.r10 = mp[4 * ms]; M.r11 = mp[5 * ms]; M.r12 = mp[6 * ms]; M.ty = mp[7 * ms];
-    M.r20 = mp[8 * ms]; M.r21 = mp[9 * ms]; M.r22 = mp[10 * ms]; M.tz = mp[11 * ms];
-    return M;
-}
-__device__ __forceinline__ float lr_model_d2(const lr_model12 &M, const float *__restrict__ corr8, int i)
-{
-    const float px = corr8[lr_corr_at(i, 0)], py = corr8[lr_corr_at(i, 1)], pz = corr8[lr_corr_at(i, 2)];
-    const float x = __builtin_fmaf(M.r00, px, __builtin_fmaf(M.r01, py, __builtin_fmaf(M.r02, pz, M.tx)));
-    const float y = __builtin_fmaf(M.r10, px, __builtin_fmaf(M.r11, py, __builtin_fmaf(M.r12, pz, M.ty)));
-    const float z = __builtin_fmaf(M.r20, px, __builtin_fmaf(M.r21, py, __builtin_fmaf(M.r22, pz, M.tz)));
-    const float dx = x - corr8[lr_corr_at(i, 3)], dy = y - corr8[lr_corr_at(i, 4)], dz = z - corr8[lr_corr_at(i, 5)];
-    return __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
-}
 __device__ __forceinline__ void lr_score_stream(const float *__restrict__ corr8, int begin, int end, int sub, float thr2,
                                                 const lr_model12 &M, uint32_t &cnt, unsigned long long &ssq)
 {
@@ -425,18 +454,13 @@ __device__ __forceinline__ void lr_score_stream(const float *__restrict__ corr8,
     // Scalar loads return out of order, so every wait for one drains all of them: the stream is read TWO records (four
     // correspondences) per wait, the loads of the next two issued before the arithmetic of these two -- one wait per ~50 vector
     // instructions with a full iteration of lookahead (a record per wait had the next record's loads and their wait ~25 instructions apart).
-    const f32x2 R00 = { M.r00, M.r00 }, R01 = { M.r01, M.r01 }, R02 = { M.r02, M.r02 }, TX = { M.tx, M.tx };
-    const f32x2 R10 = { M.r10, M.r10 }, R11 = { M.r11, M.r11 }, R12 = { M.r12, M.r12 }, TY = { M.ty, M.ty };
-    const f32x2 R20 = { M.r20, M.r20 }, R21 = { M.r21, M.r21 }, R22 = { M.r22, M.r22 }, TZ = { M.tz, M.tz };
-    const f32x2 SC = { 1048576.0f, 1048576.0f };
+    const lr_model12x2 S(M.Rt);
     uint32_t q32 = 0;
     auto pair_of = [&](const f32x2 px, const f32x2 py, const f32x2 pz, const f32x2 qx, const f32x2 qy, const f32x2 qz) {
-        const f32x2 x = __builtin_elementwise_fma(R00, px, __builtin_elementwise_fma(R01, py, __builtin_elementwise_fma(R02, pz, TX)));
-        const f32x2 y = __builtin_elementwise_fma(R10, px, __builtin_elementwise_fma(R11, py, __builtin_elementwise_fma(R12, pz, TY)));
-        const f32x2 z = __builtin_elementwise_fma(R20, px, __builtin_elementwise_fma(R21, py, __builtin_elementwise_fma(R22, pz, TZ)));
-        const f32x2 dx = x - qx, dy = y - qy, dz = z - qz;
-        const f32x2 d2 = __builtin_elementwise_fma(dx, dx, __builtin_elementwise_fma(dy, dy, dz * dz));
-        const f32x2 fx = d2 * SC;
+        const f32x2 d2 = lr_d2x2(S, px, py, pz, qx, qy, qz);
+        // (lr_add_pair's statements, kept in place: through the helper the four integer terms of a record are summed in another order
+        // and this kernel's assembly changes -- profiles/score_contract_isa.txt)
+        const f32x2 fx = d2 * f32x2{ LR_SCORE_SCALE, LR_SCORE_SCALE };
         const bool in0 = d2.x < thr2, in1 = d2.y < thr2;
         cnt += (in0 ? 1u : 0u) + (in1 ? 1u : 0u);
         q32 += (in0 ? (uint32_t)fx.x : 0u) + (in1 ? (uint32_t)fx.y : 0u);
@@ -479,8 +503,8 @@ __device__ __forceinline__ void lr_score_stream(const float *__restrict__ corr8,
         ssq += q32;
     }
     if (pend < end && begin < end) {      // (a chunk past the end -- begin > end -- owns nothing, not even the odd last correspondence)
-        const float d2 = lr_model_d2(M, corr8, pend);
-        if (d2 < thr2) { cnt += 1u; ssq += (uint32_t)(d2 * 1048576.0f); }
+        const float d2 = lr_corr_d2(M.Rt, corr8, pend);
+        if (d2 < thr2) { cnt += 1u; ssq += lr_score_term(d2); }
     }
 }
 
@@ -590,7 +614,7 @@ ransac_resid_kernel(const float *__restrict__ corr8, int m_max, const int32_t *_
         if (bad) s_bad = 1;
         if (c >= K0) {
             constexpr float INVW = 1.0f / LR_SC_W, RMAX = LR_SC_NB * LR_SC_W;
-            const float r = sqrtf(lr_model_d2(P, corr8, c));
+            const float r = sqrtf(lr_corr_d2(P.Rt, corr8, c));
             int b = LR_SC_NB - 1;
             if (r < RMAX) b = min((int)(r * INVW), LR_SC_NB - 1);      // (NaN, inf: last bucket)
             cb[c] = (uint8_t)b;
@@ -658,16 +682,18 @@ ransac_order_kernel(int m_max, const int32_t *__restrict__ m_dev, float thr2, co
     const float amax = fmaxf(fmaxf(fmaxf(fabsf(b0), fabsf(b3)), fmaxf(fabsf(b1), fabsf(b4))), fmaxf(fabsf(b2), fabsf(b5)));
     constexpr float INVW = 1.0f / LR_SC_W, RMAX = LR_SC_NB * LR_SC_W;
     const float thr = sqrtf(thr2);
-    const float pt1 = fabsf(P.tx) + fabsf(P.ty) + fabsf(P.tz);
+    const float *Pm = P.Rt;
+    const float pt1 = fabsf(Pm[3]) + fabsf(Pm[7]) + fabsf(Pm[11]);
     for (int v = tid; v < V; v += 1024) {
         const lr_model12 M = lr_load_model(models + v, ms);
-        const float d00 = M.r00 - P.r00, d01 = M.r01 - P.r01, d02 = M.r02 - P.r02, d10 = M.r10 - P.r10, d11 = M.r11 - P.r11, d12 = M.r12 - P.r12,
-                    d20 = M.r20 - P.r20, d21 = M.r21 - P.r21, d22 = M.r22 - P.r22;
+        const float *Mm = M.Rt;
+        const float d00 = Mm[0] - Pm[0], d01 = Mm[1] - Pm[1], d02 = Mm[2] - Pm[2], d10 = Mm[4] - Pm[4], d11 = Mm[5] - Pm[5], d12 = Mm[6] - Pm[6],
+                    d20 = Mm[8] - Pm[8], d21 = Mm[9] - Pm[9], d22 = Mm[10] - Pm[10];
         const float F = sqrtf(d00 * d00 + d01 * d01 + d02 * d02 + d10 * d10 + d11 * d11 + d12 * d12 + d20 * d20 + d21 * d21 + d22 * d22);
-        const float ux = d00 * cx + d01 * cy + d02 * cz + (M.tx - P.tx), uy = d10 * cx + d11 * cy + d12 * cz + (M.ty - P.ty),
-                    uz = d20 * cx + d21 * cy + d22 * cz + (M.tz - P.tz);
+        const float ux = d00 * cx + d01 * cy + d02 * cz + (Mm[3] - Pm[3]), uy = d10 * cx + d11 * cy + d12 * cz + (Mm[7] - Pm[7]),
+                    uz = d20 * cx + d21 * cy + d22 * cz + (Mm[11] - Pm[11]);
         const float eps = (F * rho + sqrtf(ux * ux + uy * uy + uz * uz)) * 1.001f;
-        const float slack = 0.01f + 4e-6f * (3.0f * amax + pt1 + fabsf(M.tx) + fabsf(M.ty) + fabsf(M.tz));
+        const float slack = 0.01f + 4e-6f * (3.0f * amax + pt1 + fabsf(Mm[3]) + fabsf(Mm[7]) + fabsf(Mm[11]));
         const float cut = thr + eps + slack;
         int bv = LR_SC_NB - 1;
         if (cut < RMAX) bv = min((int)(cut * INVW), LR_SC_NB - 1);      // (NaN, inf: everything)
@@ -748,17 +774,7 @@ ransac_scatter_kernel(const float *__restrict__ corr8, float *__restrict__ corr8
 }
 
 // ------------------------------------------------------------------ select
-// best = more inliers, then lower fixed-point error, then lower hypothesis id; its fp64 model was kept by gen
-__device__ __forceinline__ bool better(uint32_t c, unsigned long long q, int h, uint32_t bc, unsigned long long bq, int bh,
-                                       uint32_t msac_T)
-{
-    if (msac_T == 0u) return c > bc || (c == bc && (q < bq || (q == bq && h < bh)));
-    // MSAC: larger sum over inliers of (thr2 - d^2) in the fixed point of the error sum; a model without inliers never wins
-    if (c == 0u) return false;
-    if (bc == 0u) return true;
-    const long long k = (long long)c * (long long)msac_T - (long long)q, bk = (long long)bc * (long long)msac_T - (long long)bq;
-    return k > bk || (k == bk && h < bh);
-}
+// best = more inliers, then lower fixed-point error, then lower hypothesis id (lr_score_better); its fp64 model was kept by gen
 
 // re-design of the SPRT for the next batch: eps follows the best model (its inlier count `nc` of `mm` correspondences), delta the
 // models rejected so far
@@ -793,7 +809,7 @@ ransac_final_kernel(const uint32_t *__restrict__ score_cnt, const unsigned long 
     __shared__ int s_h[16], s_s[16];
     lr_ransac_state *state = reinterpret_cast<lr_ransac_state *>(counters + LR_CNT_COUNT);
     if (state->done) return;
-    const uint32_t msac_T = p.scoring == 1 ? (uint32_t)(p.thr2 * 1048576.0f) : 0u;
+    const uint32_t msac_T = lr_msac_T(p.scoring, p.thr2);
     const int V = counters[vslot];
     uint32_t bc = 0; unsigned long long bq = ~0ull; int bh = 0x7fffffff, bs = -1;
     for (int s = threadIdx.x; s < V; s += 1024) {
@@ -801,24 +817,24 @@ ransac_final_kernel(const uint32_t *__restrict__ score_cnt, const unsigned long 
         if (c == 0) continue;
         unsigned long long q = score_ssq[s];
         int h = model_h[s];
-        if (better(c, q, h, bc, bq, bh, msac_T)) { bc = c; bq = q; bh = h; bs = s; }
+        if (lr_score_better(c, q, h, bc, bq, bh, msac_T)) { bc = c; bq = q; bh = h; bs = s; }
     }
 #pragma unroll
     for (int mk = 32; mk >= 1; mk >>= 1) {
         uint32_t oc = (uint32_t)__shfl_xor((int)bc, mk);
         unsigned long long oq = __shfl_xor(bq, mk);
         int oh = __shfl_xor(bh, mk), os = __shfl_xor(bs, mk);
-        if (better(oc, oq, oh, bc, bq, bh, msac_T)) { bc = oc; bq = oq; bh = oh; bs = os; }
+        if (lr_score_better(oc, oq, oh, bc, bq, bh, msac_T)) { bc = oc; bq = oq; bh = oh; bs = os; }
     }
     if ((threadIdx.x & 63) == 0) { s_c[threadIdx.x >> 6] = bc; s_q[threadIdx.x >> 6] = bq; s_h[threadIdx.x >> 6] = bh; s_s[threadIdx.x >> 6] = bs; }
     __syncthreads();
     if (threadIdx.x >= 16) return;
     for (int w = 1; w < 16; ++w)
-        if (better(s_c[w], s_q[w], s_h[w], bc, bq, bh, msac_T)) { bc = s_c[w]; bq = s_q[w]; bh = s_h[w]; bs = s_s[w]; }
+        if (lr_score_better(s_c[w], s_q[w], s_h[w], bc, bq, bh, msac_T)) { bc = s_c[w]; bq = s_q[w]; bh = s_h[w]; bs = s_s[w]; }
     // all 16 lanes hold the batch winner; merge it into the state (lane k moves T[k])
     const int k = threadIdx.x;
     const uint32_t oc = state->cnt; const unsigned long long oq = state->ssq; const int oh = state->h;
-    const bool take = bc > 0 && bs >= 0 && (oc == 0 || better(bc, bq, bh, oc, oq, oh, msac_T));
+    const bool take = bc > 0 && bs >= 0 && (oc == 0 || lr_score_better(bc, bq, bh, oc, oq, oh, msac_T));
     double v = (k % 5 == 0) ? 1.0 : 0.0;
     if (k < 12) {
         if (take) { v = models64[(size_t)bs * 12 + k]; state->T[k] = v; }
@@ -888,15 +904,6 @@ struct lo_shared {
     double baseT[12];                // the model near8 was copied around
 };
 
-__device__ __forceinline__ float lo_d2(const float *Rt, float px, float py, float pz, float qx, float qy, float qz)
-{
-    const float x = __builtin_fmaf(Rt[0], px, __builtin_fmaf(Rt[1], py, __builtin_fmaf(Rt[2], pz, Rt[3])));
-    const float y = __builtin_fmaf(Rt[4], px, __builtin_fmaf(Rt[5], py, __builtin_fmaf(Rt[6], pz, Rt[7])));
-    const float z = __builtin_fmaf(Rt[8], px, __builtin_fmaf(Rt[9], py, __builtin_fmaf(Rt[10], pz, Rt[11])));
-    const float dx = x - qx, dy = y - qy, dz = z - qz;
-    return __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, dz * dz));
-}
-
 // inliers of sh.curT over the m correspondences, in index order -> list[0 .. sh.nI).
 // A thread tests the two correspondences of one 64-byte record per step (three 16-byte loads, the packed arithmetic of the
 // scoring kernel: same fma order per component).  A pass covers LO_MAXIT * LO_THREADS records: every thread runs its LO_MAXIT steps
@@ -923,12 +930,7 @@ __device__ void lo_build_list(lo_shared &sh, const float *__restrict__ corr8, in
     const bool want_box = OUT == 1 && sh.box_state == 0;
     float bmn[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, bmx[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
     bool bad = false;
-    const f32x2 R00 = { (float)sh.curT[0], (float)sh.curT[0] }, R01 = { (float)sh.curT[1], (float)sh.curT[1] }, R02 = { (float)sh.curT[2], (float)sh.curT[2] },
-                TX = { (float)sh.curT[3], (float)sh.curT[3] };
-    const f32x2 R10 = { (float)sh.curT[4], (float)sh.curT[4] }, R11 = { (float)sh.curT[5], (float)sh.curT[5] }, R12 = { (float)sh.curT[6], (float)sh.curT[6] },
-                TY = { (float)sh.curT[7], (float)sh.curT[7] };
-    const f32x2 R20 = { (float)sh.curT[8], (float)sh.curT[8] }, R21 = { (float)sh.curT[9], (float)sh.curT[9] }, R22 = { (float)sh.curT[10], (float)sh.curT[10] },
-                TZ = { (float)sh.curT[11], (float)sh.curT[11] };
+    const lr_model12x2 S(sh.curT);
     const int nrec = (m + 1) >> 1;
     const unsigned long long lt = (1ull << lane) - 1ull;
     int total = 0;
@@ -940,12 +942,9 @@ __device__ void lo_build_list(lo_shared &sh, const float *__restrict__ corr8, in
             const int r = sbase + it * LO_THREADS + tid;
             const f32x4 *rec = reinterpret_cast<const f32x4 *>(corr8) + (size_t)min(r, nrec - 1) * 4;
             const f32x4 A = rec[0], B = rec[1], C = rec[2];
-            const f32x2 px = { A.x, A.y }, py = { A.z, A.w }, pz = { B.x, B.y }, qx = { B.z, B.w }, qy = { C.x, C.y }, qz = { C.z, C.w };
-            const f32x2 x = __builtin_elementwise_fma(R00, px, __builtin_elementwise_fma(R01, py, __builtin_elementwise_fma(R02, pz, TX)));
-            const f32x2 y = __builtin_elementwise_fma(R10, px, __builtin_elementwise_fma(R11, py, __builtin_elementwise_fma(R12, pz, TY)));
-            const f32x2 z = __builtin_elementwise_fma(R20, px, __builtin_elementwise_fma(R21, py, __builtin_elementwise_fma(R22, pz, TZ)));
-            const f32x2 dx = x - qx, dy = y - qy, dz = z - qz;
-            const f32x2 d2 = __builtin_elementwise_fma(dx, dx, __builtin_elementwise_fma(dy, dy, dz * dz));
+            f32x2 o[6];
+            lr_record_operands(A, B, C, o);
+            const f32x2 d2 = lr_d2x2(S, o);
             const bool in0 = r < nrec && d2.x < thr2, in1 = r < nrec && 2 * r + 1 < m && d2.y < thr2;
             bits |= (unsigned long long)((in0 ? 1u : 0u) | (in1 ? 2u : 0u)) << (2 * it);
             if (want_box && r < nrec) {
@@ -1092,10 +1091,7 @@ __device__ void lo_score_one(lo_shared &sh, const float *__restrict__ corr8, int
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid < LR_LO_TRIALS) { sh.cnt[tid] = 0u; sh.ssq[tid] = 0ull; }
     __syncthreads();
-    const float *Rt = sh.Rt[0];
-    const f32x2 R00 = { Rt[0], Rt[0] }, R01 = { Rt[1], Rt[1] }, R02 = { Rt[2], Rt[2] }, TX = { Rt[3], Rt[3] };
-    const f32x2 R10 = { Rt[4], Rt[4] }, R11 = { Rt[5], Rt[5] }, R12 = { Rt[6], Rt[6] }, TY = { Rt[7], Rt[7] };
-    const f32x2 R20 = { Rt[8], Rt[8] }, R21 = { Rt[9], Rt[9] }, R22 = { Rt[10], Rt[10] }, TZ = { Rt[11], Rt[11] };
+    const lr_model12x2 S(sh.Rt[0]);
     const int nrec = (m + 1) >> 1;
     uint32_t c = 0u, q = 0u;
     // the record walk of lo_build_list (three 16-byte loads per 64-byte record, both correspondences in one packed chain; the scalar
@@ -1104,15 +1100,10 @@ __device__ void lo_score_one(lo_shared &sh, const float *__restrict__ corr8, int
     for (int r = tid; r < nrec; r += LO_THREADS) {
         const f32x4 *rec = reinterpret_cast<const f32x4 *>(corr8) + (size_t)r * 4;
         const f32x4 A = rec[0], B = rec[1], C = rec[2];
-        const f32x2 px = { A.x, A.y }, py = { A.z, A.w }, pz = { B.x, B.y }, qx = { B.z, B.w }, qy = { C.x, C.y }, qz = { C.z, C.w };
-        const f32x2 x = __builtin_elementwise_fma(R00, px, __builtin_elementwise_fma(R01, py, __builtin_elementwise_fma(R02, pz, TX)));
-        const f32x2 y = __builtin_elementwise_fma(R10, px, __builtin_elementwise_fma(R11, py, __builtin_elementwise_fma(R12, pz, TY)));
-        const f32x2 z = __builtin_elementwise_fma(R20, px, __builtin_elementwise_fma(R21, py, __builtin_elementwise_fma(R22, pz, TZ)));
-        const f32x2 dx = x - qx, dy = y - qy, dz = z - qz;
-        const f32x2 d2 = __builtin_elementwise_fma(dx, dx, __builtin_elementwise_fma(dy, dy, dz * dz));
-        const bool in0 = d2.x < thr2, in1 = 2 * r + 1 < m && d2.y < thr2;
-        c += (in0 ? 1u : 0u) + (in1 ? 1u : 0u);
-        q += (in0 ? (uint32_t)(d2.x * 1048576.0f) : 0u) + (in1 ? (uint32_t)(d2.y * 1048576.0f) : 0u);
+        f32x2 o[6];
+        lr_record_operands(A, B, C, o);
+        const f32x2 d2 = lr_d2x2(S, o);
+        lr_add_pair(d2, d2.x < thr2, 2 * r + 1 < m && d2.y < thr2, c, q);
     }
     unsigned long long qq = q;
 #pragma unroll
@@ -1133,12 +1124,7 @@ __device__ void lo_score_lanes_range(lo_shared &sh, const float *__restrict__ co
     constexpr int STRIDE = NS * (LO_THREADS / 64);     // records between two steps of a stream (48)
     const int t = lane % LR_LO_TRIALS, st = lane / LR_LO_TRIALS;
     const bool act = st < NS;
-    const f32x4 *rp = reinterpret_cast<const f32x4 *>(sh.Rt[t]);
-    const f32x4 r0 = rp[0], r1 = rp[1], r2 = rp[2];
-    const f32x2 R00 = { r0.x, r0.x }, R01 = { r0.y, r0.y }, R02 = { r0.z, r0.z }, TX = { r0.w, r0.w };
-    const f32x2 R10 = { r1.x, r1.x }, R11 = { r1.y, r1.y }, R12 = { r1.z, r1.z }, TY = { r1.w, r1.w };
-    const f32x2 R20 = { r2.x, r2.x }, R21 = { r2.y, r2.y }, R22 = { r2.z, r2.z }, TZ = { r2.w, r2.w };
-    const f32x2 SC = { 1048576.0f, 1048576.0f };
+    const lr_model12x2 S(sh.Rt[t]);
     uint32_t c = 0u;
     unsigned long long q = 0ull;
     const int first = rec_begin + wave * NS + (act ? st : 0);
@@ -1150,16 +1136,10 @@ __device__ void lo_score_lanes_range(lo_shared &sh, const float *__restrict__ co
         const bool live = act && r < rec_end;
         const f32x4 *rec = reinterpret_cast<const f32x4 *>(corr8) + (size_t)(live ? r : 0) * 4;
         const f32x4 A = rec[0], B = rec[1], C = rec[2];
-        const f32x2 px = { A.x, A.y }, py = { A.z, A.w }, pz = { B.x, B.y }, qx = { B.z, B.w }, qy = { C.x, C.y }, qz = { C.z, C.w };
-        const f32x2 x = __builtin_elementwise_fma(R00, px, __builtin_elementwise_fma(R01, py, __builtin_elementwise_fma(R02, pz, TX)));
-        const f32x2 y = __builtin_elementwise_fma(R10, px, __builtin_elementwise_fma(R11, py, __builtin_elementwise_fma(R12, pz, TY)));
-        const f32x2 z = __builtin_elementwise_fma(R20, px, __builtin_elementwise_fma(R21, py, __builtin_elementwise_fma(R22, pz, TZ)));
-        const f32x2 dx = x - qx, dy = y - qy, dz = z - qz;
-        const f32x2 d2 = __builtin_elementwise_fma(dx, dx, __builtin_elementwise_fma(dy, dy, dz * dz));
-        const f32x2 fx = d2 * SC;
-        const bool in0 = live && d2.x < thr2, in1 = live && 2 * r + 1 < m && d2.y < thr2;
-        c += (in0 ? 1u : 0u) + (in1 ? 1u : 0u);
-        q += (unsigned long long)((in0 ? (uint32_t)fx.x : 0u)) + (unsigned long long)((in1 ? (uint32_t)fx.y : 0u));
+        f32x2 o[6];
+        lr_record_operands(A, B, C, o);
+        const f32x2 d2 = lr_d2x2(S, o);
+        lr_add_pair(d2, live && d2.x < thr2, live && 2 * r + 1 < m && d2.y < thr2, c, q);
     }
     if (act && c) { atomicAdd(&sh.cnt[t], c); atomicAdd(&sh.ssq[t], q); }
     __syncthreads();
@@ -1308,9 +1288,8 @@ __device__ void lo_score_wide(lo_shared &sh, const float *__restrict__ corr8, in
         for (int k = 0; k < 12; ++k) Rt[k] = sh.Rt[t][k];
         unsigned c = 0; unsigned long long q = 0;
         for (int i = l; i < m; i += per) {
-            const float d2 = lo_d2(Rt, corr8[lr_corr_at(i, 0)], corr8[lr_corr_at(i, 1)], corr8[lr_corr_at(i, 2)], corr8[lr_corr_at(i, 3)],
-                                   corr8[lr_corr_at(i, 4)], corr8[lr_corr_at(i, 5)]);
-            if (d2 < thr2) { c += 1u; q += (unsigned long long)(uint32_t)(d2 * 1048576.0f); }
+            const float d2 = lr_corr_d2(Rt, corr8, i);
+            if (d2 < thr2) { c += 1u; q += (unsigned long long)lr_score_term(d2); }
         }
         if (c) { atomicAdd(&sh.cnt[t], c); atomicAdd(&sh.ssq[t], q); }
     }
@@ -1326,7 +1305,7 @@ __device__ __forceinline__ void lo_score(lo_shared &sh, const float *__restrict_
         else lo_score_lanes(sh, corr8, m, thr2);
         return;
     }
-    const bool narrow = ((double)(m / LO_THREADS + 2)) * (double)thr2 * 1048576.0 < 4.0e9;      // (a thread's correspondences x the largest term)
+    const bool narrow = ((double)(m / LO_THREADS + 2)) * (double)thr2 * (double)LR_SCORE_SCALE < 4.0e9;      // (a thread's correspondences x the largest term)
     if (!narrow) lo_score_wide(sh, corr8, m, thr2, ntrial);
     else lo_score_one(sh, corr8, m, thr2);
 }
@@ -1371,7 +1350,7 @@ ransac_lo_kernel(const float *__restrict__ corr8, int m_max, const int32_t *__re
     const unsigned long long tk0_ = tk_;
 #endif
     LO_COUNT(mode == 0 ? 9 : 10);
-    const uint32_t msac_T = p.scoring == 1 ? (uint32_t)(p.thr2 * 1048576.0f) : 0u;
+    const uint32_t msac_T = lr_msac_T(p.scoring, p.thr2);
     if (tid < 12) sh.curT[tid] = state->T[tid];
     if (tid == 0) { sh.curc = state->cnt; sh.curq = state->ssq; }
     const int call = state->lo_calls;
@@ -1497,10 +1476,10 @@ ransac_lo_kernel(const float *__restrict__ corr8, int m_max, const int32_t *__re
                 int bt = -1; unsigned bc = 0; unsigned long long bq = 0;
                 for (int t = 0; t < ntrial; ++t) {
                     if (sh.cnt[t] == 0u) continue;
-                    if (bt < 0 || better(sh.cnt[t], sh.ssq[t], t, bc, bq, bt, msac_T)) { bt = t; bc = sh.cnt[t]; bq = sh.ssq[t]; }
+                    if (bt < 0 || lr_score_better(sh.cnt[t], sh.ssq[t], t, bc, bq, bt, msac_T)) { bt = t; bc = sh.cnt[t]; bq = sh.ssq[t]; }
                 }
                 // strictly better than the model under optimisation
-                sh.flag = (bt >= 0 && better(bc, bq, 1, sh.curc, sh.curq, 0, msac_T)) ? bt : -1;
+                sh.flag = (bt >= 0 && lr_score_better(bc, bq, 1, sh.curc, sh.curq, 0, msac_T)) ? bt : -1;
                 if (sh.flag >= 0) { sh.curc = bc; sh.curq = bq; for (int k = 0; k < 12; ++k) sh.curT[k] = sh.T[bt][k]; }
             }
             __syncthreads();
@@ -1575,7 +1554,7 @@ inlier_mask_kernel(const float *__restrict__ src, const float *__restrict__ tgt,
 #pragma unroll
         for (int k = 0; k < 12; ++k) Rt[k] = (float)T[k];
         const int a = i0 ? i0[c] : c, b = i1 ? i1[c] : c;
-        in = lo_d2(Rt, src[3 * a], src[3 * a + 1], src[3 * a + 2], tgt[3 * b], tgt[3 * b + 1], tgt[3 * b + 2]) < thr2;
+        in = lr_score_d2(Rt, src[3 * a], src[3 * a + 1], src[3 * a + 2], tgt[3 * b], tgt[3 * b + 1], tgt[3 * b + 2]) < thr2;
         mask[c] = in ? 1 : 0;
     }
     if (n_inliers) {
@@ -1611,7 +1590,7 @@ int lr_ransac_run(lr_workspace *ws, const float *corr8, int m_max, const int32_t
     LR_REQUIRE(p->iters >= 0 && p->iters <= ws->max_iters, LR_ESIZE, "lr_ransac: iters exceeds the workspace");
     LR_REQUIRE(m_max >= 0 && m_max <= ws->max_n0, LR_ESIZE, "lr_ransac: m exceeds the workspace");
     LR_REQUIRE(p->thr2 > 0.0f && p->thr2 < 2048.0f, LR_EINVAL, "lr_ransac: thr2 must be in (0, 2048)");
-    int sub = (int)(4095.0 / ((double)p->thr2 * 1.0000001 + 1e-6));     // sub * thr2 * 2^20 < 2^32
+    int sub = (int)((4294967296.0 / (double)LR_SCORE_SCALE - 1.0) / ((double)p->thr2 * 1.0000001 + 1e-6));     // sub * thr2 * 2^20 < 2^32
     if (sub > 4096) sub = 4096;
     sub &= ~1;                  // the scoring loop takes correspondences two at a time
     if (sub < 2) sub = 2;       // 2 * thr2 * 2^20 < 2^32 for every admissible thr2 (< 2048)

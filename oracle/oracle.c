@@ -36,7 +36,8 @@
  *   d2(i,j)   = fmaf(-2, dot, n0[i] + n1[j]);  s = sqrtf(fmaxf(d2, 1e-30f))
  *   NN order  = ascending (s, j): first minimal value wins, as torch.min(dim=1) does.
  * The fp64 part of the contract (deterministic logarithm, SPRT threshold, Horn / Kabsch solver, moments -> transform, the SPRT and
- * local-optimisation constants) is lidarregistration_amd/csrc/lr_contract.h: one text, compiled here and by the HIP kernels.
+ * local-optimisation constants) and the fp32 scoring of a model (residual lr_score_d2, error term, MSAC threshold, winner ordering)
+ * are lidarregistration_amd/csrc/lr_contract.h: one text, compiled here and by the HIP kernels.
  */
 #include <math.h>
 #include <stdint.h>
@@ -305,16 +306,6 @@ static orc_ransac_params eff_params(const orc_ransac_params *in)
     return p;
 }
 
-/* is model (c, q, h) better than (bc, bq, bh)?  msac_T = (uint32)(thr2 * 2^20) for MSAC scoring, else 0 */
-static int model_better(uint32_t c, uint64_t q, int64_t h, uint32_t bc, uint64_t bq, int64_t bh, uint32_t msac_T)
-{
-    if (msac_T == 0u) return c > bc || (c == bc && (q < bq || (q == bq && h < bh)));
-    if (c == 0u) return 0;
-    if (bc == 0u) return 1;
-    const long long k = (long long)c * (long long)msac_T - (long long)q, bk = (long long)bc * (long long)msac_T - (long long)bq;
-    return k > bk || (k == bk && h < bh);
-}
-
 typedef struct {
     int64_t  best_h;          /* winning hypothesis id, -1 if none                    */
     uint32_t best_count;      /* its inlier count                                     */
@@ -350,19 +341,20 @@ ORC_API int orc_hypothesis(const float *src, const float *tgt, int m, const orc_
     return ok;
 }
 
+/* squared residual of correspondence i under the fp32 model: the scoring arithmetic of lr_contract.h */
+static inline float corr_d2(const float Rt[12], const float *src, const float *tgt, int i)
+{
+    return lr_score_d2(Rt, src[3 * i], src[3 * i + 1], src[3 * i + 2], tgt[3 * i], tgt[3 * i + 1], tgt[3 * i + 2]);
+}
+
 /* inlier count + fixed-point squared-error sum of one fp32 model over all m correspondences */
 static void score_model(const float *src, const float *tgt, int m, const float Rt[12], float thr2,
                         uint32_t *count, uint64_t *ssq)
 {
     uint32_t c = 0; uint64_t q = 0;
     for (int i = 0; i < m; ++i) {
-        float px = src[3 * i], py = src[3 * i + 1], pz = src[3 * i + 2];
-        float x = fmaf(Rt[0], px, fmaf(Rt[1], py, fmaf(Rt[2], pz, Rt[3])));
-        float y = fmaf(Rt[4], px, fmaf(Rt[5], py, fmaf(Rt[6], pz, Rt[7])));
-        float z = fmaf(Rt[8], px, fmaf(Rt[9], py, fmaf(Rt[10], pz, Rt[11])));
-        float dx = x - tgt[3 * i], dy = y - tgt[3 * i + 1], dz = z - tgt[3 * i + 2];
-        float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
-        if (d2 < thr2) { c += 1; q += (uint64_t)(uint32_t)(d2 * 1048576.0f); }
+        const float d2 = corr_d2(Rt, src, tgt, i);
+        if (d2 < thr2) { c += 1; q += (uint64_t)lr_score_term(d2); }
     }
     *count = c; *ssq = q;
 }
@@ -406,12 +398,7 @@ static int sprt_test(const float *src, const float *tgt, int m, const float Rt[1
     double lambda = 1.0;
     int inl = 0;
     for (int i = 0; i < n; ++i) {
-        float px = src[3 * i], py = src[3 * i + 1], pz = src[3 * i + 2];
-        float x = fmaf(Rt[0], px, fmaf(Rt[1], py, fmaf(Rt[2], pz, Rt[3])));
-        float y = fmaf(Rt[4], px, fmaf(Rt[5], py, fmaf(Rt[6], pz, Rt[7])));
-        float z = fmaf(Rt[8], px, fmaf(Rt[9], py, fmaf(Rt[10], pz, Rt[11])));
-        float dx = x - tgt[3 * i], dy = y - tgt[3 * i + 1], dz = z - tgt[3 * i + 2];
-        float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+        const float d2 = corr_d2(Rt, src, tgt, i);
         if (d2 < thr2) { inl += 1; lambda = lambda * fin; } else lambda = lambda * fout;
         if (lambda > A) { *k_out = i + 1; *inl_out = inl; return 0; }
     }
@@ -467,12 +454,7 @@ static int lo_inliers(const float *src, const float *tgt, int m, const double T[
     for (int k = 0; k < 12; ++k) Rt[k] = (float)T[k];
     int n = 0;
     for (int i = 0; i < m; ++i) {
-        float px = src[3 * i], py = src[3 * i + 1], pz = src[3 * i + 2];
-        float x = fmaf(Rt[0], px, fmaf(Rt[1], py, fmaf(Rt[2], pz, Rt[3])));
-        float y = fmaf(Rt[4], px, fmaf(Rt[5], py, fmaf(Rt[6], pz, Rt[7])));
-        float z = fmaf(Rt[8], px, fmaf(Rt[9], py, fmaf(Rt[10], pz, Rt[11])));
-        float dx = x - tgt[3 * i], dy = y - tgt[3 * i + 1], dz = z - tgt[3 * i + 2];
-        float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+        const float d2 = corr_d2(Rt, src, tgt, i);
         if (d2 < thr2) list[n++] = i;
     }
     return n;
@@ -513,7 +495,7 @@ static void lo_draw(uint64_t seed, int call, int round, int trial, int n, int32_
 static int lo_optimise(const float *src, const float *tgt, int m, const orc_ransac_params *p, int call, double T[16],
                        uint32_t *c, uint64_t *q, int32_t *list)
 {
-    const uint32_t msac_T = p->scoring == 1 ? (uint32_t)(p->thr2 * 1048576.0f) : 0u;
+    const uint32_t msac_T = lr_msac_T(p->scoring, p->thr2);
     int changed = 0;
     for (int round = 0; round < p->lo_rounds; ++round) {
         const int nI = lo_inliers(src, tgt, m, T, p->thr2, list);
@@ -535,10 +517,10 @@ static int lo_optimise(const float *src, const float *tgt, int m, const orc_rans
             uint32_t tc; uint64_t tq;
             orc_score(src, tgt, m, Tt, p->thr2, &tc, &tq);
             if (tc == 0) continue;
-            if (bt < 0 || model_better(tc, tq, t, bc, bq, bt, msac_T)) { bt = t; bc = tc; bq = tq; memcpy(bT, Tt, sizeof(bT)); }
+            if (bt < 0 || lr_score_better(tc, tq, t, bc, bq, bt, msac_T)) { bt = t; bc = tc; bq = tq; memcpy(bT, Tt, sizeof(bT)); }
         }
         /* strictly better than the current model (an equal score keeps it: the id of the current model counts as lower) */
-        if (bt < 0 || !model_better(bc, bq, 1, *c, *q, 0, msac_T)) break;
+        if (bt < 0 || !lr_score_better(bc, bq, 1, *c, *q, 0, msac_T)) break;
         memcpy(T, bT, sizeof(bT)); *c = bc; *q = bq; changed = 1;
     }
     return changed;
@@ -585,7 +567,7 @@ ORC_API void orc_ransac(const float *src, const float *tgt, int m, const orc_ran
     const int geometric = use_exit && p->batch <= 0;
     int64_t B = use_exit ? (p->batch > 0 ? p->batch : 1024) : (p->iters > 0 ? p->iters : 1);
     int32_t *G = p->sampler == 1 ? prosac_table(m, p->sample_size, p->prosac_growth > 0 ? p->prosac_growth : 100000) : NULL;
-    const uint32_t msac_T = p->scoring == 1 ? (uint32_t)(p->thr2 * 1048576.0f) : 0u;
+    const uint32_t msac_T = lr_msac_T(p->scoring, p->thr2);
     for (int64_t h0 = 0; h0 < p->iters; h0 += B, B = geometric ? 8 * B : B) {
         const int64_t h1 = h0 + B < p->iters ? h0 + B : p->iters;
         int64_t bb_h = -1; uint32_t bb_c = 0; uint64_t bb_q = 0;      /* winner of this batch */
@@ -609,17 +591,17 @@ ORC_API void orc_ransac(const float *src, const float *tgt, int m, const orc_ran
                 uint32_t c; uint64_t q;
                 score_model(src, tgt, m, Rt, p->thr2, &c, &q);
                 if (c == 0) continue;
-                if (lh < 0 || model_better(c, q, h, lc, lq, lh, msac_T)) { lh = h; lc = c; lq = q; }
+                if (lh < 0 || lr_score_better(c, q, h, lc, lq, lh, msac_T)) { lh = h; lc = c; lq = q; }
             }
 #pragma omp critical
             {
                 n_valid += lv; b_inl += l_inl; b_pts += l_pts;
-                if (lh >= 0 && (bb_h < 0 || model_better(lc, lq, lh, bb_c, bb_q, bb_h, msac_T))) { bb_h = lh; bb_c = lc; bb_q = lq; }
+                if (lh >= 0 && (bb_h < 0 || lr_score_better(lc, lq, lh, bb_c, bb_q, bb_h, msac_T))) { bb_h = lh; bb_c = lc; bb_q = lq; }
             }
         }
         rej_inl += b_inl; rej_pts += b_pts;
         /* the batch winner replaces the best so far when it scores better (an optimised model keeps the id of its seed) */
-        if (bb_h >= 0 && (best_h < 0 || model_better(bb_c, bb_q, bb_h, best_c, best_q, best_h, msac_T))) {
+        if (bb_h >= 0 && (best_h < 0 || lr_score_better(bb_c, bb_q, bb_h, best_c, best_q, best_h, msac_T))) {
             best_h = bb_h; best_c = bb_c; best_q = bb_q;
             hypothesis_T(src, tgt, m, p, (uint64_t)best_h, Tb, NULL, G); have_T = 1;
             if (p->local_opt == 1 && lo_calls < p->lo_max_calls) { lo_optimise(src, tgt, m, p, lo_calls, Tb, &best_c, &best_q, lo_list); lo_calls += 1; }
@@ -674,7 +656,7 @@ ORC_API void orc_ransac_seq(const float *src, const float *tgt, int m, const orc
     uint64_t rej_inl = 0, rej_pts = 0;
     const int use_exit = p->confidence > 0.0f && p->confidence < 1.0f;
     int32_t *G = p->sampler == 1 ? prosac_table(m, p->sample_size, p->prosac_growth > 0 ? p->prosac_growth : 100000) : NULL;
-    const uint32_t msac_T = p->scoring == 1 ? (uint32_t)(p->thr2 * 1048576.0f) : 0u;
+    const uint32_t msac_T = lr_msac_T(p->scoring, p->thr2);
     double k_needed = INFINITY;
     int64_t h = 0;
     for (; h < p->iters; ++h) {
@@ -688,12 +670,7 @@ ORC_API void orc_ransac_seq(const float *src, const float *tgt, int m, const orc
             const double fin = sprt_delta / sprt_eps, fout = (1.0 - sprt_delta) / (1.0 - sprt_eps);
             double lambda = 1.0; int inl = 0, rejected = 0, kk = m;
             for (int i = 0; i < m; ++i) {
-                float px = src[3 * i], py = src[3 * i + 1], pz = src[3 * i + 2];
-                float x = fmaf(Rt[0], px, fmaf(Rt[1], py, fmaf(Rt[2], pz, Rt[3])));
-                float y = fmaf(Rt[4], px, fmaf(Rt[5], py, fmaf(Rt[6], pz, Rt[7])));
-                float z = fmaf(Rt[8], px, fmaf(Rt[9], py, fmaf(Rt[10], pz, Rt[11])));
-                float dx = x - tgt[3 * i], dy = y - tgt[3 * i + 1], dz = z - tgt[3 * i + 2];
-                float d2 = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+                const float d2 = corr_d2(Rt, src, tgt, i);
                 if (d2 < p->thr2) { inl += 1; lambda = lambda * fin; } else lambda = lambda * fout;
                 if (lambda > sprt_A) { rejected = 1; kk = i + 1; break; }
             }
@@ -708,7 +685,7 @@ ORC_API void orc_ransac_seq(const float *src, const float *tgt, int m, const orc
         uint32_t c; uint64_t q;
         score_model(src, tgt, m, Rt, p->thr2, &c, &q);
         if (c == 0) continue;
-        if (best_h < 0 || model_better(c, q, h, best_c, best_q, best_h, msac_T)) {
+        if (best_h < 0 || lr_score_better(c, q, h, best_c, best_q, best_h, msac_T)) {
             best_h = h; best_c = c; best_q = q; memcpy(Tb, T, sizeof(Tb)); have_T = 1;
             if (p->local_opt == 1 && lo_calls < p->lo_max_calls) { lo_optimise(src, tgt, m, p, lo_calls, Tb, &best_c, &best_q, lo_list); lo_calls += 1; }
             if (p->use_elc == 2) {

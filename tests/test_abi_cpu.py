@@ -150,3 +150,16 @@ def test_no_ablation_switches_in_the_shipped_kernels():
     conds = re.findall(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b.*$", nn, flags=re.M)
     assert len(conds) <= 6, conds
     assert any("LR_PB_PROBE" in c for c in conds)
+
+
+def test_the_scoring_contract_has_one_text():
+    """The fp32 scoring arithmetic lives in lr_contract.h alone: the 2^20 fixed-point scale is spelled out only there, and neither side keeps a
+    winner ordering of its own (the oracle's model_better, the kernels' better) next to lr_score_better."""
+    csrc = os.path.join(ROOT, "lidarregistration_amd", "csrc")
+    files = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))] + [os.path.join(ROOT, "oracle", "oracle.c")]
+    assert len(files) >= 10
+    for path in files:
+        text, name = open(path).read(), os.path.basename(path)
+        assert ("1048576" in text) == (name == "lr_contract.h"), f"{name}: the fixed-point scale belongs to lr_contract.h (LR_SCORE_SCALE) alone"
+        assert "model_better" not in text, f"{name} still carries model_better"
+        assert not re.search(r"__device__[^;{}()]*\bbetter\s*\(", text), f"{name} still defines a device-side better()"
