@@ -506,9 +506,14 @@ gpf_score_cell_kernel(int n0, int G, const uint32_t *__restrict__ mm, const uint
         const float denx = (x1 - x0) + 1e-3f, deny = (y1 - y0) + 1e-3f;
         float qx = floorf((float)G * ((xyz0[3 * pi] - x0) / (denx)));
         float qy = floorf((float)G * ((xyz0[3 * pi + 1] - y0) / (deny)));
-        int c = (int)qx * G + (int)qy;
+        // a pair is in cell (qx, qy) only if BOTH quadrants are in [0, G) (matching.py:149-152): with a range >= 32768 float32 absorbs the
+        // 1e-3 and the largest coordinate gets quadrant G, which as a flat index would wrap into cell (qx + 1, 0).  Non-finite
+        // coordinates fail the test too.  No cell (-1): never counted, never kept.
+        const float fG = (float)G;
+        const bool in_grid = qx >= 0.0f && qx < fG && qy >= 0.0f && qy < fG;
+        const int c = in_grid ? (int)qx * G + (int)qy : -1;
         cell[i] = c;
-        if (c >= 0 && c < C) atomicAdd(&s_cnt[c], 1);      // a pair with non-finite coordinates has no cell: it is never kept
+        if (c >= 0) atomicAdd(&s_cnt[c], 1);
     }
     __syncthreads();
     for (int k = threadIdx.x; k < C; k += 256) if (s_cnt[k]) atomicAdd(&cell_count[k], s_cnt[k]);

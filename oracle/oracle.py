@@ -219,8 +219,11 @@ def Grid_Prioritized_Filter(fcgf_feats0, fcgf_feats1, corres_idx0, corres_idx1, 
     xyz0 = np.asarray(xyz0, dtype=np.float32)
     quadrant_i = _to_quads(xyz0[corres_idx0, 0], GRID_WID)
     quadrant_j = _to_quads(xyz0[corres_idx0, 1], GRID_WID)
-    cell = (quadrant_i * GRID_WID + quadrant_j).astype(np.int64)
-    max_per_quad = np.bincount(cell, minlength=GRID_WID * GRID_WID).astype(np.float64).reshape(GRID_WID, GRID_WID)
+    # a pair belongs to cell (qi, qj) only if BOTH quadrants are in range(GRID_WID) (matching.py:149-152): once M - m >= 32768 float32
+    # absorbs the EPS and the largest coordinate gets quadrant GRID_WID -- such a pair is in no cell (-1), never counted, never kept
+    in_grid = (quadrant_i >= 0) & (quadrant_i < GRID_WID) & (quadrant_j >= 0) & (quadrant_j < GRID_WID)
+    cell = np.where(in_grid, quadrant_i * GRID_WID + quadrant_j, -1).astype(np.int64)
+    max_per_quad = np.bincount(cell[in_grid], minlength=GRID_WID * GRID_WID).astype(np.float64).reshape(GRID_WID, GRID_WID)
 
     per_quad = gpf_water_fill(max_per_quad, TOTAL_NUM)
 
@@ -251,10 +254,15 @@ def sparse_quantize(coordinates, return_index=True):
     """ME.utils.sparse_quantize(coordinates, return_index=True) as the reference's loaders use it
     (dataloader/generic_balanced_loader.py:62-63).  MinkowskiEngine 0.5.4 (Requirements/conda_GC_full.yml:106) is not vendored:
     PARITY UNPINNED.  Its CPU path floors the coordinates and inserts the rows one after the other into a hash map, so the
-    kept row of every occupied cell is its first one, and the kept indices come out in ascending order."""
-    cells = np.floor(np.asarray(coordinates, np.float64)).astype(np.int64)
-    _, first = np.unique(cells, axis=0, return_index=True)
-    sel = np.sort(first)
+    kept row of every occupied cell is its first one, and the kept indices come out in ascending order.  The library's grid is
+    (-2^20, 2^20) cells per axis (csrc/lr_voxel.hip): rows outside it or not finite are dropped, here as there."""
+    fl = np.floor(np.asarray(coordinates, np.float64)).reshape(-1, 3)
+    with np.errstate(invalid="ignore"):
+        inside = np.flatnonzero((np.abs(fl) < 2.0 ** 20).all(axis=1))          # (False for NaN / inf)
+    cells = np.zeros(fl.shape, np.int64)
+    cells[inside] = fl[inside].astype(np.int64)
+    _, first = np.unique(cells[inside], axis=0, return_index=True)
+    sel = np.sort(inside[first])
     return (cells[sel].astype(np.int32), sel.astype(np.int64)) if return_index else cells[sel].astype(np.int32)
 
 
