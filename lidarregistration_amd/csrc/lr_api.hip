@@ -172,7 +172,7 @@ extern "C" int lr_workspace_create_batch(lr_workspace **out, int max_pairs, int 
     ws->device = dev; ws->n_cus = di->cus;
     ws->max_n0 = max_n0; ws->max_n1 = max_n1; ws->max_n = max_n0 > max_n1 ? max_n0 : max_n1;
     ws->dim = dim; ws->max_iters = max_iters > 0 ? max_iters : 1;
-    ws->max_pairs = max_pairs; ws->zP = 1; ws->z = lr_zargs{ 0, nullptr };
+    ws->max_pairs = max_pairs;
     // tuning defaults (lr_workspace_option changes them; no environment variable is read anywhere in this library)
     ws->nn_blocks_target = 3 * ws->n_cus;      // 3 blocks per CU = every block of a single pair's filter pass resident at once (768 on an MI355X)
     ws->nn_blocks_batch = 12 * ws->n_cus;      // (3072)
@@ -207,9 +207,9 @@ extern "C" int lr_workspace_create_batch(lr_workspace **out, int max_pairs, int 
         (void)hipFree(ws->base); delete ws; lr_set_error("lr_workspace_create: hipMemset failed"); return LR_EHIP;
     }
     for (int k = 0; k < LR_NEV; ++k)
-        if (hipEventCreate(&ws->ev[k]) != hipSuccess) {
+        if (hipEventCreate(&ws->timer.ev[k]) != hipSuccess) {
             // (everything created so far goes: the events before this one, the pinned hint, the arena)
-            for (int q = 0; q < k; ++q) (void)hipEventDestroy(ws->ev[q]);
+            for (int q = 0; q < k; ++q) (void)hipEventDestroy(ws->timer.ev[q]);
             if (ws->form_host) (void)hipHostFree(ws->form_host);
             (void)hipFree(ws->base); delete ws; lr_set_error("lr_workspace_create: hipEventCreate failed"); return LR_EHIP;
         }
@@ -221,7 +221,7 @@ extern "C" int lr_workspace_destroy(lr_workspace *ws)
 {
     if (!ws) return LR_OK;
     if (ws->form_host) (void)hipHostFree(ws->form_host);
-    for (int k = 0; k < LR_NEV; ++k) (void)hipEventDestroy(ws->ev[k]);
+    for (int k = 0; k < LR_NEV; ++k) (void)hipEventDestroy(ws->timer.ev[k]);
     (void)hipFree(ws->base);
     delete ws;
     return LR_OK;
@@ -297,7 +297,7 @@ extern "C" int lr_workspace_lists_batch(lr_workspace *ws, int npairs, int width,
     return LR_OK;
 }
 
-// zero `bytes` (a multiple of 4) of scratch at p (an arena-0 pointer) in the arena of every pair of the call in flight.  A kernel, not
+// zero `bytes` (a multiple of 4) of scratch at p (an arena-0 pointer) in the arena of every pair of the call.  A kernel, not
 // hipMemset2DAsync: one launch whatever the number of pairs, and a plain kernel node when the caller captures the call in a HIP graph
 // (the 2-D memset node faulted on replay with the arena stride as its pitch: tests/test_gpu_batch.py, round 4).
 __global__ void __launch_bounds__(256) zero_scratch_kernel(uint32_t *__restrict__ p, size_t words, lr_zargs z)
@@ -305,12 +305,12 @@ __global__ void __launch_bounds__(256) zero_scratch_kernel(uint32_t *__restrict_
     lr_z(p, z, blockIdx.z);
     for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < words; k += (size_t)gridDim.x * 256) p[k] = 0u;
 }
-int lr_zero_scratch(lr_workspace *ws, void *p, size_t bytes, hipStream_t st)
+int lr_zero_scratch(const lr_call &c, void *p, size_t bytes)
 {
     const size_t words = (bytes + 3) / 4;
     int blocks = (int)((words + 255) / 256);
     if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(zero_scratch_kernel, dim3(blocks < 1 ? 1 : blocks, 1, ws->zP), dim3(256), 0, st, reinterpret_cast<uint32_t *>(p), words, ws->z);
+    hipLaunchKernelGGL(zero_scratch_kernel, dim3(blocks < 1 ? 1 : blocks, 1, c.pairs), dim3(256), 0, c.st, reinterpret_cast<uint32_t *>(p), words, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
@@ -330,32 +330,50 @@ extern "C" int lr_workspace_clock(lr_workspace *ws, double *mhz, unsigned long l
     return LR_OK;
 }
 
-extern "C" int lr_workspace_timing(lr_workspace *ws, int enable)
+// ------------------------------------------------------------------ stage timer
+// The rule of every event.  `begun` = the sample in flight has its forward filter pass (it is pending until collected); c.armed = the
+// call came in with timing on and nothing pending, so it is the one call that may begin a sample and bracket itself.
+int lr_timer_mark(const lr_call &c, lr_event e)
 {
-    LR_CHECK_DEVICE(ws, nullptr, "lr_workspace_timing");
-    ws->timing = enable; ws->ev_pending = 0; ws->rev_recorded = 0; ws->nn_ms_acc = 0; ws->ransac_ms_acc = 0; ws->n_samples = 0;
-    ws->call_ms_acc = 0; ws->fwd_ms_acc = 0; ws->fwd_filter_ms_acc = 0; ws->rev_filter_ms_acc = 0; ws->rev_ms_acc = 0; ws->rev_done_recorded = 0;
+    lr_stage_timer &t = c.ws->timer;
+    bool due = false;
+    switch (e) {
+    case LR_EV_FWD_FILTER_BEGIN: case LR_EV_FWD_FILTER_END: due = c.armed && !t.begun(); break;      // (the first forward pass of the call)
+    case LR_EV_REV_FILTER_BEGIN: case LR_EV_REV_FILTER_END: due = t.begun() && !t.has(LR_EV_REV_FILTER_END) && !t.has(LR_EV_RANSAC_END); break;
+    case LR_EV_RANSAC_BEGIN: case LR_EV_RANSAC_END: due = t.begun() && !t.has(LR_EV_RANSAC_END); break;
+    case LR_EV_CALL_BEGIN: case LR_EV_FWD_NN_DONE: case LR_EV_REV_NN_DONE: due = c.armed; break;
+    case LR_EV_CALL_END: due = c.armed && t.has(LR_EV_RANSAC_END); break;
+    case LR_NEV: break;
+    }
+    if (!t.on || !due) return LR_OK;
+    LR_HIP(hipEventRecord(t.ev[e], c.st));
+    t.recorded |= 1u << e;
     return LR_OK;
 }
 
-// folds the events of the last timed call into the sums
-static int lr_timing_collect(lr_workspace *ws)
+// folds the intervals of the pending sample whose events were recorded into the sums
+static int lr_timer_collect(lr_stage_timer &t)
 {
-    if (ws->ev_pending >= 1) {
-        float ms = 0;
-        LR_HIP(hipEventElapsedTime(&ms, ws->ev[0], ws->ev[1]));
-        ws->nn_ms_acc += ms; ws->fwd_filter_ms_acc += ms;
-        if (ws->rev_recorded) { LR_HIP(hipEventElapsedTime(&ms, ws->ev[4], ws->ev[5])); ws->nn_ms_acc += ms; ws->rev_filter_ms_acc += ms; ws->rev_recorded = 0; }
-        if (ws->ev_pending >= 2) { LR_HIP(hipEventElapsedTime(&ms, ws->ev[2], ws->ev[3])); ws->ransac_ms_acc += ms; }
-        if (ws->ev_pending >= 3) {
-            LR_HIP(hipEventElapsedTime(&ms, ws->ev[6], ws->ev[8])); ws->call_ms_acc += ms;
-            LR_HIP(hipEventElapsedTime(&ms, ws->ev[6], ws->ev[7])); ws->fwd_ms_acc += ms;
-            if (ws->rev_done_recorded) { LR_HIP(hipEventElapsedTime(&ms, ws->ev[7], ws->ev[9])); ws->rev_ms_acc += ms; }
-        }
-        ws->rev_done_recorded = 0;
-        ws->n_samples += 1;
-        ws->ev_pending = 0;
+    if (!t.begun()) return LR_OK;
+    float ms = 0;
+    auto span = [&](lr_event a, lr_event b) -> int { LR_HIP(hipEventElapsedTime(&ms, t.ev[a], t.ev[b])); return LR_OK; };
+    LR_TRY_HIP(span(LR_EV_FWD_FILTER_BEGIN, LR_EV_FWD_FILTER_END)); t.ms.nn += ms; t.ms.fwd_filter += ms;
+    if (t.has(LR_EV_REV_FILTER_END)) { LR_TRY_HIP(span(LR_EV_REV_FILTER_BEGIN, LR_EV_REV_FILTER_END)); t.ms.nn += ms; t.ms.rev_filter += ms; }
+    if (t.has(LR_EV_RANSAC_END)) { LR_TRY_HIP(span(LR_EV_RANSAC_BEGIN, LR_EV_RANSAC_END)); t.ms.ransac += ms; }
+    if (t.has(LR_EV_CALL_END)) {
+        LR_TRY_HIP(span(LR_EV_CALL_BEGIN, LR_EV_CALL_END)); t.ms.call += ms;
+        LR_TRY_HIP(span(LR_EV_CALL_BEGIN, LR_EV_FWD_NN_DONE)); t.ms.fwd += ms;
+        if (t.has(LR_EV_REV_NN_DONE)) { LR_TRY_HIP(span(LR_EV_FWD_NN_DONE, LR_EV_REV_NN_DONE)); t.ms.rev += ms; }
     }
+    t.n_samples += 1;
+    t.recorded = 0;
+    return LR_OK;
+}
+
+extern "C" int lr_workspace_timing(lr_workspace *ws, int enable)
+{
+    LR_CHECK_DEVICE(ws, nullptr, "lr_workspace_timing");
+    ws->timer.on = enable; ws->timer.recorded = 0; ws->timer.n_samples = 0; ws->timer.ms = {};
     return LR_OK;
 }
 
@@ -363,26 +381,27 @@ static int lr_timing_collect(lr_workspace *ws)
 extern "C" int lr_workspace_timing_read(lr_workspace *ws, float *nn_ms, float *ransac_ms, int *n_samples)
 {
     LR_CHECK_DEVICE(ws, nullptr, "lr_workspace_timing_read");
-    LR_TRY_HIP(lr_timing_collect(ws));
-    if (nn_ms) *nn_ms = ws->nn_ms_acc;
-    if (ransac_ms) *ransac_ms = ws->ransac_ms_acc;
-    if (n_samples) *n_samples = ws->n_samples;
+    LR_TRY_HIP(lr_timer_collect(ws->timer));
+    if (nn_ms) *nn_ms = ws->timer.ms.nn;
+    if (ransac_ms) *ransac_ms = ws->timer.ms.ransac;
+    if (n_samples) *n_samples = ws->timer.n_samples;
     return LR_OK;
 }
 
 // Stage times of the timed pair-pipeline calls so far (sums in ms over *n_samples calls; the caller has synchronised the stream):
 // out[0] the whole call, out[1] the forward NN (norms + f16 copies, filter pass, exact verification: find_nn of matching.py:22-65 with
 // the second neighbour), out[2] / out[3] the forward / reverse filter-pass launch, out[4] hypothesis generation + scoring of the
-// first RANSAC batch.  What FR.py:117 bills as registration time is out[0] - out[1] + (the second neighbour's share of out[1]).
+// first RANSAC batch, out[5] the reverse NN (ordering, filter pass, exact verification).
+// What FR.py:117 bills as registration time is out[0] - out[1] + (the second neighbour's share of out[1]).
 extern "C" int lr_workspace_stage_times(lr_workspace *ws, float out[8], int *n_samples)
 {
     LR_REQUIRE(ws && out, LR_EINVAL, "lr_workspace_stage_times: null pointer");
     LR_CHECK_DEVICE(ws, nullptr, "lr_workspace_stage_times");
-    LR_TRY_HIP(lr_timing_collect(ws));
-    out[0] = ws->call_ms_acc; out[1] = ws->fwd_ms_acc; out[2] = ws->fwd_filter_ms_acc; out[3] = ws->rev_filter_ms_acc; out[4] = ws->ransac_ms_acc;
-    out[5] = ws->rev_ms_acc;
+    const lr_stage_timer &t = ws->timer;
+    LR_TRY_HIP(lr_timer_collect(ws->timer));
+    out[0] = t.ms.call; out[1] = t.ms.fwd; out[2] = t.ms.fwd_filter; out[3] = t.ms.rev_filter; out[4] = t.ms.ransac; out[5] = t.ms.rev;
     out[6] = out[7] = 0.0f;
-    if (n_samples) *n_samples = ws->n_samples;
+    if (n_samples) *n_samples = t.n_samples;
     return LR_OK;
 }
 
@@ -448,66 +467,52 @@ __global__ void pad_patch_descs_kernel(lr_pair_desc *__restrict__ descs, int npa
         descs[k].F1 = reinterpret_cast<const float *>(reinterpret_cast<const char *>(P1) + (size_t)k * stride);
     }
 }
-static void pad_if_narrow(lr_workspace *ws, const float *&F0, int n0, const float *&F1, int n1, int &dim, hipStream_t st)
+static void pad_if_narrow(const lr_call &c, const float *&F0, int n0, const float *&F1, int n1, int &dim)
 {
     if (dim == LR_FEAT_DIM) return;
+    lr_workspace *ws = c.ws;
     const int nblk_a = lr_cdiv(n0, 8);
-    hipLaunchKernelGGL(pad_feats_kernel, dim3(nblk_a + lr_cdiv(n1, 8), 1, ws->zP), dim3(256), 0, st, F0, n0, ws->P0, F1, n1, ws->P1, dim, nblk_a, ws->z);
-    if (ws->z.descs) hipLaunchKernelGGL(pad_patch_descs_kernel, dim3(1), dim3(64), 0, st, ws->descs, ws->zP, ws->P0, ws->P1, ws->stride);
+    hipLaunchKernelGGL(pad_feats_kernel, dim3(nblk_a + lr_cdiv(n1, 8), 1, c.pairs), dim3(256), 0, c.st, F0, n0, ws->P0, F1, n1, ws->P1, dim, nblk_a, c.z);
+    if (c.z.descs) hipLaunchKernelGGL(pad_patch_descs_kernel, dim3(1), dim3(64), 0, c.st, ws->descs, c.pairs, ws->P0, ws->P1, ws->stride);
     F0 = ws->P0; F1 = ws->P1; dim = LR_FEAT_DIM;
 }
 
-// norms + f16 operand copies of both clouds
-static int prep_both(lr_workspace *ws, const float *F0, int n0, const float *F1, int n1, hipStream_t st, bool zero_counters = false)
+// What the operators over two descriptor clouds start with: the argument and device checks, `required` (the operator's own pointers,
+// refused with `required_msg`), then padding and the norms + f16 operand copies of both clouds; F0 / F1 / dim name the padded copies
+// afterwards.  The operator's own check travels through here only because it sits between the shared checks and the first launch:
+// which error a bad call gets, and that it forgets the last batch first, stay as they were.
+static int operator_prep(lr_workspace *ws, const float *&F0, int n0, const float *&F1, int n1, int &dim, void *stream, const char *who,
+                         bool required, const char *required_msg, lr_call *call)
 {
-    return lr_nn16_prep(ws, F0, n0, F1, n1, st, zero_counters);      // the prep kernel clears the counter block itself
-}
-
-// forward: rows of cloud 0 against cloud 1 (first + second NN)
-static int nn_forward(lr_workspace *ws, const float *F0, int n0, const float *F1, int n1,
-                      int32_t *idx1, int32_t *idx2, float *s1, float *s2, hipStream_t st, bool seed_reverse = false)
-{
-    return lr_nn16_run(ws, F0, ws->H0, ws->nrm0, n0, F1, ws->H1, ws->nrm1, ws->nn_range + 2, n1,
-                       idx2 ? 2 : 1, idx1, idx2, s1, idx2 ? s2 : nullptr, st, seed_reverse);
-}
-
-// reverse: rows of cloud 1 against cloud 0 (first NN only).  The reference restricts it to the unique forward
-// targets (matching.py:224-225); rows that are nobody's target never enter the intersection, so all rows is equivalent.
-static int nn_reverse(lr_workspace *ws, const float *F0, int n0, const float *F1, int n1, const int32_t *fwd_idx1,
-                      int32_t *rev, hipStream_t st, bool seeded = false)
-{
-    // seeded by the forward pairs: only columns some query points at are resolved (others get -1)
-    return lr_nn16_reverse(ws, F0, ws->H0, ws->nrm0, ws->bmax0, n0, F1, ws->H1, ws->nrm1, n1, fwd_idx1, rev, st, seeded);
+    LR_TRY(check_nn_args(ws, F0, n0, F1, n1, dim, who));
+    LR_CHECK_DEVICE(ws, stream, who);
+    forget_last_batch(ws);
+    LR_REQUIRE(required, LR_EINVAL, required_msg);
+    *call = lr_call_single(ws, stream);
+    pad_if_narrow(*call, F0, n0, F1, n1, dim);
+    return lr_nn16_prep(*call, F0, n0, F1, n1);
 }
 
 // ------------------------------------------------------------------ a1/a2
 extern "C" int lr_nn_top2(lr_workspace *ws, const float *F0, int n0, const float *F1, int n1, int dim,
                           int32_t *idx1, int32_t *idx2, float *s1, float *s2, void *stream)
 {
-    LR_TRY(check_nn_args(ws, F0, n0, F1, n1, dim, "lr_nn_top2"));
-    LR_CHECK_DEVICE(ws, stream, "lr_nn_top2");
-    forget_last_batch(ws);
-    LR_REQUIRE(idx1, LR_EINVAL, "lr_nn_top2: idx1 is required");
-    hipStream_t st = (hipStream_t)stream;
-    pad_if_narrow(ws, F0, n0, F1, n1, dim, st);
-    LR_TRY(prep_both(ws, F0, n0, F1, n1, st));
-    return nn_forward(ws, F0, n0, F1, n1, idx1, idx2, s1, s2, st);
+    lr_call c;
+    LR_TRY(operator_prep(ws, F0, n0, F1, n1, dim, stream, "lr_nn_top2", idx1, "lr_nn_top2: idx1 is required", &c));
+    return lr_nn16_run(c, F0, n0, F1, n1, idx1, idx2, s1, s2);
 }
 
 // ------------------------------------------------------------------ a3-a5
+// (the reverse NN over all rows of cloud 1: the reference restricts it to the unique forward targets (matching.py:224-225); rows that
+// are nobody's target never enter the intersection, so all rows is equivalent)
 extern "C" int lr_nn_to_mutual(lr_workspace *ws, const float *F0, int n0, const float *F1, int n1, int dim,
                                const int32_t *idx1, const int32_t *idx2, uint8_t *is_bb,
                                int32_t *o0, int32_t *o1, int32_t *o2, int32_t *n_out, void *stream)
 {
-    LR_TRY(check_nn_args(ws, F0, n0, F1, n1, dim, "lr_nn_to_mutual"));
-    LR_CHECK_DEVICE(ws, stream, "lr_nn_to_mutual");
-    forget_last_batch(ws);
-    LR_REQUIRE(idx1, LR_EINVAL, "lr_nn_to_mutual: idx1 is required");
-    hipStream_t st = (hipStream_t)stream;
-    pad_if_narrow(ws, F0, n0, F1, n1, dim, st);
-    LR_TRY(prep_both(ws, F0, n0, F1, n1, st));
-    LR_TRY(nn_reverse(ws, F0, n0, F1, n1, idx1, ws->rev_idx1, st));
-    return lr_mutual_run(ws, n0, idx1, idx2, ws->rev_idx1, is_bb, o0, o1, o2, n_out, st);
+    lr_call c;
+    LR_TRY(operator_prep(ws, F0, n0, F1, n1, dim, stream, "lr_nn_to_mutual", idx1, "lr_nn_to_mutual: idx1 is required", &c));
+    LR_TRY(lr_nn16_reverse(c, F0, n0, F1, n1, idx1, ws->rev_idx1));
+    return lr_mutual_run(c, n0, idx1, idx2, ws->rev_idx1, is_bb, o0, o1, o2, n_out);
 }
 
 // ------------------------------------------------------------------ a7
@@ -515,16 +520,11 @@ extern "C" int lr_gpf(lr_workspace *ws, const float *F0, int n0, const float *F1
                       const int32_t *idx1, const int32_t *idx2, const float *xyz0, int grid_wid, double factor,
                       int32_t *o0, int32_t *o1, int32_t *o2, float *oscore, int32_t *n_out, void *stream)
 {
-    LR_TRY(check_nn_args(ws, F0, n0, F1, n1, dim, "lr_gpf"));
-    LR_CHECK_DEVICE(ws, stream, "lr_gpf");
-    forget_last_batch(ws);
-    LR_REQUIRE(idx1 && idx2 && xyz0 && o0 && o1, LR_EINVAL, "lr_gpf: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    pad_if_narrow(ws, F0, n0, F1, n1, dim, st);
-    LR_TRY(prep_both(ws, F0, n0, F1, n1, st));
-    LR_TRY(nn_reverse(ws, F0, n0, F1, n1, idx1, ws->rev_idx1, st));
-    LR_TRY(lr_mutual_run(ws, n0, idx1, nullptr, ws->rev_idx1, ws->is_bb, nullptr, nullptr, nullptr, nullptr, st));
-    return lr_gpf_run(ws, F0, n0, F1, dim, idx1, idx2, ws->is_bb, xyz0, grid_wid, factor, o0, o1, o2, oscore, n_out, st);
+    lr_call c;
+    LR_TRY(operator_prep(ws, F0, n0, F1, n1, dim, stream, "lr_gpf", idx1 && idx2 && xyz0 && o0 && o1, "lr_gpf: null pointer", &c));
+    LR_TRY(lr_nn16_reverse(c, F0, n0, F1, n1, idx1, ws->rev_idx1));
+    LR_TRY(lr_mutual_run(c, n0, idx1, nullptr, ws->rev_idx1, ws->is_bb, nullptr, nullptr, nullptr, nullptr));
+    return lr_gpf_run(c, F0, n0, F1, dim, idx1, idx2, ws->is_bb, xyz0, grid_wid, factor, o0, o1, o2, oscore, n_out);
 }
 
 // a7, BB_first=True: mutual pairs first, then the grid filter over them with TOTAL_NUM = max_matches
@@ -533,18 +533,14 @@ extern "C" int lr_gpf_bb_first(lr_workspace *ws, const float *F0, int n0, const 
                                int32_t *o0, int32_t *o1, int32_t *o2, float *oscore, int32_t *n_out, int32_t *has_score,
                                void *stream)
 {
-    LR_TRY(check_nn_args(ws, F0, n0, F1, n1, dim, "lr_gpf_bb_first"));
-    LR_CHECK_DEVICE(ws, stream, "lr_gpf_bb_first");
-    forget_last_batch(ws);
-    LR_REQUIRE(idx1 && idx2 && xyz0 && o0 && o1 && o2 && n_out && has_score, LR_EINVAL, "lr_gpf_bb_first: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    pad_if_narrow(ws, F0, n0, F1, n1, dim, st);
+    lr_call c;
+    LR_TRY(operator_prep(ws, F0, n0, F1, n1, dim, stream, "lr_gpf_bb_first", idx1 && idx2 && xyz0 && o0 && o1 && o2 && n_out && has_score,
+                         "lr_gpf_bb_first: null pointer", &c));
     int32_t *mb_dev = ws->counters + LR_CNT_NCORR;
-    LR_TRY(prep_both(ws, F0, n0, F1, n1, st));
-    LR_TRY(nn_reverse(ws, F0, n0, F1, n1, idx1, ws->rev_idx1, st));
-    LR_TRY(lr_mutual_run(ws, n0, idx1, idx2, ws->rev_idx1, ws->is_bb, ws->corr_idx0, ws->corr_idx1, ws->corr_idx2, mb_dev, st));
-    return lr_gpf_bb_run(ws, F0, n0, F1, dim, ws->corr_idx0, ws->corr_idx1, ws->corr_idx2, mb_dev, xyz0, grid_wid, max_matches,
-                         o0, o1, o2, oscore, n_out, has_score, st);
+    LR_TRY(lr_nn16_reverse(c, F0, n0, F1, n1, idx1, ws->rev_idx1));
+    LR_TRY(lr_mutual_run(c, n0, idx1, idx2, ws->rev_idx1, ws->is_bb, ws->corr_idx0, ws->corr_idx1, ws->corr_idx2, mb_dev));
+    const lr_gpf_subset sub = { mb_dev, ws->corr_idx0, has_score, max_matches };
+    return lr_gpf_run(c, F0, n0, F1, dim, ws->corr_idx1, ws->corr_idx2, nullptr, xyz0, grid_wid, 0.0, o0, o1, o2, oscore, n_out, nullptr, nullptr, &sub);
 }
 
 // ------------------------------------------------------------------ a10/a12
@@ -556,9 +552,9 @@ extern "C" int lr_ransac(lr_workspace *ws, const float *src, const float *tgt, i
     LR_CHECK_DEVICE(ws, stream, "lr_ransac");
     forget_last_batch(ws);
     LR_REQUIRE(m >= 0 && m <= ws->max_n0, LR_ESIZE, "lr_ransac: m exceeds the workspace");
-    hipStream_t st = (hipStream_t)stream;
-    LR_TRY(lr_pack_corr(ws, src, tgt, nullptr, nullptr, m, m_dev, ws->corr8, st));
-    return lr_ransac_run(ws, ws->corr8, m, m_dev, p, T_out, res, st);
+    const lr_call c = lr_call_single(ws, stream);
+    LR_TRY(lr_pack_corr(c, src, tgt, nullptr, nullptr, m, m_dev, ws->corr8));
+    return lr_ransac_run(c, ws->corr8, m, m_dev, p, T_out, res);
 }
 
 // the inlier mask pygcransac returns next to the pose (gcransac_python.cpp:594-603)
@@ -595,7 +591,7 @@ extern "C" int lr_refit(lr_workspace *ws, const float *xyz0, int n0, const float
     LR_REQUIRE(n0 > 0 && n0 <= ws->max_n0, LR_ESIZE, "lr_refit: n0 exceeds the workspace");
     LR_CHECK_DEVICE(ws, stream, "lr_refit");
     forget_last_batch(ws);          // (arena-0 counters and the refit scratch are overwritten)
-    return lr_refit_run(ws, xyz0, n0, xyz1, idx1, T_in, thr2, T_out, n_inl, nullptr, (hipStream_t)stream);
+    return lr_refit_run(lr_call_single(ws, stream), xyz0, n0, xyz1, idx1, T_in, thr2, T_out, n_inl, nullptr);
 }
 
 // ------------------------------------------------------------------ f1: ICP
@@ -606,7 +602,7 @@ extern "C" int lr_icp(lr_workspace *ws, const float *xyz0, int n0, const float *
     LR_REQUIRE(n0 > 0 && n0 <= ws->max_n0 && n1 > 0 && n1 <= ws->max_n1, LR_ESIZE, "lr_icp: cloud exceeds the workspace");
     LR_CHECK_DEVICE(ws, stream, "lr_icp");
     forget_last_batch(ws);          // (the ICP scratch and the result temporaries are overwritten)
-    return lr_icp_run(ws, xyz0, n0, xyz1, n1, T_init, nullptr, max_dist, max_iter, rel_fitness, rel_rmse, T_out, res, (hipStream_t)stream);
+    return lr_icp_run(lr_call_single(ws, stream), xyz0, n0, xyz1, n1, T_init, nullptr, max_dist, max_iter, rel_fitness, rel_rmse, T_out, res);
 }
 
 __global__ void pair_icp_kernel(const double *__restrict__ T_icp, const lr_icp_result *__restrict__ r, lr_pair_result *__restrict__ out, int have, lr_zargs z);
@@ -623,16 +619,13 @@ extern "C" int lr_icp_batch(lr_workspace *ws, double max_dist, int max_iter, dou
     hipStream_t st = (hipStream_t)stream;
     // the transforms it starts from are written by the registration call's stream: the ICP must be ordered behind it
     LR_REQUIRE(st == ws->last_stream, LR_EINVAL, "lr_icp_batch: must be enqueued on the stream of the lr_register_batch call it continues");
-    ws->zP = ws->last_npairs; ws->z = lr_zargs{ ws->stride, ws->descs };
+    const lr_call c = lr_call_batch(ws, stream, ws->last_npairs);
     lr_icp_result *icp_res = reinterpret_cast<lr_icp_result *>(ws->icp_state + 24);
-    int rc = lr_icp_run(ws, nullptr, ws->last_mx0, nullptr, ws->last_mx1, ws->last_T_final, ws->res_tmp, max_dist, max_iter, rel_fitness, rel_rmse,
-                        ws->T_tmp + 32, icp_res, st);
-    if (rc == LR_OK) {
-        hipLaunchKernelGGL(pair_icp_kernel, dim3(1, 1, ws->zP), dim3(64), 0, st, ws->T_tmp + 32, icp_res, out, 1, ws->z);
-        if (hipGetLastError() != hipSuccess) { lr_set_error("lr_icp_batch: launch failed"); rc = LR_EHIP; }
-    }
-    ws->zP = 1; ws->z = lr_zargs{ 0, nullptr };
-    return rc;
+    LR_TRY(lr_icp_run(c, nullptr, ws->last_mx0, nullptr, ws->last_mx1, ws->last_T_final, ws->res_tmp, max_dist, max_iter, rel_fitness, rel_rmse,
+                      ws->T_tmp + 32, icp_res));
+    hipLaunchKernelGGL(pair_icp_kernel, dim3(1, 1, c.pairs), dim3(64), 0, st, ws->T_tmp + 32, icp_res, out, 1, c.z);
+    if (hipGetLastError() != hipSuccess) { lr_set_error("lr_icp_batch: launch failed"); return LR_EHIP; }
+    return LR_OK;
 }
 
 __global__ void pair_icp_kernel(const double *__restrict__ T_icp, const lr_icp_result *__restrict__ r, lr_pair_result *__restrict__ out, int have,
@@ -671,73 +664,72 @@ __global__ void pair_result_kernel(const double *__restrict__ T_ransac, const do
     if (k < 16) out->T_icp[k] = T_final[k];      // overwritten by pair_icp_kernel when the ICP stage runs
 }
 
-// The stages of FR() for the call in flight: one pair with its pointers as given (ws->zP == 1, ws->z.descs == nullptr), or
-// ws->zP pairs described by ws->z.descs (n0 / n1 are then the largest cloud sizes of the batch: they size the grids).
-static int register_stages(lr_workspace *ws, const float *xyz0, const float *xyz1, const float *F0, const float *F1,
-                           int n0, int n1, int dim, const lr_pair_params *p, lr_pair_result *out, hipStream_t st)
+// The stages of FR() for the call: one pair with its pointers as given (c.pairs == 1, c.z.descs == nullptr), or c.pairs pairs
+// described by c.z.descs (n0 / n1 are then the largest cloud sizes of the batch: they size the grids).
+static int register_stages(const lr_call &c, const float *xyz0, const float *xyz1, const float *F0, const float *F1,
+                           int n0, int n1, int dim, const lr_pair_params *p, lr_pair_result *out)
 {
+    lr_workspace *ws = c.ws;
     int32_t *m_dev = ws->counters + LR_CNT_NCORR;
     int32_t *n_refit = ws->counters + LR_CNT_COUNT - 2;
-    pad_if_narrow(ws, F0, n0, F1, n1, dim, st);
+    pad_if_narrow(c, F0, n0, F1, n1, dim);
     // 1. coarse correspondences (FR.py:38): first + second NN of every cloud-0 descriptor
-    LR_TRY(prep_both(ws, F0, n0, F1, n1, st, true));
+    LR_TRY(lr_nn16_prep(c, F0, n0, F1, n1, true));         // (the prep kernel clears the counter block itself)
     const bool fuse_seed = p->mode != LR_MODE_NO_FILTER;   // the forward exact kernel seeds the reverse pass
-    const bool timed = ws->timing && !ws->ev_pending;
-    if (timed) LR_HIP(hipEventRecord(ws->ev[6], st));
+    LR_TRY_HIP(lr_timer_mark(c, LR_EV_CALL_BEGIN));
     // The second neighbour (find_2nn, FR.py:38) feeds the feature-distance ratio only: GPF (matching.py:116) and the PROSAC
     // quality (FR.py:77).  By default it is computed as the reference does; with the option LR_OPT_NN_SECOND_AUTO it is left out
     // when no stage of this call reads it (plain mutual-NN / no filter with uniform sampling): the outputs are the same, the
     // candidate lists of the forward pass are half as long (and the reverse pass prunes less: not a gain on its own).
     const bool want2 = !(ws->nn_second_auto && p->mode != LR_MODE_GPF && p->ransac.sampler == 0);
     int32_t *idx2 = want2 ? ws->nn_idx2 : nullptr;
-    LR_TRY(nn_forward(ws, F0, n0, F1, n1, ws->nn_idx1, idx2, ws->nn_s1, ws->nn_s2, st, fuse_seed));
-    if (timed) LR_HIP(hipEventRecord(ws->ev[7], st));
+    LR_TRY(lr_nn16_run(c, F0, n0, F1, n1, ws->nn_idx1, idx2, ws->nn_s1, ws->nn_s2, fuse_seed));
+    LR_TRY_HIP(lr_timer_mark(c, LR_EV_FWD_NN_DONE));
     // 2. filter (FR.py:48-56)
     if (p->mode == LR_MODE_NO_FILTER) {
-        LR_TRY(lr_identity_corr(ws, n0, ws->nn_idx1, idx2, ws->corr_idx0, ws->corr_idx1, idx2 ? ws->corr_idx2 : nullptr, m_dev, st));
+        LR_TRY(lr_identity_corr(c, n0, ws->nn_idx1, idx2, ws->corr_idx0, ws->corr_idx1, idx2 ? ws->corr_idx2 : nullptr, m_dev));
     } else {
-        LR_TRY(nn_reverse(ws, F0, n0, F1, n1, ws->nn_idx1, ws->rev_idx1, st, fuse_seed));
-        if (timed) { LR_HIP(hipEventRecord(ws->ev[9], st)); ws->rev_done_recorded = 1; }
+        // seeded by the forward pairs: only columns some query points at are resolved (others get -1)
+        LR_TRY(lr_nn16_reverse(c, F0, n0, F1, n1, ws->nn_idx1, ws->rev_idx1, fuse_seed));
+        LR_TRY_HIP(lr_timer_mark(c, LR_EV_REV_NN_DONE));
         if (p->mode == LR_MODE_MNN) {
-            LR_TRY(lr_mutual_run(ws, n0, ws->nn_idx1, idx2, ws->rev_idx1, ws->is_bb, ws->corr_idx0, ws->corr_idx1,
-                                 idx2 ? ws->corr_idx2 : nullptr, m_dev, st, xyz0, xyz1, ws->corr8));
+            LR_TRY(lr_mutual_run(c, n0, ws->nn_idx1, idx2, ws->rev_idx1, ws->is_bb, ws->corr_idx0, ws->corr_idx1,
+                                 idx2 ? ws->corr_idx2 : nullptr, m_dev, xyz0, xyz1, ws->corr8));
         } else {
-            LR_TRY(lr_mutual_run(ws, n0, ws->nn_idx1, nullptr, ws->rev_idx1, ws->is_bb, nullptr, nullptr, nullptr, nullptr, st));
-            LR_TRY(lr_gpf_run(ws, F0, n0, F1, dim, ws->nn_idx1, ws->nn_idx2, ws->is_bb, xyz0, p->gpf_grid_wid, p->gpf_factor,
-                              ws->corr_idx0, ws->corr_idx1, ws->corr_idx2, ws->corr_score, m_dev, st, xyz1, ws->corr8));
+            LR_TRY(lr_mutual_run(c, n0, ws->nn_idx1, nullptr, ws->rev_idx1, ws->is_bb, nullptr, nullptr, nullptr, nullptr));
+            LR_TRY(lr_gpf_run(c, F0, n0, F1, dim, ws->nn_idx1, ws->nn_idx2, ws->is_bb, xyz0, p->gpf_grid_wid, p->gpf_factor,
+                              ws->corr_idx0, ws->corr_idx1, ws->corr_idx2, ws->corr_score, m_dev, xyz1, ws->corr8));
         }
     }
     // 3. RANSAC on the surviving pairs (FR.py:70-97); MNN / GPF pack the point pairs inside their compaction kernel
     if (p->ransac.sampler == 1) {
         // PROSAC (FR.py:73-80, GC_RANSAC.py:39-43): records re-packed best match quality first; quality = -feature-distance
         // ratio of the pair, or GPF's normalised feature distance
-        LR_TRY(lr_prosac_order(ws, F0, F1, dim, p->mode == LR_MODE_GPF ? ws->corr_score : nullptr, n0, m_dev, st));
-        LR_TRY(lr_pack_corr(ws, xyz0, xyz1, ws->corr_idx0, ws->corr_idx1, n0, m_dev, ws->corr8, st, ws->prosac_rank));
-    } else if (p->mode == LR_MODE_NO_FILTER) LR_TRY(lr_pack_corr(ws, xyz0, xyz1, ws->corr_idx0, ws->corr_idx1, n0, m_dev, ws->corr8, st));
-    LR_TRY(lr_ransac_run(ws, ws->corr8, n0, m_dev, &p->ransac, ws->T_tmp, ws->res_tmp, st));
-    // 4. LS refit over the original NN pairs (FR.py:99-111)
+        LR_TRY(lr_prosac_order(c, F0, F1, dim, p->mode == LR_MODE_GPF ? ws->corr_score : nullptr, n0, m_dev));
+        LR_TRY(lr_pack_corr(c, xyz0, xyz1, ws->corr_idx0, ws->corr_idx1, n0, m_dev, ws->corr8, ws->prosac_rank));
+    } else if (p->mode == LR_MODE_NO_FILTER) LR_TRY(lr_pack_corr(c, xyz0, xyz1, ws->corr_idx0, ws->corr_idx1, n0, m_dev, ws->corr8));
+    LR_TRY(lr_ransac_run(c, ws->corr8, n0, m_dev, &p->ransac, ws->T_tmp, ws->res_tmp));
+    // 4. LS refit (FR.py:99-111); its kernel writes the result block
     const double *T_final = ws->T_tmp;
     if (p->refit) {
-        if (p->refit == 2)      // GC codebase: final least squares over the inliers among the FILTERED pairs RANSAC worked on
-            LR_TRY(lr_refit_run(ws, xyz0, n0, xyz1, ws->corr_idx1, ws->T_tmp, p->refit_thr2, ws->T_tmp + 16, n_refit, ws->res_tmp, st, out,
-                                ws->corr_idx0, m_dev));
-        else if (p->refit == 3) // DGR register_FCGF: inverse-feature-distance weighted Procrustes over the original NN pairs
-            LR_TRY(lr_refit_run(ws, xyz0, n0, xyz1, ws->nn_idx1, ws->T_tmp, p->refit_thr2, ws->T_tmp + 16, n_refit, ws->res_tmp, st, out,
-                                nullptr, nullptr, F0, F1));
-        else                    // open3D codebase: inliers over the ORIGINAL NN pairs (FR.py:99-111)
-            LR_TRY(lr_refit_run(ws, xyz0, n0, xyz1, ws->nn_idx1, ws->T_tmp, p->refit_thr2,
-                                ws->T_tmp + 16, n_refit, ws->res_tmp, st, out));
+        // 1, open3D codebase: inliers over the ORIGINAL NN pairs (FR.py:99-111); 2, GC codebase: final least squares over the inliers among
+        // the FILTERED pairs RANSAC worked on; 3, DGR register_FCGF: inverse-feature-distance weighted Procrustes over the original NN pairs
+        const bool filtered = p->refit == 2, weighted = p->refit == 3;
+        LR_TRY(lr_refit_run(c, xyz0, n0, xyz1, filtered ? ws->corr_idx1 : ws->nn_idx1, ws->T_tmp, p->refit_thr2, ws->T_tmp + 16, n_refit, ws->res_tmp, out,
+                            filtered ? ws->corr_idx0 : nullptr, filtered ? m_dev : nullptr, weighted ? F0 : nullptr, weighted ? F1 : nullptr));
         T_final = ws->T_tmp + 16;
-    } else
-    hipLaunchKernelGGL(pair_result_kernel, dim3(1, 1, ws->zP), dim3(64), 0, st, ws->T_tmp, T_final, ws->res_tmp, ws->counters,
-                       p->refit ? n_refit : (const int32_t *)nullptr, out, ws->z);
+    }
+    if (!p->refit)
+        hipLaunchKernelGGL(pair_result_kernel, dim3(1, 1, c.pairs), dim3(64), 0, c.st, ws->T_tmp, T_final, ws->res_tmp, ws->counters,
+                           (const int32_t *)nullptr, out, c.z);
     ws->last_T_final = T_final; ws->last_mx0 = n0; ws->last_mx1 = n1;
     // 5. ICP refinement (test.py:183-189): max distance 2*voxel, Open3D's default criteria
-    lr_icp_result *icp_res = reinterpret_cast<lr_icp_result *>(ws->icp_state + 24);
-    if (p->icp)
-        LR_TRY(lr_icp_run(ws, xyz0, n0, xyz1, n1, T_final, ws->res_tmp, 0.6, 30, 1e-6, 1e-6, ws->T_tmp + 32, icp_res, st));
-    if (p->icp) hipLaunchKernelGGL(pair_icp_kernel, dim3(1, 1, ws->zP), dim3(64), 0, st, ws->T_tmp + 32, icp_res, out, 1, ws->z);
-    if (timed && ws->ev_pending == 2) { LR_HIP(hipEventRecord(ws->ev[8], st)); ws->ev_pending = 3; }
+    if (p->icp) {
+        lr_icp_result *icp_res = reinterpret_cast<lr_icp_result *>(ws->icp_state + 24);
+        LR_TRY(lr_icp_run(c, xyz0, n0, xyz1, n1, T_final, ws->res_tmp, 0.6, 30, 1e-6, 1e-6, ws->T_tmp + 32, icp_res));
+        hipLaunchKernelGGL(pair_icp_kernel, dim3(1, 1, c.pairs), dim3(64), 0, c.st, ws->T_tmp + 32, icp_res, out, 1, c.z);
+    }
+    LR_TRY_HIP(lr_timer_mark(c, LR_EV_CALL_END));
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
@@ -751,9 +743,8 @@ extern "C" int lr_register_pair(lr_workspace *ws, const float *xyz0, const float
     LR_CHECK_DEVICE(ws, stream, "lr_register_pair");
     LR_REQUIRE(p->mode == LR_MODE_NO_FILTER || p->mode == LR_MODE_MNN || p->mode == LR_MODE_GPF, LR_EINVAL,
                "lr_register_pair: unknown mode");
-    ws->zP = 1; ws->z = lr_zargs{ 0, nullptr };
     ws->last_npairs = 1; ws->last_batch = 0;
-    return register_stages(ws, xyz0, xyz1, F0, F1, n0, n1, dim, p, out, (hipStream_t)stream);
+    return register_stages(lr_call_single(ws, stream), xyz0, xyz1, F0, F1, n0, n1, dim, p, out);
 }
 
 // descriptor table -> device memory (it travels as a kernel argument: no host staging buffer, no copy engine)
@@ -784,10 +775,8 @@ extern "C" int lr_register_batch(lr_workspace *ws, int npairs, const float *cons
     for (int k = npairs; k < LR_MAX_BATCH; ++k) t.d[k] = lr_pair_desc{ nullptr, nullptr, nullptr, nullptr, 0, 0 };
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(batch_setup_kernel, dim3(1), dim3(64), 0, st, t, ws->descs, npairs);
-    ws->zP = npairs; ws->z = lr_zargs{ ws->stride, ws->descs };
     ws->last_npairs = npairs; forget_last_batch(ws);
-    const int rc = register_stages(ws, xyz0[0], xyz1[0], F0[0], F1[0], mx0, mx1, dim, p, out, st);
-    ws->zP = 1; ws->z = lr_zargs{ 0, nullptr };
+    const int rc = register_stages(lr_call_batch(ws, stream, npairs), xyz0[0], xyz1[0], F0[0], F1[0], mx0, mx1, dim, p, out);
     if (rc == LR_OK) { ws->last_batch = 1; ws->last_stream = st; } else ws->last_T_final = nullptr;      // (lr_icp_batch: only after a call that went through)
     return rc;
 }

@@ -99,16 +99,17 @@ compact_kernel(int n0, const uint8_t *__restrict__ flags, const int32_t *__restr
     }
 }
 
-int lr_mutual_run(lr_workspace *ws, int n0, const int32_t *idx1, const int32_t *idx2, const int32_t *rev,
-                  uint8_t *is_bb, int32_t *o0, int32_t *o1, int32_t *o2, int32_t *n_out, hipStream_t st,
+int lr_mutual_run(const lr_call &c, int n0, const int32_t *idx1, const int32_t *idx2, const int32_t *rev,
+                  uint8_t *is_bb, int32_t *o0, int32_t *o1, int32_t *o2, int32_t *n_out,
                   const float *xyz0, const float *xyz1, float *corr8)
 {
+    lr_workspace *ws = c.ws; hipStream_t st = c.st;
     const int nb = lr_cdiv(n0, 256);
     uint8_t *flags = is_bb ? is_bb : ws->is_bb;
-    hipLaunchKernelGGL(mutual_flag_kernel, dim3(nb, 1, ws->zP), dim3(256), 0, st, n0, idx1, rev, flags, ws->blk_cnt, ws->z);
+    hipLaunchKernelGGL(mutual_flag_kernel, dim3(nb, 1, c.pairs), dim3(256), 0, st, n0, idx1, rev, flags, ws->blk_cnt, c.z);
     // the number of best buddies is wanted even when no list is (GPF's TOTAL_NUM, matching.py:115-116)
-    hipLaunchKernelGGL(compact_kernel, dim3(nb, 1, ws->zP), dim3(256), 0, st, n0, flags, ws->blk_cnt, idx1, idx2, (const float *)nullptr,
-                       o0, o1, o2, (float *)nullptr, n_out, ws->counters + LR_CNT_NBB, xyz0, xyz1, corr8, ws->counters, ws->z);
+    hipLaunchKernelGGL(compact_kernel, dim3(nb, 1, c.pairs), dim3(256), 0, st, n0, flags, ws->blk_cnt, idx1, idx2, (const float *)nullptr,
+                       o0, o1, o2, (float *)nullptr, n_out, ws->counters + LR_CNT_NBB, xyz0, xyz1, corr8, ws->counters, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
@@ -127,10 +128,10 @@ __global__ void identity_corr_kernel(int n0, const int32_t *__restrict__ idx1, c
     if (i == 0 && n_out) *n_out = n0;
 }
 
-int lr_identity_corr(lr_workspace *ws, int n0, const int32_t *idx1, const int32_t *idx2,
-                     int32_t *o0, int32_t *o1, int32_t *o2, int32_t *n_out, hipStream_t st)
+int lr_identity_corr(const lr_call &c, int n0, const int32_t *idx1, const int32_t *idx2,
+                     int32_t *o0, int32_t *o1, int32_t *o2, int32_t *n_out)
 {
-    hipLaunchKernelGGL(identity_corr_kernel, dim3(lr_cdiv(n0, 256), 1, ws->zP), dim3(256), 0, st, n0, idx1, idx2, o0, o1, o2, n_out, ws->z);
+    hipLaunchKernelGGL(identity_corr_kernel, dim3(lr_cdiv(n0, 256), 1, c.pairs), dim3(256), 0, c.st, n0, idx1, idx2, o0, o1, o2, n_out, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
@@ -159,11 +160,11 @@ __global__ void pack_corr_kernel(const float *__restrict__ xyz0, const float *__
     }
 }
 
-int lr_pack_corr(lr_workspace *ws, const float *xyz0, const float *xyz1, const int32_t *i0, const int32_t *i1, int m_max,
-                 const int32_t *m_dev, float *corr8, hipStream_t st, const int32_t *rank)
+int lr_pack_corr(const lr_call &c, const float *xyz0, const float *xyz1, const int32_t *i0, const int32_t *i1, int m_max,
+                 const int32_t *m_dev, float *corr8, const int32_t *rank)
 {
-    hipLaunchKernelGGL(pack_corr_kernel, dim3(lr_cdiv(m_max > 0 ? m_max : 1, 256), 1, ws->zP), dim3(256), 0, st, xyz0, xyz1, i0, i1, m_max, m_dev, corr8,
-                       ws->counters, rank, ws->z);
+    hipLaunchKernelGGL(pack_corr_kernel, dim3(lr_cdiv(m_max > 0 ? m_max : 1, 256), 1, c.pairs), dim3(256), 0, c.st, xyz0, xyz1, i0, i1, m_max, m_dev, corr8,
+                       c.ws->counters, rank, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
@@ -299,28 +300,28 @@ __global__ void ratio_kernel(const float *__restrict__ F0, const float *__restri
 
 // quality = feature-distance ratio of the listed pairs (FR.py:77) unless the caller has one already (GPF's
 // norm_feat_dist, FR.py:75); then the ranks
-int lr_prosac_order(lr_workspace *ws, const float *F0, const float *F1, int dim, const float *quality, int m_max, const int32_t *m_dev,
-                    hipStream_t st)
+int lr_prosac_order(const lr_call &c, const float *F0, const float *F1, int dim, const float *quality, int m_max, const int32_t *m_dev)
 {
+    lr_workspace *ws = c.ws; hipStream_t st = c.st;
     const int nb = lr_cdiv(m_max > 0 ? m_max : 1, 256);
     if (!quality) {
-        hipLaunchKernelGGL(ratio_kernel, dim3(nb, 1, ws->zP), dim3(256), 0, st, F0, F1, dim, m_max, m_dev, (const int32_t *)ws->corr_idx0,
-                           (const int32_t *)ws->corr_idx1, (const int32_t *)ws->corr_idx2, ws->ratio, (uint32_t *)nullptr, (const float *)nullptr, ws->z);
+        hipLaunchKernelGGL(ratio_kernel, dim3(nb, 1, c.pairs), dim3(256), 0, st, F0, F1, dim, m_max, m_dev, (const int32_t *)ws->corr_idx0,
+                           (const int32_t *)ws->corr_idx1, (const int32_t *)ws->corr_idx2, ws->ratio, (uint32_t *)nullptr, (const float *)nullptr, c.z);
         quality = ws->ratio;
     }
     // GPF's scratch is free by now: offsets | fill | range in its cell arrays, bucket members in its sort buffer
     int32_t *offs = ws->gpf_cells, *fill = offs + LR_PR_BUCKETS + 8;
     float *range = reinterpret_cast<float *>(fill + LR_PR_BUCKETS + 8);
     float *mkeys = reinterpret_cast<float *>(ws->cell);       // (GPF's cell ids: free by now, like the rest of its scratch)
-    const bool fused = ws->zP > 4;      // (full batches: the scatter inside the one-block-per-pair scan, hidden behind the other calls' filter passes)
+    const bool fused = c.pairs > 4;      // (full batches: the scatter inside the one-block-per-pair scan, hidden behind the other calls' filter passes)
     if (fused)
-        hipLaunchKernelGGL(prosac_scan_kernel<true>, dim3(1, 1, ws->zP), dim3(1024), 0, st, quality, m_max, m_dev, offs, fill, ws->cell_sorted, mkeys, range, ws->z);
+        hipLaunchKernelGGL(prosac_scan_kernel<true>, dim3(1, 1, c.pairs), dim3(1024), 0, st, quality, m_max, m_dev, offs, fill, ws->cell_sorted, mkeys, range, c.z);
     else {
-        hipLaunchKernelGGL(prosac_scan_kernel<false>, dim3(1, 1, ws->zP), dim3(1024), 0, st, quality, m_max, m_dev, offs, fill, ws->cell_sorted, mkeys, range, ws->z);
-        hipLaunchKernelGGL(prosac_scatter_kernel, dim3(nb, 1, ws->zP), dim3(256), 0, st, quality, m_max, m_dev, (const float *)range, fill, ws->cell_sorted, mkeys, ws->z);
+        hipLaunchKernelGGL(prosac_scan_kernel<false>, dim3(1, 1, c.pairs), dim3(1024), 0, st, quality, m_max, m_dev, offs, fill, ws->cell_sorted, mkeys, range, c.z);
+        hipLaunchKernelGGL(prosac_scatter_kernel, dim3(nb, 1, c.pairs), dim3(256), 0, st, quality, m_max, m_dev, (const float *)range, fill, ws->cell_sorted, mkeys, c.z);
     }
-    hipLaunchKernelGGL(prosac_rank_kernel, dim3(nb, 1, ws->zP), dim3(256), 0, st, m_max, m_dev, (const float *)range, (const int32_t *)offs,
-                       (const int32_t *)ws->cell_sorted, (const float *)mkeys, ws->prosac_rank, ws->z);
+    hipLaunchKernelGGL(prosac_rank_kernel, dim3(nb, 1, c.pairs), dim3(256), 0, st, m_max, m_dev, (const float *)range, (const int32_t *)offs,
+                       (const int32_t *)ws->cell_sorted, (const float *)mkeys, ws->prosac_rank, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
@@ -693,68 +694,39 @@ gpf_select_kernel(int n0, const int32_t *__restrict__ cell, const int32_t *__res
     keep[i] = k ? 1 : 0;
 }
 
-int lr_gpf_run(lr_workspace *ws, const float *F0, int n0, const float *F1, int dim,
+// Grid_Prioritized_Filter (matching.py:100-205) over all n0 NN pairs (i, idx1[i], idx2[i]), or, with `sub`, its BB_first=True form
+// (matching.py:109-113,126) over the mutual pairs (sub->b0[k], idx1[k], idx2[k]) of live length *sub->mb_dev: TOTAL_NUM = GPF_max_matches,
+// no best-buddy shift, no packed records.  The reference's TEASER wrapper uses that form only (TEASER_plus_plus.py:109-110).
+int lr_gpf_run(const lr_call &c, const float *F0, int n0, const float *F1, int dim,
                const int32_t *idx1, const int32_t *idx2, const uint8_t *is_bb, const float *xyz0,
                int G, double factor, int32_t *o0, int32_t *o1, int32_t *o2, float *oscore,
-               int32_t *n_out, hipStream_t st, const float *xyz1, float *corr8)
+               int32_t *n_out, const float *xyz1, float *corr8, const lr_gpf_subset *sub)
 {
     LR_REQUIRE(G >= 1 && G <= 64, LR_EINVAL, "lr_gpf: grid width must be in [1,64]");
+    lr_workspace *ws = c.ws; hipStream_t st = c.st;
     int32_t *cell_count = ws->gpf_cells;
     int32_t *cell_fill = cell_count + LR_GPF_MAX_CELLS + 8;
     int32_t *cell_off = cell_fill + LR_GPF_MAX_CELLS + 8;
     double *quota = ws->gpf_quota;
     uint8_t *keep = ws->gpf_keep;
     const int nb = lr_cdiv(n0, 256);
-    // one memset clears the cell counters and the six min/max slots behind them (atomicMax on encoded values, 0 = identity)
+    const int32_t *mb_dev = sub ? sub->mb_dev : nullptr, *b0 = sub ? sub->b0 : nullptr;
+    // one launch clears the cell counters and the six min/max slots behind them (atomicMax on encoded values, 0 = identity)
     uint32_t *mm = reinterpret_cast<uint32_t *>(cell_fill + LR_GPF_MAX_CELLS);
-    LR_TRY_HIP(lr_zero_scratch(ws, cell_count, sizeof(int32_t) * 2 * (LR_GPF_MAX_CELLS + 8), st));
-    const dim3 gN(nb, 1, ws->zP), g1(1, 1, ws->zP);
-    // ratio over all n0 NN pairs (corres_idx0 == arange), and the extrema of ratio / x / y
-    hipLaunchKernelGGL(ratio_kernel, gN, dim3(256), 0, st, F0, F1, dim, n0, (const int32_t *)nullptr,
-                       (const int32_t *)nullptr, idx1, idx2, ws->ratio, mm, xyz0, ws->z);
+    LR_TRY_HIP(lr_zero_scratch(c, cell_count, sizeof(int32_t) * 2 * (LR_GPF_MAX_CELLS + 8)));
+    const dim3 gN(nb, 1, c.pairs), g1(1, 1, c.pairs);
+    // ratio over the pairs (all of them: corres_idx0 == arange), and the extrema of ratio / x / y
+    hipLaunchKernelGGL(ratio_kernel, gN, dim3(256), 0, st, F0, F1, dim, n0, mb_dev, b0, idx1, idx2, ws->ratio, mm, xyz0, c.z);
     hipLaunchKernelGGL(gpf_score_cell_kernel, gN, dim3(256), 0, st, n0, G, (const uint32_t *)mm, is_bb, xyz0, ws->ratio,
-                       ws->cell, cell_count, ws->z);
-    hipLaunchKernelGGL(gpf_waterfill_kernel, g1, dim3(64), 0, st, G, factor, ws->counters, cell_count, quota, cell_off, ws->z);
-    hipLaunchKernelGGL(gpf_bucket_kernel, gN, dim3(256), 0, st, n0, G, ws->cell, cell_off, cell_fill, ws->cell_sorted, ws->z);
+                       ws->cell, cell_count, c.z, mb_dev, b0);
+    hipLaunchKernelGGL(gpf_waterfill_kernel, g1, dim3(64), 0, st, G, factor, ws->counters, cell_count, quota, cell_off, c.z,
+                       sub ? sub->max_matches : -1.0, mb_dev, sub ? sub->has_score : (int32_t *)nullptr);
+    hipLaunchKernelGGL(gpf_bucket_kernel, gN, dim3(256), 0, st, n0, G, ws->cell, cell_off, cell_fill, ws->cell_sorted, c.z, mb_dev);
     hipLaunchKernelGGL(gpf_select_kernel, gN, dim3(256), 0, st, n0, ws->cell, cell_off, cell_count, quota,
-                       ws->cell_sorted, ws->ratio, keep, G * G, ws->z);
-    hipLaunchKernelGGL(count_flags_kernel, gN, dim3(256), 0, st, n0, (const int32_t *)nullptr, keep, ws->blk_cnt, ws->z);
+                       ws->cell_sorted, ws->ratio, keep, G * G, c.z, mb_dev);
+    hipLaunchKernelGGL(count_flags_kernel, gN, dim3(256), 0, st, n0, mb_dev, keep, ws->blk_cnt, c.z);
     hipLaunchKernelGGL(compact_kernel, gN, dim3(256), 0, st, n0, keep, ws->blk_cnt, idx1, idx2, ws->ratio, o0, o1, o2, oscore,
-                       n_out, (int32_t *)nullptr, xyz0, xyz1, corr8, ws->counters, ws->z);
-    LR_LAUNCH_CHECK();
-    return LR_OK;
-}
-
-// Grid_Prioritized_Filter(BB_first=True) (matching.py:100-205 with :109-113,126): the filter runs over the MUTUAL pairs
-// (b0,b1,b2 of live length *mb_dev), TOTAL_NUM = GPF_max_matches, no best-buddy shift.  Used by the reference's TEASER
-// wrapper only (TEASER_plus_plus.py:109-110).
-int lr_gpf_bb_run(lr_workspace *ws, const float *F0, int n0, const float *F1, int dim,
-                  const int32_t *b0, const int32_t *b1, const int32_t *b2, const int32_t *mb_dev, const float *xyz0,
-                  int G, double max_matches, int32_t *o0, int32_t *o1, int32_t *o2, float *oscore,
-                  int32_t *n_out, int32_t *has_score, hipStream_t st)
-{
-    LR_REQUIRE(G >= 1 && G <= 64, LR_EINVAL, "lr_gpf: grid width must be in [1,64]");
-    int32_t *cell_count = ws->gpf_cells;
-    int32_t *cell_fill = cell_count + LR_GPF_MAX_CELLS + 8;
-    int32_t *cell_off = cell_fill + LR_GPF_MAX_CELLS + 8;
-    double *quota = ws->gpf_quota;
-    uint8_t *keep = ws->gpf_keep;
-    const int nb = lr_cdiv(n0, 256);
-    uint32_t *mm = reinterpret_cast<uint32_t *>(cell_fill + LR_GPF_MAX_CELLS);
-    // (single-pair operator only: the reference's TEASER wrapper is not on the batched path)
-    const lr_zargs z1 = { 0, nullptr };
-    LR_HIP(hipMemsetAsync(cell_count, 0, sizeof(int32_t) * 2 * (LR_GPF_MAX_CELLS + 8), st));
-    hipLaunchKernelGGL(ratio_kernel, dim3(nb), dim3(256), 0, st, F0, F1, dim, n0, mb_dev, b0, b1, b2, ws->ratio, mm, xyz0, z1);
-    hipLaunchKernelGGL(gpf_score_cell_kernel, dim3(nb), dim3(256), 0, st, n0, G, (const uint32_t *)mm, (const uint8_t *)nullptr, xyz0, ws->ratio,
-                       ws->cell, cell_count, z1, mb_dev, b0);
-    hipLaunchKernelGGL(gpf_waterfill_kernel, dim3(1), dim3(64), 0, st, G, 0.0, ws->counters, cell_count, quota, cell_off, z1, max_matches,
-                       mb_dev, has_score);
-    hipLaunchKernelGGL(gpf_bucket_kernel, dim3(nb), dim3(256), 0, st, n0, G, ws->cell, cell_off, cell_fill, ws->cell_sorted, z1, mb_dev);
-    hipLaunchKernelGGL(gpf_select_kernel, dim3(nb), dim3(256), 0, st, n0, ws->cell, cell_off, cell_count, quota,
-                       ws->cell_sorted, ws->ratio, keep, G * G, z1, mb_dev);
-    hipLaunchKernelGGL(count_flags_kernel, dim3(nb), dim3(256), 0, st, n0, mb_dev, keep, ws->blk_cnt, z1);
-    hipLaunchKernelGGL(compact_kernel, dim3(nb), dim3(256), 0, st, n0, keep, ws->blk_cnt, b1, b2, ws->ratio, o0, o1, o2, oscore,
-                       n_out, (int32_t *)nullptr, (const float *)nullptr, (const float *)nullptr, (float *)nullptr, ws->counters, z1, mb_dev, b0);
+                       n_out, (int32_t *)nullptr, sub ? (const float *)nullptr : xyz0, xyz1, corr8, ws->counters, c.z, mb_dev, b0);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }

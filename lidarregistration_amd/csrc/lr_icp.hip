@@ -227,24 +227,24 @@ __global__ void icp_result_kernel(const double *__restrict__ state, double *__re
     }
 }
 
-int lr_icp_run(lr_workspace *ws, const float *xyz0, int n0, const float *xyz1, int n1, const double *T_init,
+int lr_icp_run(const lr_call &c, const float *xyz0, int n0, const float *xyz1, int n1, const double *T_init,
                const lr_ransac_result *gate, double max_dist, int max_iter, double rel_fit, double rel_rmse,
-               double *T_out, lr_icp_result *res, hipStream_t st)
+               double *T_out, lr_icp_result *res)
 {
+    lr_workspace *ws = c.ws; hipStream_t st = c.st;
     LR_REQUIRE(max_dist > 0.0 && max_iter >= 0 && max_iter <= 1000, LR_EINVAL, "lr_icp: bad max_dist / max_iter");
     const double inv_cell = 1.0 / max_dist;
     int32_t *hist = ws->icp_ints, *fill = hist + LR_ICP_NB + 8, *start = fill + LR_ICP_NB + 8;
-    LR_TRY_HIP(lr_zero_scratch(ws, hist, sizeof(int32_t) * 2 * (LR_ICP_NB + 8), st));
-    const int P = ws->zP;
-    hipLaunchKernelGGL(icp_hist_kernel, dim3(lr_cdiv(n1, 256), 1, P), dim3(256), 0, st, xyz1, n1, inv_cell, ws->icp_bucket, hist, ws->z);
-    hipLaunchKernelGGL(icp_scan_kernel, dim3(1, 1, P), dim3(1024), 0, st, hist, start, ws->z);
-    hipLaunchKernelGGL(icp_scatter_kernel, dim3(lr_cdiv(n1, 256), 1, P), dim3(256), 0, st, n1, ws->icp_bucket, start, fill, xyz1, reinterpret_cast<float4 *>(ws->icp_pts), ws->z);
-    hipLaunchKernelGGL(icp_init_kernel, dim3(1, 1, P), dim3(64), 0, st, T_init, gate, ws->icp_state, ws->z);
+    LR_TRY_HIP(lr_zero_scratch(c, hist, sizeof(int32_t) * 2 * (LR_ICP_NB + 8)));
+    hipLaunchKernelGGL(icp_hist_kernel, dim3(lr_cdiv(n1, 256), 1, c.pairs), dim3(256), 0, st, xyz1, n1, inv_cell, ws->icp_bucket, hist, c.z);
+    hipLaunchKernelGGL(icp_scan_kernel, dim3(1, 1, c.pairs), dim3(1024), 0, st, hist, start, c.z);
+    hipLaunchKernelGGL(icp_scatter_kernel, dim3(lr_cdiv(n1, 256), 1, c.pairs), dim3(256), 0, st, n1, ws->icp_bucket, start, fill, xyz1, reinterpret_cast<float4 *>(ws->icp_pts), c.z);
+    hipLaunchKernelGGL(icp_init_kernel, dim3(1, 1, c.pairs), dim3(64), 0, st, T_init, gate, ws->icp_state, c.z);
     const int nb = lr_cdiv(n0, 256);
     for (int k = 0; k <= max_iter; ++k)
-        hipLaunchKernelGGL(icp_iter_kernel, dim3(nb, 1, P), dim3(256), 0, st, xyz0, n0, xyz1, start, reinterpret_cast<const float4 *>(ws->icp_pts), inv_cell,
-                           max_dist * max_dist, max_iter, rel_fit, rel_rmse, ws->icp_state, ws->icp_part, ws->z);
-    hipLaunchKernelGGL(icp_result_kernel, dim3(1, 1, P), dim3(64), 0, st, ws->icp_state, T_out, res, ws->z);
+        hipLaunchKernelGGL(icp_iter_kernel, dim3(nb, 1, c.pairs), dim3(256), 0, st, xyz0, n0, xyz1, start, reinterpret_cast<const float4 *>(ws->icp_pts), inv_cell,
+                           max_dist * max_dist, max_iter, rel_fit, rel_rmse, ws->icp_state, ws->icp_part, c.z);
+    hipLaunchKernelGGL(icp_result_kernel, dim3(1, 1, c.pairs), dim3(64), 0, st, ws->icp_state, T_out, res, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }

@@ -48,13 +48,13 @@ __host__ __device__ static inline int lr_seg_cap(int strips) { const int c = (LR
 #define LR_PR_BUCKETS 8192        // PROSAC ordering: linear buckets over the quality range (lr_filter.hip); its offsets / fill / range reuse gpf_cells
 #define LR_SC_INFO_BYTES 2048
 #define LR_LO_CTL_BYTES 20480      // lr_lo_ctl: control block of the local optimisation's helper blocks
-#define LR_NEV 10
 
 // ---- pair-batched launches -------------------------------------------------------------------------------------------
 // A workspace holds `max_pairs` arenas of identical layout, `stride` bytes apart; every scratch pointer below refers to
 // arena 0.  A batched call launches each kernel ONCE for all pairs: the pair is the grid's z index (or decoded from a
 // 1-D XCD-aware grid), scratch pointers are moved by pair * stride, and the pair's inputs / sizes come from a descriptor
-// table in device memory.  The single-pair operators pass z = { 0, nullptr }: pointers and sizes are used as given.
+// table in device memory.  A single-pair call passes z = { 0, nullptr }: pointers and sizes are used as given.  How many pairs a
+// call is for, and its z, travel from the entry point to every launcher in an lr_call (below the workspace).
 struct lr_pair_desc {
     const float *xyz0, *xyz1, *F0, *F1;
     int32_t n0, n1;
@@ -85,6 +85,29 @@ __device__ __forceinline__ bool lr_xcd_block(int total, int &logical)
 }
 #endif
 
+// ---- stage timer -----------------------------------------------------------------------------------------------------
+// One sample at a time: the events of a timed call stay recorded until lr_workspace_timing_read / _stage_times folds them into the
+// sums (lr_timer_collect); a call that comes in meanwhile begins no sample of its own.  A sample has begun, and will be counted, once its forward filter pass
+// is recorded.  lr_timer_mark (lr_api.hip) holds the rule of every event.
+enum lr_event {
+    LR_EV_FWD_FILTER_BEGIN, LR_EV_FWD_FILTER_END,      // the forward filter-pass launches
+    LR_EV_RANSAC_BEGIN, LR_EV_RANSAC_END,              // hypothesis generation + scoring of the first RANSAC batch
+    LR_EV_REV_FILTER_BEGIN, LR_EV_REV_FILTER_END,      // the reverse filter-pass launches
+    LR_EV_CALL_BEGIN,                                  // the stages of a pair-pipeline call, after its prep kernels
+    LR_EV_FWD_NN_DONE, LR_EV_CALL_END, LR_EV_REV_NN_DONE,
+    LR_NEV
+};
+struct lr_stage_timer {
+    int on;
+    unsigned recorded;           // bit e: ev[e] was recorded for the sample in flight
+    int n_samples;
+    hipEvent_t ev[LR_NEV];
+    struct { float call, fwd, fwd_filter, rev_filter, ransac, rev, nn; } ms;      // sums over the samples (nn = fwd_filter + rev_filter)
+    bool has(lr_event e) const { return (recorded >> e & 1u) != 0; }
+    bool begun() const { return has(LR_EV_FWD_FILTER_END); }
+    bool armed() const { return on && !begun(); }      // a call that comes in now may begin a sample
+};
+
 struct lr_workspace {
     int max_n0, max_n1, max_n, dim, max_iters;
     int max_pairs;               // arenas in this workspace
@@ -98,9 +121,6 @@ struct lr_workspace {
     size_t bytes;
     char *base;                  // one hipMalloc
     lr_pair_desc *descs;         // [LR_MAX_BATCH] descriptor table of the batched call in flight (arena 0 only)
-    // call context of the entry point in flight (one stream at a time per workspace): grid z extent and the kernels' z argument
-    int zP;
-    lr_zargs z;
     // --- NN (both directions share these) ---
     float *nrm0, *nrm1;          // row norms
     _Float16 *H0, *H1;           // [n,32] f16 copies for the matrix-core filter passes
@@ -175,15 +195,22 @@ struct lr_workspace {
     int32_t *icp_bucket;         // [max_n1] bucket of every target point
     float *icp_pts;              // [max_n1][4] target points in bucket order: x y z index-bits
     double *icp_state, *icp_part;
-    // --- timing hook ---
-    int timing;
-    hipEvent_t ev[LR_NEV];       // [0,1] forward filter pass, [2,3] RANSAC gen+score, [4,5] reverse filter pass, [6] call start, [7] forward NN done, [8] call end, [9] reverse NN done
-    float nn_ms_acc, ransac_ms_acc, call_ms_acc, fwd_ms_acc, fwd_filter_ms_acc, rev_filter_ms_acc, rev_ms_acc;
-    int rev_done_recorded;
-    int n_samples;
-    int ev_pending;
-    int rev_recorded;
+    lr_stage_timer timer;
 };
+
+// ---- call context ----------------------------------------------------------------------------------------------------
+// What an entry point hands to every launcher: built once, after the entry point's checks, and never stored.
+struct lr_call {
+    lr_workspace *ws;
+    hipStream_t st;
+    int pairs;                   // pairs of the call: the grids' z extent, and what the host decisions keyed on the batch size read
+    lr_zargs z;                  // the kernels' z argument
+    bool armed;                  // stage timer: timing was on and no uncollected sample pending when the call came in (lr_timer_mark).  A snapshot
+                                 // taken at entry on purpose: the call's own forward pass sets begun(), after which timer.armed() is false
+};
+static inline lr_call lr_call_single(lr_workspace *ws, void *stream) { return lr_call{ ws, (hipStream_t)stream, 1, lr_zargs{ 0, nullptr }, ws->timer.armed() }; }
+// (the pairs that ws->descs describes)
+static inline lr_call lr_call_batch(lr_workspace *ws, void *stream, int pairs) { return lr_call{ ws, (hipStream_t)stream, pairs, lr_zargs{ ws->stride, ws->descs }, ws->timer.armed() }; }
 
 enum {
     LR_CNT_FIX = 0,      // number of rows in fix_list
@@ -228,49 +255,45 @@ struct lr_ransac_state {
 };
 static_assert(sizeof(lr_ransac_state) <= (LR_CNT_TOTAL - LR_CNT_COUNT) * sizeof(int32_t), "lr_ransac_state does not fit");
 
-// lr_api.hip: zero `bytes` of scratch at `p` (arena 0) in the arena of every pair of the call in flight
-int lr_zero_scratch(lr_workspace *ws, void *p, size_t bytes, hipStream_t st);
+// lr_api.hip: zero `bytes` of scratch at `p` (arena 0) in the arena of every pair of the call
+int lr_zero_scratch(const lr_call &c, void *p, size_t bytes);
+// lr_api.hip: records `e` on the call's stream if the stage timer's rule for it says so
+int lr_timer_mark(const lr_call &c, lr_event e);
 
-// lr_nn16.hip
-int lr_nn16_prep(lr_workspace *ws, const float *F0, int n0, const float *F1, int n1, hipStream_t st, bool zero_counters = false);
-int lr_nn16_run(lr_workspace *ws, const float *Fq, const _Float16 *Hq, const float *nQ, int na,
-                const float *Fc, const _Float16 *Hc, const float *nC, const float *range_c, int nb,
-                int need, int32_t *idx1, int32_t *idx2, float *s1, float *s2, hipStream_t st, bool seed_reverse = false);
-int lr_nn16_reverse(lr_workspace *ws, const float *F0, const _Float16 *H0, const float *nrm0, const float *bmax0, int n0,
-                    const float *F1, const _Float16 *H1, const float *nrm1, int n1, const int32_t *fwd_idx1,
-                    int32_t *rev, hipStream_t st, bool seeded = false);
+// lr_nn16.hip: norms + f16 operand copies of both clouds; forward (rows of cloud 0 against cloud 1: first NN, and the second when idx2
+// is given); reverse (rows of cloud 1 against cloud 0, first NN only; `seeded`: by the forward pass of the same call)
+int lr_nn16_prep(const lr_call &c, const float *F0, int n0, const float *F1, int n1, bool zero_counters = false);
+int lr_nn16_run(const lr_call &c, const float *F0, int n0, const float *F1, int n1,
+                int32_t *idx1, int32_t *idx2, float *s1, float *s2, bool seed_reverse = false);
+int lr_nn16_reverse(const lr_call &c, const float *F0, int n0, const float *F1, int n1, const int32_t *fwd_idx1, int32_t *rev, bool seeded = false);
 
 // lr_filter.hip
-int lr_mutual_run(lr_workspace *ws, int n0, const int32_t *idx1, const int32_t *idx2, const int32_t *rev,
-                  uint8_t *is_bb, int32_t *o0, int32_t *o1, int32_t *o2, int32_t *n_out, hipStream_t st,
+int lr_mutual_run(const lr_call &c, int n0, const int32_t *idx1, const int32_t *idx2, const int32_t *rev,
+                  uint8_t *is_bb, int32_t *o0, int32_t *o1, int32_t *o2, int32_t *n_out,
                   const float *xyz0 = nullptr, const float *xyz1 = nullptr, float *corr8 = nullptr);
-int lr_identity_corr(lr_workspace *ws, int n0, const int32_t *idx1, const int32_t *idx2,
-                     int32_t *o0, int32_t *o1, int32_t *o2, int32_t *n_out, hipStream_t st);
-int lr_pack_corr(lr_workspace *ws, const float *xyz0, const float *xyz1, const int32_t *i0, const int32_t *i1, int m_max,
-                 const int32_t *m_dev, float *corr8, hipStream_t st, const int32_t *rank = nullptr);
-int lr_prosac_order(lr_workspace *ws, const float *F0, const float *F1, int dim, const float *quality, int m_max, const int32_t *m_dev,
-                    hipStream_t st);
-int lr_gpf_run(lr_workspace *ws, const float *F0, int n0, const float *F1, int dim,
+int lr_identity_corr(const lr_call &c, int n0, const int32_t *idx1, const int32_t *idx2,
+                     int32_t *o0, int32_t *o1, int32_t *o2, int32_t *n_out);
+int lr_pack_corr(const lr_call &c, const float *xyz0, const float *xyz1, const int32_t *i0, const int32_t *i1, int m_max,
+                 const int32_t *m_dev, float *corr8, const int32_t *rank = nullptr);
+int lr_prosac_order(const lr_call &c, const float *F0, const float *F1, int dim, const float *quality, int m_max, const int32_t *m_dev);
+// BB_first=True form of the grid filter: it runs over the mutual pairs (b0[k], idx1[k], idx2[k]), k < *mb_dev, with TOTAL_NUM = max_matches
+struct lr_gpf_subset { const int32_t *mb_dev, *b0; int32_t *has_score; double max_matches; };
+int lr_gpf_run(const lr_call &c, const float *F0, int n0, const float *F1, int dim,
                const int32_t *idx1, const int32_t *idx2, const uint8_t *is_bb, const float *xyz0,
                int grid_wid, double factor, int32_t *o0, int32_t *o1, int32_t *o2, float *oscore,
-               int32_t *n_out, hipStream_t st, const float *xyz1 = nullptr, float *corr8 = nullptr);
-
-int lr_gpf_bb_run(lr_workspace *ws, const float *F0, int n0, const float *F1, int dim,
-                  const int32_t *b0, const int32_t *b1, const int32_t *b2, const int32_t *mb_dev, const float *xyz0,
-                  int G, double max_matches, int32_t *o0, int32_t *o1, int32_t *o2, float *oscore,
-                  int32_t *n_out, int32_t *has_score, hipStream_t st);
+               int32_t *n_out, const float *xyz1 = nullptr, float *corr8 = nullptr, const lr_gpf_subset *sub = nullptr);
 
 // lr_icp.hip
-int lr_icp_run(lr_workspace *ws, const float *xyz0, int n0, const float *xyz1, int n1, const double *T_init,
+int lr_icp_run(const lr_call &c, const float *xyz0, int n0, const float *xyz1, int n1, const double *T_init,
                const lr_ransac_result *gate, double max_dist, int max_iter, double rel_fit, double rel_rmse,
-               double *T_out, lr_icp_result *res, hipStream_t st);
+               double *T_out, lr_icp_result *res);
 
 // lr_ransac.hip
-int lr_ransac_run(lr_workspace *ws, const float *corr8, int m_max, const int32_t *m_dev, const lr_ransac_params *p,
-                  double *T_out, lr_ransac_result *res, hipStream_t st);
+int lr_ransac_run(const lr_call &c, const float *corr8, int m_max, const int32_t *m_dev, const lr_ransac_params *p,
+                  double *T_out, lr_ransac_result *res);
 int lr_inlier_mask_run(const float *src, const float *tgt, const int32_t *i0, const int32_t *i1, int m_max, const int32_t *m_dev,
                        const double *T, float thr2, uint8_t *mask, int32_t *n_inliers, hipStream_t st);
-int lr_refit_run(lr_workspace *ws, const float *xyz0, int n0, const float *xyz1, const int32_t *idx1,
+int lr_refit_run(const lr_call &c, const float *xyz0, int n0, const float *xyz1, const int32_t *idx1,
                  const double *T_in, double thr2, double *T_out, int32_t *n_inl, const lr_ransac_result *gate,
-                 hipStream_t st, lr_pair_result *pair_out = nullptr, const int32_t *idx0 = nullptr, const int32_t *m_dev = nullptr,
+                 lr_pair_result *pair_out = nullptr, const int32_t *idx0 = nullptr, const int32_t *m_dev = nullptr,
                  const float *F0 = nullptr, const float *F1 = nullptr);

@@ -1178,12 +1178,13 @@ nn16_exact_kernel(const float *__restrict__ Fq, const float *__restrict__ nQ, in
 }
 
 // ------------------------------------------------------------------ host side
-int lr_nn16_prep(lr_workspace *ws, const float *F0, int n0, const float *F1, int n1, hipStream_t st, bool zero_counters)
+int lr_nn16_prep(const lr_call &c, const float *F0, int n0, const float *F1, int n1, bool zero_counters)
 {
-    hipLaunchKernelGGL(nn16_prep_kernel, dim3(lr_cdiv(n0, 32) + lr_cdiv(n1, 32), 1, ws->zP), dim3(256), 0, st, F0, n0, ws->H0, ws->nrm0, ws->bmax0, ws->bmin0,
-                       F1, n1, ws->H1, ws->nrm1, ws->bmax1, ws->bmin1, ws->rev_seed, ws->rev_seed64, ws->counters, zero_counters ? 1 : 0, lr_cdiv(n0, 32), ws->yshare, ws->z);
-    hipLaunchKernelGGL(nn16_range_kernel, dim3(2, 1, ws->zP), dim3(256), 0, st, n0, (const float *)ws->bmax0, (const float *)ws->bmin0, n1, (const float *)ws->bmax1,
-                       (const float *)ws->bmin1, ws->nn_range, ws->zP == 1 ? ws->form_dev : (int32_t *)nullptr, ws->z);
+    lr_workspace *ws = c.ws;
+    hipLaunchKernelGGL(nn16_prep_kernel, dim3(lr_cdiv(n0, 32) + lr_cdiv(n1, 32), 1, c.pairs), dim3(256), 0, c.st, F0, n0, ws->H0, ws->nrm0, ws->bmax0, ws->bmin0,
+                       F1, n1, ws->H1, ws->nrm1, ws->bmax1, ws->bmin1, ws->rev_seed, ws->rev_seed64, ws->counters, zero_counters ? 1 : 0, lr_cdiv(n0, 32), ws->yshare, c.z);
+    hipLaunchKernelGGL(nn16_range_kernel, dim3(2, 1, c.pairs), dim3(256), 0, c.st, n0, (const float *)ws->bmax0, (const float *)ws->bmin0, n1, (const float *)ws->bmax1,
+                       (const float *)ws->bmin1, ws->nn_range, c.pairs == 1 ? ws->form_dev : (int32_t *)nullptr, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
@@ -1194,25 +1195,66 @@ int lr_nn16_prep(lr_workspace *ws, const float *F0, int n0, const float *F1, int
 // clouds (the harness' calibration call next to user calls) would otherwise guess wrong on every call and pay the exact kernel's
 // full scan each time, silently -- it launches both forms instead, the cost of an empty launch.  A miss that still
 // happens (the first call of a changed workload) is reported in lr_pair_result.reserved[2].
-static int lr_nn16_form_hint(lr_workspace *ws, int col_cloud)
+static int lr_nn16_form_hint(const lr_call &c, int col_cloud)
 {
-    if (ws->zP != 1 || !ws->form_host) return 0;
+    lr_workspace *ws = c.ws;
+    if (c.pairs != 1 || !ws->form_host) return 0;
     const int h = *reinterpret_cast<const volatile int32_t *>(&ws->form_host[col_cloud]);
     const int prev = ws->form_prev[col_cloud];
     ws->form_prev[col_cloud] = h;
     return ((h == 1 || h == 2) && h == prev) ? h : 0;
 }
 
-int lr_nn16_run(lr_workspace *ws, const float *Fq, const _Float16 *Hq, const float *nQ, int na,
-                const float *Fc, const _Float16 *Hc, const float *nC, const float *range_c, int nb,
-                int need, int32_t *idx1, int32_t *idx2, float *s1, float *s2, hipStream_t st, bool seed_reverse)
+// One filter pass: what nn16_passb_kernel takes between its clock words and its grid (the candidate store is the workspace's), and the
+// shape of the pass.  dir 0: rows = cloud 0, columns = cloud 1; 1: the reverse pass.
+struct lr_pb_args {
+    const _Float16 *Hq; int na; const int32_t *rowmap, *na_dev;
+    const _Float16 *Hc; const float *nC; int nb, tps;
+    const float *tau;
+    const int32_t *colmap; const float *tile_min; const uint32_t *row_bound; const int32_t *rev_offs; const uint32_t *rev_range;
+    float *yfin; int yfin_stride; uint32_t *yshare;
+    lr_thr_in thr;
+    int row_blocks, strips, dir;
+};
+// The launch site of the filter pass, bracketed by the direction's stage-timer events.  Both forms of the walk's candidate test; the
+// blocks of the one the column norms do not ask for return at once.  A single-pair call launches only the form the column cloud's
+// norms asked for in the PREVIOUS call on this workspace (lr_nn16_form_hint: a flag the range kernel leaves in pinned host memory; no
+// synchronisation, any value is safe): if this call's norms ask for the other form, the launched kernel flags the miss and the exact
+// kernel re-does every row by the full scan -- correct, slow once, and the next call launches the right form.  (An empty launch costs
+// 4.7 us: 9.4 of a single pair's 346 us of kernels.)
+static int lr_nn16_passb(const lr_call &c, const lr_pb_args &a)
 {
+    lr_workspace *ws = c.ws;
+    // 1-D XCD-aware grid over (row block, strip, pair), padded to a multiple of 8
+    const int total = a.row_blocks * a.strips * c.pairs;
+    const dim3 grid(8 * lr_cdiv(total, 8));
+    LR_TRY_HIP(lr_timer_mark(c, a.dir ? LR_EV_REV_FILTER_BEGIN : LR_EV_FWD_FILTER_BEGIN));
+    const int only = lr_nn16_form_hint(c, a.dir ? 0 : 1);      // (the columns of the reverse pass are cloud 0)
+    int32_t *miss = ws->counters + (a.dir ? LR_CNT_FORM_MISS_R : LR_CNT_FORM_MISS_F);
+    unsigned long long *clk = ws->clock_probe ? ws->clk_dev : (unsigned long long *)nullptr;
+    const lr_pb_tail tl = { clk };
+    const lr_pb_grid pg = { a.row_blocks, a.strips, total, a.dir, only };
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, c.st, tl, clk, a.Hq, a.na, a.rowmap, a.na_dev, a.Hc, a.nC, a.nb, a.tps, a.tau, ws->cand_cnt, ws->cand,
+                           a.colmap, a.tile_min, a.row_bound, a.rev_offs, a.rev_range, a.yfin, a.yfin_stride, a.yshare, miss, a.thr, pg, c.z);
+    };
+    if (only != 2) launch(nn16_passb_kernel<true>);
+    if (only != 1) launch(nn16_passb_kernel<false>);
+    return lr_timer_mark(c, a.dir ? LR_EV_REV_FILTER_END : LR_EV_FWD_FILTER_END);
+}
+
+int lr_nn16_run(const lr_call &c, const float *Fq, int na, const float *Fc, int nb,
+                int32_t *idx1, int32_t *idx2, float *s1, float *s2, bool seed_reverse)
+{
+    lr_workspace *ws = c.ws;
+    const float *nQ = ws->nrm0, *nC = ws->nrm1, *range_c = ws->nn_range + 2;
+    const int need = idx2 ? 2 : 1;
     const int ntiles = lr_cdiv(nb, 32);
     const int row_blocks = lr_cdiv(na, LR_BLOCK_ROWS);
     // strips: enough blocks (over all pairs of a batched call) to fill 256 CUs a few times over, at least 64 tiles per strip
     // (a single pair: as many strips as keep ALL blocks resident at once -- the strips of a row block pool their thresholds, see the
     // kernel, so a shorter strip no longer means a looser one, and a second round of blocks would be a tail)
-    int strips = ws->zP > 1 ? lr_cdiv(ws->nn_blocks_batch, row_blocks * ws->zP) : ws->nn_blocks_target / row_blocks;
+    int strips = c.pairs > 1 ? lr_cdiv(ws->nn_blocks_batch, row_blocks * c.pairs) : ws->nn_blocks_target / row_blocks;
     int smax = ntiles / 64;
     if (strips > smax) strips = smax;
     if (strips > LR_NN_MAX_STRIPS) strips = LR_NN_MAX_STRIPS;
@@ -1226,37 +1268,18 @@ int lr_nn16_run(lr_workspace *ws, const float *Fq, const _Float16 *Hq, const flo
     if (ws->nn_sample_stride <= 0) { const int cap = strips > 1 ? 16 : 32; if (sstride > cap) sstride = cap; }      // (pipeline, 30k points: 16 / 24 / 32 / 48 / 64 -> 11 750 / 11 820 / 11 910 / 11 880 / 11 920 pairs/s)
     if (sstride < 1) sstride = 1;
     if (sstride > tps) sstride = tps;          // (one sampled tile per strip at least; keeps phase 1's column index in range)
-    // 1-D XCD-aware grid over (row block, strip, pair), padded to a multiple of 8
-    const int total = row_blocks * strips * ws->zP;
-    dim3 grid(8 * lr_cdiv(total, 8));
-    if (ws->timing && !ws->ev_pending) { LR_HIP(hipEventRecord(ws->ev[0], st)); }
-    lr_thr_in thr = { nQ, range_c, need, sstride };
-    // Both forms of the walk's candidate test; the blocks of the one the column norms do not ask for return at once.  A single-pair call
-    // launches only the form the column cloud's norms asked for in the PREVIOUS call on this workspace (lr_nn16_form_hint: a flag the range
-    // kernel leaves in pinned host memory; no synchronisation, any value is safe): if this call's norms ask for the other form, the
-    // launched kernel flags the miss and the exact kernel re-does every row by the full scan -- correct, slow once, and the next call
-    // launches the right form.  (An empty launch costs 4.7 us: 9.4 of a single pair's 346 us of kernels.)
-    const int only = lr_nn16_form_hint(ws, 1);
-    int32_t *miss = ws->counters + LR_CNT_FORM_MISS_F;
-    const lr_ex_out eo = { idx1, idx2, s1, s2, seed_reverse ? ws->rev_seed : (uint32_t *)nullptr, ws->rev_s1, reinterpret_cast<uint32_t *>(ws->counters + LR_CNT_RLO),
-                           ws->rev_seed64 };
-    unsigned long long *clk = ws->clock_probe ? ws->clk_dev : (unsigned long long *)nullptr;
-    const lr_pb_tail tl = { clk };
-    if (only != 2)
-        hipLaunchKernelGGL(nn16_passb_kernel<true>, grid, dim3(256), 0, st, tl, clk, Hq, na, (const int32_t *)nullptr, (const int32_t *)nullptr, Hc, nC, nb,
-                           tps, (const float *)nullptr, ws->cand_cnt, ws->cand, (const int32_t *)nullptr, (const float *)nullptr,
-                           (const uint32_t *)nullptr, (const int32_t *)nullptr, (const uint32_t *)nullptr, ws->yfin, ws->max_n, ws->yshare, miss, thr,
-                           lr_pb_grid{ row_blocks, strips, total, 0, only }, ws->z);
-    if (only != 1)
-        hipLaunchKernelGGL(nn16_passb_kernel<false>, grid, dim3(256), 0, st, tl, clk, Hq, na, (const int32_t *)nullptr, (const int32_t *)nullptr, Hc, nC, nb,
-                           tps, (const float *)nullptr, ws->cand_cnt, ws->cand, (const int32_t *)nullptr, (const float *)nullptr,
-                           (const uint32_t *)nullptr, (const int32_t *)nullptr, (const uint32_t *)nullptr, ws->yfin, ws->max_n, ws->yshare, miss, thr,
-                           lr_pb_grid{ row_blocks, strips, total, 0, only }, ws->z);
-    if (ws->timing && !ws->ev_pending) { LR_HIP(hipEventRecord(ws->ev[1], st)); ws->ev_pending = 1; }
-    const int ex_gx = lr_cdiv(na, LR_EX_ROWS), ex_total = ex_gx * ws->zP;
-    hipLaunchKernelGGL(nn16_exact_kernel, dim3(8 * lr_cdiv(ex_total, 8)), dim3(256), 0, st, Fq, nQ, na, Fc, nC, nb, ws->cand_cnt, ws->cand,
+    lr_pb_args a = {};      // (no row / column maps, bounds or start thresholds in this direction)
+    a.Hq = ws->H0; a.na = na; a.Hc = ws->H1; a.nC = nC; a.nb = nb; a.tps = tps;
+    a.yfin = ws->yfin; a.yfin_stride = ws->max_n; a.yshare = ws->yshare;
+    a.thr = lr_thr_in{ nQ, range_c, need, sstride };
+    a.row_blocks = row_blocks; a.strips = strips; a.dir = 0;
+    LR_TRY_HIP(lr_nn16_passb(c, a));
+    const lr_ex_out eo = { idx1, idx2, s1, idx2 ? s2 : (float *)nullptr, seed_reverse ? ws->rev_seed : (uint32_t *)nullptr, ws->rev_s1,
+                           reinterpret_cast<uint32_t *>(ws->counters + LR_CNT_RLO), ws->rev_seed64 };
+    const int ex_gx = lr_cdiv(na, LR_EX_ROWS), ex_total = ex_gx * c.pairs;
+    hipLaunchKernelGGL(nn16_exact_kernel, dim3(8 * lr_cdiv(ex_total, 8)), dim3(256), 0, c.st, Fq, nQ, na, Fc, nC, nb, ws->cand_cnt, ws->cand,
                        strips, need, (const float *)ws->yfin, ws->max_n, (const int32_t *)nullptr, (const int32_t *)nullptr, eo, ws->counters,
-                       range_c, 0, ex_gx, ex_total, ws->z);
+                       range_c, 0, ex_gx, ex_total, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
@@ -1470,10 +1493,10 @@ nn16_rev_order_kernel(int n0, int n1, const float *__restrict__ s1, const uint32
     }
 }
 
-int lr_nn16_reverse(lr_workspace *ws, const float *F0, const _Float16 *H0, const float *nrm0, const float *bmax0, int n0,
-                    const float *F1, const _Float16 *H1, const float *nrm1, int n1, const int32_t *fwd_idx1,
-                    int32_t *rev, hipStream_t st, bool seeded)
+int lr_nn16_reverse(const lr_call &c, const float *F0, int n0, const float *F1, int n1, const int32_t *fwd_idx1, int32_t *rev, bool seeded)
 {
+    lr_workspace *ws = c.ws; hipStream_t st = c.st;
+    const float *nrm0 = ws->nrm0, *nrm1 = ws->nrm1;
     // rows = cloud 1 (the columns of the forward direction), columns = cloud 0
     const int na = n1, nb = n0;
     const int ntiles = lr_cdiv(nb, 32);
@@ -1482,7 +1505,7 @@ int lr_nn16_reverse(lr_workspace *ws, const float *F0, const _Float16 *H0, const
     // strips offered to every row block (no pass-A partial arrays on this path: not bound by LR_NN_MAX_STRIPS).  A block that is
     // not needed leaves after three loads, but tens of thousands of them still cost: 8 for one pair (parallelism for the row blocks
     // with long prefixes), fewer the more pairs a batched call brings (2 at 32 pairs: 7 990 against 7 740 pairs/s with 16)
-    int strips = ws->rev_strips > 0 ? ws->rev_strips : 48 / ws->zP;
+    int strips = ws->rev_strips > 0 ? ws->rev_strips : 48 / c.pairs;
     if (ws->rev_strips <= 0) { if (strips > 8) strips = 8; if (strips < 2) strips = 2; }
     int smax = ntiles / 8;
     if (strips > smax) strips = smax;
@@ -1493,42 +1516,27 @@ int lr_nn16_reverse(lr_workspace *ws, const float *F0, const _Float16 *H0, const
     int32_t *n_rows = ws->counters + LR_CNT_NREV;
     if (!seeded)     // (the forward pass of lr_register_pair seeds from its exact kernel: same values, one launch less)
         hipLaunchKernelGGL(nn16_rev_seed_kernel, dim3(lr_cdiv(n0, 256)), dim3(256), 0, st, F0, nrm0, n0, F1, nrm1, fwd_idx1, seed, ws->rev_s1, range);
-    const int order_parts = ws->zP >= 16 ? 8 : ws->zP >= 4 ? 16 : 32;      // (a power of two; few pairs: more, smaller shares)
-    hipLaunchKernelGGL(nn16_rev_order_kernel, dim3(order_parts, 1, ws->zP), dim3(1024), 0, st, n0, n1, (const float *)ws->rev_s1, (const uint32_t *)seed,
-                       (const uint32_t *)range, ws->rev_hist, n_rows, bmax0, lr_cdiv(nb, 32), nrm1, H0, nrm0, ws->rev_cols, ws->Hs, ws->nrms,
-                       ws->rev_rows, ws->tau, ws->cand_cnt, rev, row_blocks * 4 * (strips + 1), ws->z);
+    const int order_parts = c.pairs >= 16 ? 8 : c.pairs >= 4 ? 16 : 32;      // (a power of two; few pairs: more, smaller shares)
+    hipLaunchKernelGGL(nn16_rev_order_kernel, dim3(order_parts, 1, c.pairs), dim3(1024), 0, st, n0, n1, (const float *)ws->rev_s1, (const uint32_t *)seed,
+                       (const uint32_t *)range, ws->rev_hist, n_rows, (const float *)ws->bmax0, lr_cdiv(nb, 32), nrm1, (const _Float16 *)ws->H0, nrm0, ws->rev_cols, ws->Hs, ws->nrms,
+                       ws->rev_rows, ws->tau, ws->cand_cnt, rev, row_blocks * 4 * (strips + 1), c.z);
     // grids are sized for all rows; blocks past the compacted count (or past their row block's strips) leave at once.
     // The column-prefix pruning (flagged by a non-null tile_min) rests on the keys being true lower bounds: that holds when
     // the list comes from this library's own forward pass (`seeded`, lr_register_pair).  A caller-supplied list (lr_nn_to_mutual,
     // lr_gpf*) may be anything -- the reference's nn_to_mutual accepts any corres_idx1 -- so every row block walks all column
     // tiles there: the seeds are still upper bounds of the row minima, only the prefix cut is given up.
-    const int total = row_blocks * strips * ws->zP;
-    dim3 grid(8 * lr_cdiv(total, 8));
-    const bool timed = ws->timing && ws->ev_pending == 1 && !ws->rev_recorded;
-    if (timed) { LR_HIP(hipEventRecord(ws->ev[4], st)); }
-    const int only = lr_nn16_form_hint(ws, 0);          // (the columns of the reverse pass are cloud 0)
-    int32_t *miss = ws->counters + LR_CNT_FORM_MISS_R;
-    const lr_thr_in rthr = { nullptr, (const float *)ws->nn_range, 1, 0 };      // (no tightening: the column norms' range selects the form of the walk's test)
+    lr_pb_args a = {};      // (no final thresholds kept, no pooling of them across strips in this direction)
+    a.Hq = ws->H1; a.na = na; a.rowmap = ws->rev_rows; a.na_dev = n_rows; a.Hc = ws->Hs; a.nC = ws->nrms; a.nb = nb; a.tps = tps;
+    a.tau = ws->tau;
+    a.colmap = ws->rev_cols; a.tile_min = seeded ? ws->rev_tmin : nullptr; a.row_bound = seed; a.rev_offs = ws->rev_hist; a.rev_range = range;
+    a.thr = lr_thr_in{ nullptr, ws->nn_range, 1, 0 };      // (no tightening: the column norms' range selects the form of the walk's test)
+    a.row_blocks = row_blocks; a.strips = strips; a.dir = 1;
+    LR_TRY_HIP(lr_nn16_passb(c, a));
     const lr_ex_out reo = { rev, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, seeded ? ws->rev_seed64 : (unsigned long long *)nullptr };
-    unsigned long long *clk = ws->clock_probe ? ws->clk_dev : (unsigned long long *)nullptr;
-    const lr_pb_tail tl = { clk };
-    if (only != 2)
-        hipLaunchKernelGGL(nn16_passb_kernel<true>, grid, dim3(256), 0, st, tl, clk, H1, na, (const int32_t *)ws->rev_rows, (const int32_t *)n_rows,
-                           (const _Float16 *)ws->Hs, (const float *)ws->nrms, nb, tps, ws->tau, ws->cand_cnt, ws->cand,
-                           (const int32_t *)ws->rev_cols, seeded ? (const float *)ws->rev_tmin : (const float *)nullptr, (const uint32_t *)seed,
-                           (const int32_t *)ws->rev_hist, (const uint32_t *)range, (float *)nullptr, 0, (uint32_t *)nullptr, miss, rthr,
-                           lr_pb_grid{ row_blocks, strips, total, 1, only }, ws->z);
-    if (only != 1)
-        hipLaunchKernelGGL(nn16_passb_kernel<false>, grid, dim3(256), 0, st, tl, clk, H1, na, (const int32_t *)ws->rev_rows, (const int32_t *)n_rows,
-                           (const _Float16 *)ws->Hs, (const float *)ws->nrms, nb, tps, ws->tau, ws->cand_cnt, ws->cand,
-                           (const int32_t *)ws->rev_cols, seeded ? (const float *)ws->rev_tmin : (const float *)nullptr, (const uint32_t *)seed,
-                           (const int32_t *)ws->rev_hist, (const uint32_t *)range, (float *)nullptr, 0, (uint32_t *)nullptr, miss, rthr,
-                           lr_pb_grid{ row_blocks, strips, total, 1, only }, ws->z);
-    if (timed) { LR_HIP(hipEventRecord(ws->ev[5], st)); ws->rev_recorded = 1; }
-    const int ex_gx = lr_cdiv(na, LR_EX_ROWS), ex_total = ex_gx * ws->zP;
+    const int ex_gx = lr_cdiv(na, LR_EX_ROWS), ex_total = ex_gx * c.pairs;
     hipLaunchKernelGGL(nn16_exact_kernel, dim3(8 * lr_cdiv(ex_total, 8)), dim3(256), 0, st, F1, nrm1, na, F0, nrm0, nb, ws->cand_cnt, ws->cand,
                        strips, 1, (const float *)nullptr, 0, (const int32_t *)ws->rev_rows, (const int32_t *)n_rows, reo, ws->counters,
-                       (const float *)ws->nn_range, 1, ex_gx, ex_total, ws->z);
+                       (const float *)ws->nn_range, 1, ex_gx, ex_total, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }

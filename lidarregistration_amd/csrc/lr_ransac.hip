@@ -1572,9 +1572,10 @@ int lr_inlier_mask_run(const float *src, const float *tgt, const int32_t *i0, co
     return LR_OK;
 }
 
-int lr_ransac_run(lr_workspace *ws, const float *corr8, int m_max, const int32_t *m_dev, const lr_ransac_params *p_in,
-                  double *T_out, lr_ransac_result *res, hipStream_t st)
+int lr_ransac_run(const lr_call &c, const float *corr8, int m_max, const int32_t *m_dev, const lr_ransac_params *p_in,
+                  double *T_out, lr_ransac_result *res)
 {
+    lr_workspace *ws = c.ws; hipStream_t st = c.st;
     LR_REQUIRE(p_in->scoring >= 0 && p_in->scoring <= 2, LR_EINVAL, "lr_ransac: scoring must be 0 (count, then error), 1 (MSAC) or 2 (MSAC at GC-RANSAC's truncated threshold)");
     LR_REQUIRE(p_in->lo_rounds >= 0 && p_in->lo_trials >= 0 && p_in->lo_trials <= 20 && p_in->lo_max_calls >= 0 && p_in->min_iters >= 0, LR_EINVAL,
                "lr_ransac: lo_rounds, lo_trials (<= 20), lo_max_calls and min_iters must be >= 0 (0 = default)");
@@ -1609,10 +1610,10 @@ int lr_ransac_run(lr_workspace *ws, const float *corr8, int m_max, const int32_t
     // blocks per pair of the local-optimisation launches: with one or a few pairs in the call the GPU is idle next to the one block
     // that optimises a pair's model, so helper blocks take shares of its scoring jobs (lo_score_shared); with a full batch the calls of the
     // other streams fill the GPU (2 / 4 / 8 helper groups per pair of a 32-pair call: +1 ... -3 % over the list runs, round 4)
-    const int lo_groups = (p->local_opt == 1 && m_max >= 4 * LO_CHUNK_REC) ? (ws->zP <= 2 ? 16 : ws->zP <= 4 ? 8 : 1) : 1;
-    if (ws->timing && ws->ev_pending == 1) { LR_HIP(hipEventRecord(ws->ev[2], st)); }
+    const int lo_groups = (p->local_opt == 1 && m_max >= 4 * LO_CHUNK_REC) ? (c.pairs <= 2 ? 16 : c.pairs <= 4 ? 8 : 1) : 1;
+    LR_TRY_HIP(lr_timer_mark(c, LR_EV_RANSAC_BEGIN));
     if (p->sampler == 1) {
-        hipLaunchKernelGGL(prosac_growth_kernel, dim3(1, 1, ws->zP), dim3(1024), 0, st, m_max, m_dev, p->sample_size, TN, ws->prosac_G, ws->z);
+        hipLaunchKernelGGL(prosac_growth_kernel, dim3(1, 1, c.pairs), dim3(1024), 0, st, m_max, m_dev, p->sample_size, TN, ws->prosac_G, c.z);
         G = ws->prosac_G;
     }
     for (long long h0l = 0; h0l < (p->iters > 0 ? p->iters : 1); h0l += B, B = geometric ? 8 * B : B) {
@@ -1622,24 +1623,24 @@ int lr_ransac_run(lr_workspace *ws, const float *corr8, int m_max, const int32_t
         const int gb = gb_all < 1024 ? gb_all : 1024;                       // blocks per pair (they stride over the groups)
         lr_score_info *info = reinterpret_cast<lr_score_info *>(ws->sc_info);
         // fit: a wave per 64 list slots, at most 4096 waves in the launch (four per SIMD; they stride over longer lists)
-        const int fb_all = lr_cdiv(h1 - h0 > 0 ? h1 - h0 : 1, 64), fb_cap = 4096 / ws->zP > 16 ? 4096 / ws->zP : 16;
+        const int fb_all = lr_cdiv(h1 - h0 > 0 ? h1 - h0 : 1, 64), fb_cap = 4096 / c.pairs > 16 ? 4096 / c.pairs : 16;
         const int fb = fb_all < fb_cap ? fb_all : fb_cap;
         if (p->sample_size == 3) {
-            hipLaunchKernelGGL(ransac_gen_kernel<3>, dim3(gb, 1, ws->zP), dim3(256), 0, st, corr8, m_max, m_dev, *p, h0, h1, ws->model_h, ws->score_cnt, ws->score_ssq,
-                               ws->counters, G, TN, info, ws->z);
-            hipLaunchKernelGGL(ransac_fit_kernel<3>, dim3(fb, 1, ws->zP), dim3(64), 0, st, corr8, m_max, m_dev, *p, ws->models, ws->models64, (const int32_t *)ws->model_h,
-                               (const int32_t *)ws->counters, G, TN, ws->max_iters, ws->z);
+            hipLaunchKernelGGL(ransac_gen_kernel<3>, dim3(gb, 1, c.pairs), dim3(256), 0, st, corr8, m_max, m_dev, *p, h0, h1, ws->model_h, ws->score_cnt, ws->score_ssq,
+                               ws->counters, G, TN, info, c.z);
+            hipLaunchKernelGGL(ransac_fit_kernel<3>, dim3(fb, 1, c.pairs), dim3(64), 0, st, corr8, m_max, m_dev, *p, ws->models, ws->models64, (const int32_t *)ws->model_h,
+                               (const int32_t *)ws->counters, G, TN, ws->max_iters, c.z);
         } else {
-            hipLaunchKernelGGL(ransac_gen_kernel<4>, dim3(gb, 1, ws->zP), dim3(256), 0, st, corr8, m_max, m_dev, *p, h0, h1, ws->model_h, ws->score_cnt, ws->score_ssq,
-                               ws->counters, G, TN, info, ws->z);
-            hipLaunchKernelGGL(ransac_fit_kernel<4>, dim3(fb, 1, ws->zP), dim3(64), 0, st, corr8, m_max, m_dev, *p, ws->models, ws->models64, (const int32_t *)ws->model_h,
-                               (const int32_t *)ws->counters, G, TN, ws->max_iters, ws->z);
+            hipLaunchKernelGGL(ransac_gen_kernel<4>, dim3(gb, 1, c.pairs), dim3(256), 0, st, corr8, m_max, m_dev, *p, h0, h1, ws->model_h, ws->score_cnt, ws->score_ssq,
+                               ws->counters, G, TN, info, c.z);
+            hipLaunchKernelGGL(ransac_fit_kernel<4>, dim3(fb, 1, c.pairs), dim3(64), 0, st, corr8, m_max, m_dev, *p, ws->models, ws->models64, (const int32_t *)ws->model_h,
+                               (const int32_t *)ws->counters, G, TN, ws->max_iters, c.z);
         }
         const bool sprt = p->use_elc == 2;
         if (sprt)       // every estimated model is pre-verified; the survivors form a second dense list that is scored in full
-            hipLaunchKernelGGL(ransac_sprt_kernel, dim3(gb_all, 1, ws->zP), dim3(256), 0, st, corr8, m_max, m_dev, p->thr2,
+            hipLaunchKernelGGL(ransac_sprt_kernel, dim3(gb_all, 1, c.pairs), dim3(256), 0, st, corr8, m_max, m_dev, p->thr2,
                                (const float *)ws->models, (const double *)ws->models64, (const int32_t *)ws->model_h, ws->models2, ws->models64_2, ws->model_h2,
-                               ws->score_cnt, ws->score_ssq, ws->counters, ws->max_iters, ws->z);
+                               ws->score_cnt, ws->score_ssq, ws->counters, ws->max_iters, c.z);
         const int vslot = sprt ? LR_CNT_NVALID2 : LR_CNT_NVALID;
         {
             // pilot-ordered scoring: head (every model over the first records) -> order (one block per pair) -> main.
@@ -1651,37 +1652,37 @@ int lr_ransac_run(lr_workspace *ws, const float *corr8, int m_max, const int32_t
             // Nor with a few pairs in the call: the GPU is not full, the main pass over everything costs a lone 30k pair 37 us where the
             // pruned pass costs 39 us AFTER 39 us of ordering launches (FR() 296 -> 254 us; one call of 2 / 4 / 8 / 16 pairs:
             // 0.50 -> 0.46, 0.69 -> 0.65, 1.00 -> 1.03, 1.67 -> 1.76 ms).
-            const bool may_prune = m_max >= LR_SC_MIN_M && h1 - h0 >= 2048 && ws->zP > LR_SC_MIN_PAIRS;
+            const bool may_prune = m_max >= LR_SC_MIN_M && h1 - h0 >= 2048 && c.pairs > LR_SC_MIN_PAIRS;
             if (may_prune) {
-                const int hgx = 64, htotal = hgx * ws->zP;
+                const int hgx = 64, htotal = hgx * c.pairs;
                 hipLaunchKernelGGL(ransac_score_kernel<1>, dim3(8 * lr_cdiv(htotal, 8)), dim3(256), 0, st, corr8, (const float *)ws->corr8s, m_max, m_dev, p->thr2,
                                    mdl, (const float *)ws->models_s, ws->score_cnt, ws->score_ssq, ws->counters, info, (const int32_t *)ws->sc_perm, (const int32_t *)ws->sc_glen, sub,
-                                   ws->max_iters, vslot, hgx, htotal, 1, ws->z);
-                const dim3 cgrid(lr_cdiv(m_max, 256), 1, ws->zP);
+                                   ws->max_iters, vslot, hgx, htotal, 1, c.z);
+                const dim3 cgrid(lr_cdiv(m_max, 256), 1, c.pairs);
                 hipLaunchKernelGGL(ransac_resid_kernel, cgrid, dim3(256), 0, st, corr8, m_max, m_dev, mdl, (const int32_t *)ws->counters, info, ws->sc_cb,
-                                   ws->max_iters, vslot, ws->z);
-                hipLaunchKernelGGL(ransac_order_kernel, dim3(1, 1, ws->zP), dim3(1024), 0, st, m_max, m_dev, p->thr2, mdl, ws->counters, info,
-                                   ws->sc_perm, ws->sc_glen, ws->sc_mb, ws->models_s, ws->max_iters, vslot, ws->z);
+                                   ws->max_iters, vslot, c.z);
+                hipLaunchKernelGGL(ransac_order_kernel, dim3(1, 1, c.pairs), dim3(1024), 0, st, m_max, m_dev, p->thr2, mdl, ws->counters, info,
+                                   ws->sc_perm, ws->sc_glen, ws->sc_mb, ws->models_s, ws->max_iters, vslot, c.z);
                 hipLaunchKernelGGL(ransac_scatter_kernel, cgrid, dim3(256), 0, st, corr8, ws->corr8s, m_max, m_dev, (const int32_t *)ws->counters, info,
-                                   (const uint8_t *)ws->sc_cb, vslot, ws->z);
+                                   (const uint8_t *)ws->sc_cb, vslot, c.z);
             }
-            const int sgx = LR_SCORE_BLOCKS / 4, stotal = sgx * ws->zP;
+            const int sgx = LR_SCORE_BLOCKS / 4, stotal = sgx * c.pairs;
             hipLaunchKernelGGL(ransac_score_kernel<0>, dim3(8 * lr_cdiv(stotal, 8)), dim3(256), 0, st, corr8, (const float *)ws->corr8s, m_max, m_dev, p->thr2,
                                mdl, (const float *)ws->models_s, ws->score_cnt, ws->score_ssq, ws->counters, info, (const int32_t *)ws->sc_perm, (const int32_t *)ws->sc_glen, sub,
-                               ws->max_iters, vslot, sgx, stotal, may_prune ? 1 : 0, ws->z);
+                               ws->max_iters, vslot, sgx, stotal, may_prune ? 1 : 0, c.z);
         }
-        if (h0 == 0 && ws->timing && ws->ev_pending == 1) { LR_HIP(hipEventRecord(ws->ev[3], st)); ws->ev_pending = 2; }
-        hipLaunchKernelGGL(ransac_final_kernel, dim3(1, 1, ws->zP), dim3(1024), 0, st, ws->score_cnt, ws->score_ssq,
+        if (h0 == 0) LR_TRY_HIP(lr_timer_mark(c, LR_EV_RANSAC_END));      // (generation + scoring of the first batch)
+        hipLaunchKernelGGL(ransac_final_kernel, dim3(1, 1, c.pairs), dim3(1024), 0, st, ws->score_cnt, ws->score_ssq,
                            sprt ? (const int32_t *)ws->model_h2 : (const int32_t *)ws->model_h, sprt ? (const double *)ws->models64_2 : (const double *)ws->models64,
-                           ws->counters, m_max, m_dev, *p, h1, T_out, res, vslot, lo_groups > 1 ? reinterpret_cast<int32_t *>(ws->lo_ctl) : (int32_t *)nullptr, ws->z);
+                           ws->counters, m_max, m_dev, *p, h1, T_out, res, vslot, lo_groups > 1 ? reinterpret_cast<int32_t *>(ws->lo_ctl) : (int32_t *)nullptr, c.z);
         if (p->local_opt == 1)
             // (near8 = the scratch of the pilot-ordered scoring: this batch's scoring is over, the next batch's scatter pass rewrites it before it is read)
-            hipLaunchKernelGGL(ransac_lo_kernel, dim3(lo_groups, 1, ws->zP), dim3(LO_THREADS), 0, st, corr8, m_max, m_dev, *p, h1, 0, ws->counters, ws->lo_list,
-                               T_out, res, reinterpret_cast<lr_lo_ctl *>(ws->lo_ctl), ws->corr8s, ws->z);
+            hipLaunchKernelGGL(ransac_lo_kernel, dim3(lo_groups, 1, c.pairs), dim3(LO_THREADS), 0, st, corr8, m_max, m_dev, *p, h1, 0, ws->counters, ws->lo_list,
+                               T_out, res, reinterpret_cast<lr_lo_ctl *>(ws->lo_ctl), ws->corr8s, c.z);
     }
     if (p->local_opt)          // final iterated least squares over the inliers
-        hipLaunchKernelGGL(ransac_lo_kernel, dim3(1, 1, ws->zP), dim3(LO_THREADS), 0, st, corr8, m_max, m_dev, *p, p->iters, 1, ws->counters, ws->lo_list,
-                           T_out, res, reinterpret_cast<lr_lo_ctl *>(ws->lo_ctl), (float *)nullptr, ws->z);
+        hipLaunchKernelGGL(ransac_lo_kernel, dim3(1, 1, c.pairs), dim3(LO_THREADS), 0, st, corr8, m_max, m_dev, *p, p->iters, 1, ws->counters, ws->lo_list,
+                           T_out, res, reinterpret_cast<lr_lo_ctl *>(ws->lo_ctl), (float *)nullptr, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
@@ -1837,16 +1838,17 @@ refit_moments_kernel(const float *__restrict__ xyz0, int n0, const float *__rest
     refit_solve_body(partial, (int)gridDim.x, T_in, gate, T_out, n_inl, pair_out, counters, F0 ? 1 : 0);
 }
 
-int lr_refit_run(lr_workspace *ws, const float *xyz0, int n0, const float *xyz1, const int32_t *idx1,
+int lr_refit_run(const lr_call &c, const float *xyz0, int n0, const float *xyz1, const int32_t *idx1,
                  const double *T_in, double thr2, double *T_out, int32_t *n_inl, const lr_ransac_result *gate,
-                 hipStream_t st, lr_pair_result *pair_out, const int32_t *idx0, const int32_t *m_dev,
+                 lr_pair_result *pair_out, const int32_t *idx0, const int32_t *m_dev,
                  const float *F0, const float *F1)
 {
+    lr_workspace *ws = c.ws; hipStream_t st = c.st;
     const int nb = lr_cdiv(n0, 256 * LR_REFIT_PER);
     int32_t *ticket = ws->counters + LR_CNT_REFIT_TICKET;
     if (!pair_out) LR_HIP(hipMemsetAsync(ticket, 0, sizeof(int32_t), st));      // lr_register_pair starts from cleared counters
-    hipLaunchKernelGGL(refit_moments_kernel, dim3(nb, 1, ws->zP), dim3(256), 0, st, xyz0, n0, xyz1, idx1, T_in, thr2, ws->refit_part, idx0, m_dev,
-                       F0, F1, ticket, gate, T_out, n_inl, pair_out, (const int32_t *)ws->counters, ws->z);
+    hipLaunchKernelGGL(refit_moments_kernel, dim3(nb, 1, c.pairs), dim3(256), 0, st, xyz0, n0, xyz1, idx1, T_in, thr2, ws->refit_part, idx0, m_dev,
+                       F0, F1, ticket, gate, T_out, n_inl, pair_out, (const int32_t *)ws->counters, c.z);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }

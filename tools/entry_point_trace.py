@@ -1,0 +1,38 @@
+"""One call of every entry point of liblidarreg.so that launches kernels, at dim 32 and dim 3: the workload behind
+profiles/host_context_trace.txt.  Run it under `rocprofv3 --kernel-trace -- python tools/entry_point_trace.py`, once per library
+(LIDARREG_LIB names an alternate build), and compare the two kernel traces with tools/trace_compare.py."""
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from lidarregistration_amd import FR, _ext, matching, ransac, synth
+from types import SimpleNamespace as Args      # (FR.pair_params supplies the reference's defaults for what is not given)
+
+t = torch.from_numpy
+SIZES = [(3000, 2500), (2000, 2500), (2500, 1800)]
+host = [synth.make_pair(N=n0, N1=n1, rho=0.5, s=0.9, seed=610 + k) for k, (n0, n1) in enumerate(SIZES)]
+dev = [tuple(t(p[key]).cuda() for key in ("xyz0", "xyz1", "feats0", "feats1")) for p in host]
+A, B, FA, FB = dev[0]
+
+# the pair pipeline: MNN / open3D and GPF / GC
+for kw in (dict(mode="MNN", codebase="open3D", ransac_n=3, o3d_conf=1.0), dict(mode="GPF", codebase="GC", prosac=True)):
+    FR.read_result(FR.register_pair_dev(A, B, FA, FB, FR.pair_params(Args(iters=2048, **kw))))
+# a ragged batch of three with the ICP stage inside, then the ICP stage on its own
+params = FR.pair_params(Args(mode="MNN", codebase="open3D", iters=2048, ransac_n=3, o3d_conf=1.0, icp=True))
+ws = _ext.Workspace(3000, 2500, 32, 2048, max_pairs=3)
+out = FR.register_batch_dev(dev, params, ws=ws)
+_ext.check(_ext.lib().lr_icp_batch(ws.handle, 0.6, 30, 1e-6, 1e-6, out.data_ptr(), torch.cuda.current_stream().cuda_stream))
+torch.cuda.synchronize()
+# every operator once
+i1, i2, _, _ = matching.nn_top2_dev(FA, FB, want_2nd=True, want_dist=True)
+_, o0, o1, _ = matching.mutual_dev(FA, FB, i1, i2)
+gpf = Args(GPF_grid_wid=7, GPF_factor=0.5, GPF_max_matches=300)
+matching.Grid_Prioritized_Filter(FA, FB, None, i1, i2, A, gpf)
+matching.Grid_Prioritized_Filter(FA, FB, None, i1, i2, A, gpf, BB_first=True)
+T, _ = ransac.ransac_dev(A[o0.long()], B[o1.long()], 2048, want_mask=True)
+ransac.refit_dev(A, B, i1, T)
+ransac.icp_dev(A, B, T)
+# descriptors narrower than 32: the coordinates themselves
+FR.read_result(FR.register_pair_dev(A, B, A.contiguous(), B.contiguous(), FR.pair_params(Args(mode="MNN", codebase="open3D", iters=2048, ransac_n=3, o3d_conf=1.0))))
+matching.nn_top2_dev(A, B)
+torch.cuda.synchronize()
+print("entry_point_trace: done")
