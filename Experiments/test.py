@@ -46,7 +46,7 @@ def get_args(argv=None):
         world_size, rank, do_analysis = 1, 0, True
     p = argparse.ArgumentParser()
     p.add_argument("--dataset", type=str, default="synthetic", help="A, B, S, K, L (balanced sets) or synthetic")
-    p.add_argument("--algo", type=str, default="RANSAC", choices=["RANSAC", "TEASER"])
+    p.add_argument("--algo", type=str, default="RANSAC", choices=["RANSAC", "TEASER", "SM"])
     p.add_argument("--codebase", type=str, default="GC", choices=["open3D", "GC"])
     p.add_argument("--mode", type=str, default="MNN", help="MNN (alias MMN), GPF or no_filter; with --algo TEASER: FAIL_TOLERANT or anything else")
     p.add_argument("--max_samples", type=int, default=None)
@@ -60,6 +60,8 @@ def get_args(argv=None):
     p.add_argument("--GPF_max_matches", type=int, default=10 ** 9)
     p.add_argument("--GC_conf", type=float, default=0.999)
     p.add_argument("--GC_LO", type=str2bool, default=True)
+    p.add_argument("--SM_top_ratio", type=float, default=0.05, help="--algo SM: share of the correspondences kept as inliers (baseline_KITTI.py:52)")
+    p.add_argument("--SM_iters", type=int, default=10, help="--algo SM: power iterations (baseline_3DMatch.py:41)")
     # additions of this implementation
     p.add_argument("--num_pairs", type=int, default=32, help="synthetic: number of pairs")
     p.add_argument("--synthetic_n", type=int, default=30000, help="synthetic: points per cloud")
@@ -111,6 +113,9 @@ def test_subset(args):
     if args.algo == "TEASER":
         from lidarregistration_amd import teaser
         run = teaser.eval_pairs(source, idx, args, batch=args.batch, nstreams=args.streams or 3, verbose=False)
+    elif args.algo == "SM":
+        from lidarregistration_amd import sm
+        run = sm.eval_pairs(source, idx, args, batch=args.batch, nstreams=args.streams or 3, verbose=False)
     elif args.serial:
         run = harness.eval_pairs_serial(source, idx, args, in_flight=min(args.in_flight, 4), verbose=args.rank == 0)
     else:

@@ -358,6 +358,56 @@ LR_API int lr_teaser_batch(int npairs, const float *const *src, const float *con
 LR_API int lr_teaser_timing(int enable);
 LR_API int lr_teaser_stage_times(float out[4]);
 
+/* ---- s1: spectral matching over M correspondences src[i] <-> tgt[i]  ([M,3] float32 device arrays) -------------------------------
+ * Replaces SM() of the reference's baseline survey (Experiments/baseline_scripts/baseline_3DMatch.py:19-53; run with inlier_threshold
+ * 0.6 and top_ratio 0.05 by baseline_KITTI.py:51-52) and the weighted fit it ends in (Experiments/models/common.py:7-45).  The M x M
+ * compatibility matrix is never stored: every power iteration re-evaluates it.  Contract (restated in tests/sm_cpu.py):
+ *  1. compatibility (3DMatch.py:20-37): c(i,j) = max(0, 4.5 - d^2 / (2 sigma^2)), sigma = inlier_threshold / 3, d = |a_i - a_j| - |b_i - b_j|,
+ *     in fp32 on the direct differences: (dx*dx + dy*dy) + dz*dz, correctly rounded sqrt, d = la - lb, fmaf(d*d, -1/(2 sigma^2), 4.5), no
+ *     other fusion.  c(i,i) = 0 by INDEX: a duplicated correspondence gets 4.5.  Deviation: a correspondence with a non-finite
+ *     coordinate has compatibility 0 with everything (the reference propagates NaN into every output);
+ *  2. power iteration (3DMatch.py:40-44): v = 1; `iterations` times v <- C v, v <- v / (|v|_2 + 1e-6).  Row sums are fp32 over column
+ *     chunks in ascending order, the chunks and the norm are summed in fp64 in a fixed order;
+ *  3. selection (3DMatch.py:47-49): K = (int)((double)M * top_ratio), Python's int(M * top_ratio); the K largest v under (value descending,
+ *     index ascending) -- torch's argsort leaves ties open, this pins them; labels in {0,1};
+ *  4. fit (3DMatch.py:52, common.py:7-45): weights w_i = v_i label_i, centroids divided by (sum w + 1e-6), covariance of the centred
+ *     points, all fp64 in a fixed order, rotation by the Horn solver of csrc/lr_contract.h (= V diag(1,1,det) U^T of common.py:36-41);
+ *  5. K < 3 or sum w = 0: status 1 and T = identity.
+ * The same input gives the same bits on every run, whatever the scratch held, alone or as pair k of a batch (on devices with the same
+ * number of compute units: it sizes the column chunks, i.e. the order of the fp32 sums).                                        */
+typedef struct lr_sm_params {
+    uint32_t struct_size;        /* = sizeof(lr_sm_params), checked like lr_ransac_params.struct_size                              */
+    int32_t  iterations;         /* power iterations, 10 (3DMatch.py:41); 1..1000                                                   */
+    double   inlier_threshold;   /* 0.6 (baseline_KITTI.py:51); sigma = inlier_threshold / 3                                        */
+    double   top_ratio;          /* 0.05 (baseline_KITTI.py:52; SM()'s own default is 0.1); in (0, 1]                               */
+} lr_sm_params;
+
+/* Written to device memory by lr_sm / lr_sm_batch (152 bytes). */
+typedef struct lr_sm_result {
+    double   T[16];              /* cloud 0 -> cloud 1, row-major; identity when status = 1                                        */
+    int32_t  status;             /* 0 ok, 1 = fewer than 3 selected correspondences or all of weight 0                              */
+    int32_t  K;                  /* selected correspondences                                                                        */
+    int32_t  m;                  /* live correspondence count the call ran on                                                       */
+    int32_t  reserved;           /* 0                                                                                               */
+    double   weight_sum;         /* sum of the weights w_i                                                                          */
+} lr_sm_result;
+
+/* Caller-owned device scratch per pair for up to max_m correspondences (0 when max_m is outside 0..32768). */
+LR_API size_t lr_sm_scratch_bytes(int max_m);
+/* m_dev, if not NULL, is a device int32 holding the live M (clamped to 0..m); K is then formed on the device.  eig_out (nullable,
+ * float32[m]) receives the final v, labels_out (nullable, uint8[m]) the labels; entries at and past the live count are written 0.
+ * scratch: >= lr_sm_scratch_bytes(m) bytes, 256-byte aligned, memory of the current device (checked, like the stream: LR_EINVAL).
+ * Every refusal (short scratch, m > 32768, iterations / top_ratio out of range, struct_size) is LR_EINVAL, before any launch.  */
+LR_API int lr_sm(const float *src, const float *tgt, int m, const int32_t *m_dev, const lr_sm_params *p, lr_sm_result *result,
+                 float *eig_out, uint8_t *labels_out, void *scratch, size_t scratch_bytes, void *stream);
+/* npairs (1..64) independent problems in one sequence of launches (the pair is a grid dimension); src/tgt/m/m_dev/eig_out/labels_out are
+ * HOST arrays of length npairs (m_dev, eig_out and labels_out, and their entries, may be NULL), carried by value into a setup kernel (no
+ * copy, no host synchronisation: graph-capturable); results is a DEVICE array of npairs blocks; scratch >= npairs *
+ * lr_sm_scratch_bytes(max m).  The result of pair k is bit-identical to lr_sm on that pair.                                       */
+LR_API int lr_sm_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
+                       const lr_sm_params *p, lr_sm_result *results, float *const *eig_out, uint8_t *const *labels_out, void *scratch,
+                       size_t scratch_bytes, void *stream);
+
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */
 LR_API int lr_workspace_timing(lr_workspace *ws, int enable);

@@ -21,6 +21,7 @@ SYMBOLS = [
     "lr_voxel_dedup_scratch_bytes", "lr_voxel_dedup", "lr_workspace_option", "lr_workspace_stage_times", "lr_icp_batch", "lr_workspace_lists_batch",
     "lr_workspace_clock", "lr_debug_fake_current_device",
     "lr_teaser_scratch_bytes", "lr_teaser", "lr_teaser_batch", "lr_teaser_timing", "lr_teaser_stage_times",
+    "lr_sm_scratch_bytes", "lr_sm", "lr_sm_batch",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -100,7 +101,24 @@ class TeaserResult(ctypes.Structure):
                 ("pad1", ctypes.c_int32)]
 
 
+class SmParams(ctypes.Structure):
+    """lr_sm_params with the settings the reference runs SM() with (baseline_KITTI.py:51-52) as defaults; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("iterations", ctypes.c_int32), ("inlier_threshold", ctypes.c_double),
+                ("top_ratio", ctypes.c_double)]
+    DEFAULTS = dict(iterations=10, inlier_threshold=0.6, top_ratio=0.05)
+
+    def __init__(self, **kw):
+        kw.pop("struct_size", None)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
+
+
+class SmResult(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_double * 16), ("status", ctypes.c_int32), ("K", ctypes.c_int32), ("m", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("weight_sum", ctypes.c_double)]
+
+
 assert ctypes.sizeof(TeaserParams) == 72 and ctypes.sizeof(TeaserResult) == 176
+assert ctypes.sizeof(SmParams) == 24 and ctypes.sizeof(SmResult) == 152
 assert ctypes.sizeof(PairResult) == 496 and ctypes.sizeof(RansacParams) == 72 and ctypes.sizeof(PairParams) == 112
 
 _lib = None
@@ -171,6 +189,10 @@ def lib():
         L.lr_teaser_batch.argtypes = [ci, pp, pp, ip, pp, ctypes.POINTER(TeaserParams), vp, pp, vp, ctypes.c_size_t, vp]
         L.lr_teaser_timing.argtypes = [ci]
         L.lr_teaser_stage_times.argtypes = [ctypes.POINTER(ctypes.c_float * 4)]
+        L.lr_sm_scratch_bytes.restype = ctypes.c_size_t
+        L.lr_sm_scratch_bytes.argtypes = [ci]
+        L.lr_sm.argtypes = [vp, vp, ci, vp, ctypes.POINTER(SmParams), vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.lr_sm_batch.argtypes = [ci, pp, pp, ip, pp, ctypes.POINTER(SmParams), vp, pp, pp, vp, ctypes.c_size_t, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

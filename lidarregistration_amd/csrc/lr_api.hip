@@ -72,6 +72,35 @@ static int check_device(const lr_workspace *ws, hipStream_t st, const char *who)
 }
 #define LR_CHECK_DEVICE(ws, stream, who) do { int rc_d_ = check_device(ws, (hipStream_t)(stream), who); if (rc_d_ != LR_OK) return rc_d_; } while (0)
 
+// The same check for an entry point without a workspace (lr_sm): the device that owns the caller's scratch takes the workspace's place.
+int lr_check_memory_device(const void *mem, hipStream_t st, const char *who, int *n_cus)
+{
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, mem) != hipSuccess || attr.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        lr_set_error("%s: scratch is not device memory", who);
+        return LR_EINVAL;
+    }
+    int cur = -1;
+    LR_HIP(hipGetDevice(&cur));
+    if (g_fake_device >= 0) cur = g_fake_device;
+    if (cur != attr.device) {
+        lr_set_error("%s: the scratch lives on device %d but device %d is current (hipSetDevice / torch.cuda.set_device before the call)", who, attr.device, cur);
+        return LR_EINVAL;
+    }
+    if (st) {
+        hipDevice_t sd = -1;
+        if (hipStreamGetDevice(st, &sd) == hipSuccess) {
+            if ((int)sd != attr.device) { lr_set_error("%s: the stream belongs to device %d, the scratch to device %d", who, (int)sd, attr.device); return LR_EINVAL; }
+        } else (void)hipGetLastError();
+    }
+    const lr_device_info *info = nullptr;
+    LR_TRY_HIP(device_info(attr.device, &info));
+    if (!info->ok) { lr_set_error("%s: device %d is %s; this library holds gfx950 code objects only", who, attr.device, info->arch); return LR_EINVAL; }
+    if (n_cus) *n_cus = info->cus;
+    return LR_OK;
+}
+
 // Test hook (no reference counterpart): from now on the entry points take `device` for the current device (-1: ask HIP again).  Lets the
 // one-GPU test box exercise the wrong-device refusal.
 extern "C" int lr_debug_fake_current_device(int device) { g_fake_device = device; return LR_OK; }

@@ -257,6 +257,9 @@ static_assert(sizeof(lr_ransac_state) <= (LR_CNT_TOTAL - LR_CNT_COUNT) * sizeof(
 
 // lr_api.hip: zero `bytes` of scratch at `p` (arena 0) in the arena of every pair of the call
 int lr_zero_scratch(const lr_call &c, void *p, size_t bytes);
+// lr_api.hip: the device check of an entry point that takes caller-owned scratch instead of a workspace: `mem` must be memory of the
+// current device (lr_debug_fake_current_device counts), a gfx950, and the stream must belong to it; *n_cus = its compute units
+int lr_check_memory_device(const void *mem, hipStream_t st, const char *who, int *n_cus);
 // lr_api.hip: records `e` on the call's stream if the stage timer's rule for it says so
 int lr_timer_mark(const lr_call &c, lr_event e);
 
