@@ -15,6 +15,7 @@ FCGF_FAST/test.py:86-106).  Datasets and FCGF weights are not part of this repo;
 """
 import argparse
 import datetime
+import importlib
 import logging
 import os
 import sys
@@ -27,6 +28,10 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s", datefmt="%m/%d %H:%M:%S", stream=sys.stdout)
+
+# --algo -> the module of lidarregistration_amd whose eval_pairs runs it (a correspondence-set solver on corrset.eval_pairs); every other
+# --algo goes through the FR pipeline's engines (harness.eval_pairs / eval_pairs_serial)
+CORRSET_ENGINES = {"TEASER": "teaser", "SM": "sm"}
 
 
 def str2bool(v):
@@ -110,12 +115,9 @@ def test_subset(args):
     idx = shard.shard_indices(P, args.world_size, args.rank)
     print("process %d, GPU: cuda:%d, %d pairs" % (args.rank, torch.cuda.current_device(), len(idx)))
     t0 = time.time()
-    if args.algo == "TEASER":
-        from lidarregistration_amd import teaser
-        run = teaser.eval_pairs(source, idx, args, batch=args.batch, nstreams=args.streams or 3, verbose=False)
-    elif args.algo == "SM":
-        from lidarregistration_amd import sm
-        run = sm.eval_pairs(source, idx, args, batch=args.batch, nstreams=args.streams or 3, verbose=False)
+    if args.algo in CORRSET_ENGINES:
+        engine = importlib.import_module("lidarregistration_amd." + CORRSET_ENGINES[args.algo])
+        run = engine.eval_pairs(source, idx, args, batch=args.batch, nstreams=args.streams or 3, verbose=False)
     elif args.serial:
         run = harness.eval_pairs_serial(source, idx, args, in_flight=min(args.in_flight, 4), verbose=args.rank == 0)
     else:

@@ -285,7 +285,8 @@ LR_API int lr_workspace_lists_batch(lr_workspace *ws, int npairs, int width, int
  * coords [n,3] float64 device = xyz / voxel_size (the division is the caller's, as in the reference); one point per occupied
  * integer cell floor(coords) is kept -- the first in input order -- and the kept point indices are written to sel in ascending
  * order, their number to *n_sel (device).  cells (optional, [n,3] int32) receives the integer cell of every kept point.
- * Points with a non-finite coordinate or |cell| >= 2^20 are dropped.  scratch: lr_voxel_dedup_scratch_bytes(n) device bytes.  */
+ * Points with a non-finite coordinate or |cell| >= 2^20 are dropped.  scratch: lr_voxel_dedup_scratch_bytes(n) device bytes, memory
+ * of the current device (checked, like the stream: LR_EINVAL, before any launch; n == 0 takes no scratch and checks none).       */
 LR_API size_t lr_voxel_dedup_scratch_bytes(int n);
 LR_API int    lr_voxel_dedup(const double *coords, int n, int32_t *sel, int32_t *n_sel, int32_t *cells, void *scratch,
                              size_t scratch_bytes, void *stream);
@@ -343,7 +344,8 @@ typedef struct lr_teaser_result {
  * i < M is ceil(max m / 64) uint64 words apart, bit j of word j / 64 set iff i ~ j (words past ceil(M / 64) are not written).     */
 LR_API size_t lr_teaser_scratch_bytes(int max_m);
 /* m_dev, if not NULL, is a device int32 holding the live M (clamped to 0..m).  clique_out (nullable, room for m int32) receives the
- * clique, ascending; result->K entries are live.  scratch: >= lr_teaser_scratch_bytes(m) bytes, 256-byte aligned.              */
+ * clique, ascending; result->K entries are live.  scratch: >= lr_teaser_scratch_bytes(m) bytes, 256-byte aligned, memory of the
+ * current device (checked, like the stream: LR_EINVAL, before any launch; a short scratch and m > 32768 are LR_ESIZE).          */
 LR_API int lr_teaser(const float *src, const float *tgt, int m, const int32_t *m_dev, const lr_teaser_params *p,
                      lr_teaser_result *result, int32_t *clique_out, void *scratch, size_t scratch_bytes, void *stream);
 /* npairs (1..64) independent problems in one sequence of launches (the pair is a grid dimension); src/tgt/m/m_dev/clique_out are

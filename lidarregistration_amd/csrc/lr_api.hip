@@ -72,7 +72,7 @@ static int check_device(const lr_workspace *ws, hipStream_t st, const char *who)
 }
 #define LR_CHECK_DEVICE(ws, stream, who) do { int rc_d_ = check_device(ws, (hipStream_t)(stream), who); if (rc_d_ != LR_OK) return rc_d_; } while (0)
 
-// The same check for an entry point without a workspace (lr_sm): the device that owns the caller's scratch takes the workspace's place.
+// The same check for the entry points without a workspace (lr_teaser, lr_sm, lr_voxel_dedup): the device that owns the caller's scratch takes the workspace's place.
 int lr_check_memory_device(const void *mem, hipStream_t st, const char *who, int *n_cus)
 {
     hipPointerAttribute_t attr;
@@ -447,28 +447,8 @@ static int check_nn_args(const lr_workspace *ws, const void *F0, int n0, const v
 #define LR_TRY(x) do { int rc_ = (x); if (rc_ != LR_OK) return rc_; } while (0)
 
 
-// The params structs start with their own size: a caller built against another version of include/lidarreg.h is turned away instead
-// of having a shorter struct read past its end (lr_version 102)
-static int check_ransac_params(const lr_ransac_params *p, const char *who)
-{
-    if (!p) { lr_set_error("%s: null params", who); return LR_EINVAL; }
-    if (p->struct_size != sizeof(lr_ransac_params)) {
-        lr_set_error("%s: lr_ransac_params.struct_size is %u, this library (lr_version %d) expects %zu -- set it to sizeof(lr_ransac_params) / rebuild against include/lidarreg.h",
-                     who, p->struct_size, lr_version(), sizeof(lr_ransac_params));
-        return LR_EINVAL;
-    }
-    return LR_OK;
-}
-static int check_pair_params(const lr_pair_params *p, const char *who)
-{
-    if (!p) { lr_set_error("%s: null params", who); return LR_EINVAL; }
-    if (p->struct_size != sizeof(lr_pair_params)) {
-        lr_set_error("%s: lr_pair_params.struct_size is %u, this library (lr_version %d) expects %zu -- set it to sizeof(lr_pair_params) / rebuild against include/lidarreg.h",
-                     who, p->struct_size, lr_version(), sizeof(lr_pair_params));
-        return LR_EINVAL;
-    }
-    return check_ransac_params(&p->ransac, who);
-}
+static int check_ransac_params(const lr_ransac_params *p, const char *who) { LR_CHECK_STRUCT_SIZE(lr_ransac_params, p, who); return LR_OK; }
+static int check_pair_params(const lr_pair_params *p, const char *who) { LR_CHECK_STRUCT_SIZE(lr_pair_params, p, who); return check_ransac_params(&p->ransac, who); }
 
 // Descriptors narrower than 32 (matching.py:22-65 is dimension-agnostic; FCGF_FAST/net/BBR_F.py:148-176 calls it with D = 3): zero-padded
 // fp32 copies in the workspace, and everything downstream runs 32 wide on them.  A zero term changes neither the fma chains of the

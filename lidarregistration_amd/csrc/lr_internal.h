@@ -35,6 +35,16 @@ __host__ __device__ static inline int lr_seg_cap(int strips) { const int c = (LR
 
 #define LR_TRY_HIP(x) do { int rc__ = (x); if (rc__ != LR_OK) return rc__; } while (0)
 
+// The params structs start with their own size: a caller built against another version of include/lidarreg.h is turned away instead
+// of having a shorter struct read past its end (lr_version 102).  First check of every check_*_params; `who` = the entry point.
+#define LR_CHECK_STRUCT_SIZE(T, p, who) do {                                                                                            \
+        if (!(p)) { lr_set_error("%s: null params", who); return LR_EINVAL; }                                                            \
+        if ((p)->struct_size != sizeof(T)) {                                                                                             \
+            lr_set_error("%s: " #T ".struct_size is %u, this library (lr_version %d) expects %zu -- set it to sizeof(" #T ") / rebuild against include/lidarreg.h", \
+                         who, (p)->struct_size, lr_version(), sizeof(T));                                                                \
+            return LR_EINVAL;                                                                                                            \
+        } } while (0)
+
 // Column strips of the NN distance kernel: each wave owns 32 query rows x one strip.
 #define LR_NN_MAX_STRIPS 8
 #define LR_FEAT_DIM 32

@@ -20,26 +20,15 @@
 //   sm_fit_kernel      one block per pair: weighted fp64 centroids and covariance in a fixed order, Horn's solver of lr_contract.h
 // No floating-point atomics anywhere: every sum has one order, which depends on the pair's own M (and the device's compute-unit count)
 // only -- never on the batch the pair is in, on scheduling or on what the scratch held.
-#include "lr_internal.h"
+#include "lr_corrset.h"
 #include "lr_contract.h"
 #include <math.h>
 
-#define SM_MAX_M 32768
 #define SM_MAX_CHUNKS 64
 #define SM_MAX_TARGET 4096           // upper bound of the matvec's work items per pair (it sizes part[][] without knowing the device)
 #define SM_MAX_ITERS 1000
 
 typedef float sm_f32x8 __attribute__((ext_vector_type(8)));
-
-struct sm_desc {
-    const float *a, *b;
-    const int32_t *m_dev;
-    float *eig_out;
-    uint8_t *labels_out;
-    int32_t m;
-    int32_t pad;
-};
-struct sm_desc_table { sm_desc d[LR_MAX_BATCH]; };
 
 // per-pair control block at the head of the pair's scratch arena
 struct sm_ctl {
@@ -70,7 +59,6 @@ __host__ __device__ static inline sm_plan sm_make_plan(int m, int target)
 }
 
 struct sm_layout { size_t ctl, rec, part, rowsum, sel, total; };
-static inline size_t sm_al(size_t x) { return (x + 255) & ~size_t(255); }
 static sm_layout sm_make_layout(int max_m)
 {
     const size_t Mp = ((size_t)(max_m < 1 ? 1 : max_m) + 63) & ~size_t(63);
@@ -84,11 +72,11 @@ static sm_layout sm_make_layout(int max_m)
     if (items < rb) items = rb;
     sm_layout L;
     size_t o = 0;
-    L.ctl = o;    o += sm_al(sizeof(sm_ctl));
-    L.rec = o;    o += sm_al(Mp * 32);
-    L.part = o;   o += sm_al(items * 64 * 4);
-    L.rowsum = o; o += sm_al(Mp * 8);
-    L.sel = o;    o += sm_al(Mp * 4);
+    L.ctl = o;    o += cs_al(sizeof(sm_ctl));
+    L.rec = o;    o += cs_al(Mp * 32);
+    L.part = o;   o += cs_al(items * 64 * 4);
+    L.rowsum = o; o += cs_al(Mp * 8);
+    L.sel = o;    o += cs_al(Mp * 4);
     L.total = o;
     return L;
 }
@@ -100,22 +88,16 @@ struct sm_args {
     sm_layout L;
 };
 
-template <typename T> __device__ __forceinline__ T *sm_ptr(const sm_args &g, int pair, size_t off)
-{
-    return reinterpret_cast<T *>(g.base + (size_t)pair * g.stride + off);
-}
-
 // ---- setup: descriptors by value -> control blocks (no host copy, graph-capturable) ------------------------------------------
-__global__ void sm_setup_kernel(sm_desc_table t, sm_args g, int npairs, double top_ratio)
+__global__ void sm_setup_kernel(cs_desc_table t, sm_args g, int npairs, double top_ratio)
 {
     const int k = threadIdx.x;
     if (k >= npairs) return;
-    const sm_desc d = t.d[k];
-    sm_ctl *c = sm_ptr<sm_ctl>(g, k, g.L.ctl);
-    int m = d.m;
-    if (d.m_dev) { const int v = *d.m_dev; m = v < 0 ? 0 : (v < m ? v : m); }
+    const cs_desc d = t.d[k];
+    sm_ctl *c = cs_ptr<sm_ctl>(g, k, g.L.ctl);
+    const int m = cs_live_m(d);
     const sm_plan p = sm_make_plan(m, g.target);
-    c->a = d.a; c->b = d.b; c->eig_out = d.eig_out; c->labels_out = d.labels_out;
+    c->a = d.a; c->b = d.b; c->eig_out = (float *)d.out0; c->labels_out = (uint8_t *)d.out1;
     c->m_host = d.m; c->m = m;
     c->K = (int)((double)m * top_ratio);             // Python's int(M * top_ratio): the product in double, truncated
     c->rb = p.rb; c->chunks = p.chunks; c->per = p.per;
@@ -126,10 +108,10 @@ __global__ void sm_setup_kernel(sm_desc_table t, sm_args g, int npairs, double t
 __global__ void __launch_bounds__(256) sm_pack_kernel(sm_args g)
 {
     const int pair = blockIdx.z;
-    const sm_ctl *c = sm_ptr<sm_ctl>(g, pair, g.L.ctl);
+    const sm_ctl *c = cs_ptr<sm_ctl>(g, pair, g.L.ctl);
     const int m = c->m, m4 = (m + 3) & ~3, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= m4) return;
-    float *rec = sm_ptr<float>(g, pair, g.L.rec) + (size_t)i * 8;
+    float *rec = cs_ptr<float>(g, pair, g.L.rec) + (size_t)i * 8;
     float r[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
     bool ok = i < m;
     if (ok) {
@@ -242,12 +224,12 @@ __global__ void __launch_bounds__(SM_NB) sm_norm_kernel(sm_args g, int last)
 {
     __shared__ double s_red[SM_NB];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const sm_ctl *c = sm_ptr<sm_ctl>(g, pair, g.L.ctl);
+    const sm_ctl *c = cs_ptr<sm_ctl>(g, pair, g.L.ctl);
     const int m = c->m, chunks = c->chunks, Mp = c->rb * 64;
     if (m <= 0) return;
-    const float *part = sm_ptr<float>(g, pair, g.L.part);
-    double *rowsum = sm_ptr<double>(g, pair, g.L.rowsum);
-    float *rec = sm_ptr<float>(g, pair, g.L.rec);
+    const float *part = cs_ptr<float>(g, pair, g.L.part);
+    double *rowsum = cs_ptr<double>(g, pair, g.L.rowsum);
+    float *rec = cs_ptr<float>(g, pair, g.L.rec);
     double q = 0.0;
     for (int i = tid; i < m; i += SM_NB) {
         double s = 0.0;
@@ -285,10 +267,10 @@ __global__ void __launch_bounds__(SM_NB) sm_select_kernel(sm_args g)
     __shared__ int s_cnt[SM_NB / 64];
     __shared__ unsigned s_pick[2];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    sm_ctl *c = sm_ptr<sm_ctl>(g, pair, g.L.ctl);
+    sm_ctl *c = cs_ptr<sm_ctl>(g, pair, g.L.ctl);
     const int m = c->m, mh = c->m_host, K = c->K;
-    const uint32_t *rec = sm_ptr<uint32_t>(g, pair, g.L.rec);
-    int32_t *sel = sm_ptr<int32_t>(g, pair, g.L.sel);
+    const uint32_t *rec = cs_ptr<uint32_t>(g, pair, g.L.rec);
+    int32_t *sel = cs_ptr<int32_t>(g, pair, g.L.sel);
     uint8_t *labels = c->labels_out;
     float *eig = c->eig_out;
     // the K-th largest value: its bits (v >= 0), most significant byte first
@@ -341,10 +323,10 @@ __global__ void __launch_bounds__(SM_FB) sm_fit_kernel(sm_args g, lr_sm_result *
 {
     __shared__ double s_red[SM_FB];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const sm_ctl *c = sm_ptr<sm_ctl>(g, pair, g.L.ctl);
+    const sm_ctl *c = cs_ptr<sm_ctl>(g, pair, g.L.ctl);
     const int K = c->K, n = c->nsel;
-    const float *rec = sm_ptr<float>(g, pair, g.L.rec);
-    const int32_t *sel = sm_ptr<int32_t>(g, pair, g.L.sel);
+    const float *rec = cs_ptr<float>(g, pair, g.L.rec);
+    const int32_t *sel = cs_ptr<int32_t>(g, pair, g.L.sel);
     const float *a = c->a, *b = c->b;
     lr_sm_result *res = results + pair;
     // weights w = v of the selected entries; an entry of weight 0 adds nothing and is not read (its coordinates may be non-finite)
@@ -394,58 +376,41 @@ static_assert(sizeof(lr_sm_params) == 24 && sizeof(lr_sm_result) == 152, "ABI st
 
 extern "C" size_t lr_sm_scratch_bytes(int max_m)
 {
-    if (max_m < 0 || max_m > SM_MAX_M) return 0;
+    if (max_m < 0 || max_m > CS_MAX_M) return 0;
     return sm_make_layout(max_m).total;
 }
 
 static int check_sm_params(const lr_sm_params *p, const char *who)
 {
-    if (!p) { lr_set_error("%s: null params", who); return LR_EINVAL; }
-    if (p->struct_size != sizeof(lr_sm_params)) {
-        lr_set_error("%s: lr_sm_params.struct_size is %u, this library (lr_version %d) expects %zu -- set it to sizeof(lr_sm_params) / rebuild against include/lidarreg.h",
-                     who, p->struct_size, lr_version(), sizeof(lr_sm_params));
-        return LR_EINVAL;
-    }
+    LR_CHECK_STRUCT_SIZE(lr_sm_params, p, who);
     if (p->iterations < 1 || p->iterations > SM_MAX_ITERS) { lr_set_error("%s: iterations must lie in 1..%d", who, SM_MAX_ITERS); return LR_EINVAL; }
     if (!(p->inlier_threshold > 0.0 && isfinite(p->inlier_threshold))) { lr_set_error("%s: inlier_threshold must be positive and finite", who); return LR_EINVAL; }
     if (!(p->top_ratio > 0.0 && p->top_ratio <= 1.0)) { lr_set_error("%s: top_ratio must lie in (0, 1]", who); return LR_EINVAL; }
     return LR_OK;
 }
 
-extern "C" int lr_sm_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
-                           const lr_sm_params *p, lr_sm_result *results, float *const *eig_out, uint8_t *const *labels_out,
-                           void *scratch, size_t scratch_bytes, void *stream)
+// `who`: the entry point the params messages name; the checks of the shared front have always reported as lr_sm_batch
+static int sm_run(const char *who, int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
+                  const lr_sm_params *p, lr_sm_result *results, float *const *eig_out, uint8_t *const *labels_out,
+                  void *scratch, size_t scratch_bytes, void *stream)
 {
-    LR_TRY_HIP(check_sm_params(p, "lr_sm_batch"));
-    LR_REQUIRE(npairs >= 1 && npairs <= LR_MAX_BATCH, LR_EINVAL, "lr_sm_batch: npairs must lie in 1..64");
-    LR_REQUIRE(src && tgt && m && results && scratch, LR_EINVAL, "lr_sm_batch: null pointer");
-    sm_desc_table t;
-    int mx = 0;
-    for (int k = 0; k < npairs; ++k) {
-        LR_REQUIRE(m[k] >= 0, LR_EINVAL, "lr_sm_batch: negative correspondence count");
-        LR_REQUIRE(m[k] <= SM_MAX_M, LR_EINVAL, "lr_sm_batch: more than 32768 correspondences");
-        LR_REQUIRE(m[k] == 0 || (src[k] && tgt[k]), LR_EINVAL, "lr_sm_batch: null point array");
-        t.d[k] = sm_desc{ src[k], tgt[k], m_dev ? m_dev[k] : nullptr, eig_out ? eig_out[k] : nullptr, labels_out ? labels_out[k] : nullptr, m[k], 0 };
-        mx = m[k] > mx ? m[k] : mx;
-    }
-    for (int k = npairs; k < LR_MAX_BATCH; ++k) t.d[k] = sm_desc{ nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0 };
-    const size_t per = lr_sm_scratch_bytes(mx);
-    LR_REQUIRE(scratch_bytes >= per * (size_t)npairs, LR_EINVAL, "lr_sm_batch: scratch too small (npairs * lr_sm_scratch_bytes(max m))");
-    LR_REQUIRE(((uintptr_t)scratch & 255) == 0, LR_EINVAL, "lr_sm_batch: scratch must be 256-byte aligned");
-    int n_cus = 0;
-    LR_TRY_HIP(lr_check_memory_device(scratch, (hipStream_t)stream, "lr_sm_batch", &n_cus));
+    static const cs_backend be = { "lr_sm_batch", "lr_sm_scratch_bytes", lr_sm_scratch_bytes, LR_EINVAL };
+    LR_TRY_HIP(check_sm_params(p, who));
+    cs_front f;
+    LR_TRY_HIP(cs_check_batch(be, npairs, src, tgt, m, m_dev, (void *const *)eig_out, (void *const *)labels_out, results, scratch, scratch_bytes, stream, &f));
+    const int mx = f.mx;
 
     sm_args g;
     g.base = reinterpret_cast<char *>(scratch);
-    g.stride = per;
+    g.stride = f.per;
     g.L = sm_make_layout(mx);
-    g.target = 8 * n_cus;                            // two waves per SIMD
+    g.target = 8 * f.n_cus;                          // two waves per SIMD
     if (g.target > SM_MAX_TARGET) g.target = SM_MAX_TARGET;
     if (g.target < 64) g.target = 64;
     const double sigma = p->inlier_threshold / 3.0;
     const float nk = (float)(-1.0 / (2.0 * sigma * sigma));
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(sm_setup_kernel, dim3(1), dim3(64), 0, st, t, g, npairs, p->top_ratio);
+    hipLaunchKernelGGL(sm_setup_kernel, dim3(1), dim3(64), 0, st, f.t, g, npairs, p->top_ratio);
     if (mx > 0) {
         const sm_plan plan = sm_make_plan(mx, g.target);
         int items = plan.rb * plan.chunks;           // (a smaller live M plans at most max(target, its row blocks) items; the waves stride over them)
@@ -463,9 +428,15 @@ extern "C" int lr_sm_batch(int npairs, const float *const *src, const float *con
     return LR_OK;
 }
 
+extern "C" int lr_sm_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
+                           const lr_sm_params *p, lr_sm_result *results, float *const *eig_out, uint8_t *const *labels_out,
+                           void *scratch, size_t scratch_bytes, void *stream)
+{
+    return sm_run("lr_sm_batch", npairs, src, tgt, m, m_dev, p, results, eig_out, labels_out, scratch, scratch_bytes, stream);
+}
+
 extern "C" int lr_sm(const float *src, const float *tgt, int m, const int32_t *m_dev, const lr_sm_params *p, lr_sm_result *result,
                      float *eig_out, uint8_t *labels_out, void *scratch, size_t scratch_bytes, void *stream)
 {
-    LR_TRY_HIP(check_sm_params(p, "lr_sm"));
-    return lr_sm_batch(1, &src, &tgt, &m, &m_dev, p, result, &eig_out, &labels_out, scratch, scratch_bytes, stream);
+    return sm_run("lr_sm", 1, &src, &tgt, &m, &m_dev, p, result, &eig_out, &labels_out, scratch, scratch_bytes, stream);
 }

@@ -17,22 +17,13 @@
 //                                      endpoint is the set of intervals whose entry key <= its key < their exit key), then
 //                 tz_final_kernel      first minimum per axis, translation inliers, result block.
 // All reductions run in a fixed order, so a pair's result does not depend on the batch it is in or on scheduling.
-#include "lr_internal.h"
+#include "lr_corrset.h"
 #include <math.h>
 
-#define TZ_MAX_M 32768
+#define TZ_MAX_M CS_MAX_M
 #define TZ_MAX_W (TZ_MAX_M / 64)
 #define TZ_NWL (TZ_MAX_W / 64)       // bitset words per lane of the search wave
 #define TZ_GREEDY_WAVES 16
-
-struct tz_desc {
-    const float *a, *b;
-    const int32_t *m_dev;
-    int32_t *clique_out;
-    int32_t m;
-    int32_t pad;
-};
-struct tz_desc_table { tz_desc d[LR_MAX_BATCH]; };
 
 // per-pair control block at the head of the pair's scratch arena
 struct tz_ctl {
@@ -50,8 +41,6 @@ struct tz_layout {
     size_t ctl, adj, cadj, stack, core, rlist, cstack, bestc, clique, pidx, bits, tim, wgt, xv, ecost, total;
 };
 
-static inline size_t tz_al(size_t x) { return (x + 255) & ~size_t(255); }
-
 __host__ __device__ static inline int tz_words(int m) { return (m + 63) >> 6; }
 
 static tz_layout tz_make_layout(int max_m)
@@ -59,21 +48,21 @@ static tz_layout tz_make_layout(int max_m)
     const size_t W = (size_t)tz_words(max_m < 1 ? 1 : max_m), Mp = W * 64;
     tz_layout L;
     size_t o = 0;
-    L.ctl = o;    o += tz_al(sizeof(tz_ctl));
-    L.adj = o;    o += tz_al(Mp * W * 8);
-    L.cadj = o;   o += tz_al(Mp * W * 8);
-    L.stack = o;  o += tz_al((Mp + 1) * W * 8);
-    L.core = o;   o += tz_al(Mp * 4);
-    L.rlist = o;  o += tz_al(Mp * 4);
-    L.cstack = o; o += tz_al(Mp * 4);
-    L.bestc = o;  o += tz_al(Mp * 4);
-    L.clique = o; o += tz_al(Mp * 4);
-    L.pidx = o;   o += tz_al(Mp * 4);
-    L.bits = o;   o += tz_al(3 * W * 8);       // [0] incumbent clique, [1] universal vertices, [2] final clique
-    L.tim = o;    o += tz_al(6 * Mp * 8);
-    L.wgt = o;    o += tz_al(Mp * 8);
-    L.xv = o;     o += tz_al(3 * Mp * 8);
-    L.ecost = o;  o += tz_al(3 * 2 * Mp * 8);
+    L.ctl = o;    o += cs_al(sizeof(tz_ctl));
+    L.adj = o;    o += cs_al(Mp * W * 8);
+    L.cadj = o;   o += cs_al(Mp * W * 8);
+    L.stack = o;  o += cs_al((Mp + 1) * W * 8);
+    L.core = o;   o += cs_al(Mp * 4);
+    L.rlist = o;  o += cs_al(Mp * 4);
+    L.cstack = o; o += cs_al(Mp * 4);
+    L.bestc = o;  o += cs_al(Mp * 4);
+    L.clique = o; o += cs_al(Mp * 4);
+    L.pidx = o;   o += cs_al(Mp * 4);
+    L.bits = o;   o += cs_al(3 * W * 8);       // [0] incumbent clique, [1] universal vertices, [2] final clique
+    L.tim = o;    o += cs_al(6 * Mp * 8);
+    L.wgt = o;    o += cs_al(Mp * 8);
+    L.xv = o;     o += cs_al(3 * Mp * 8);
+    L.ecost = o;  o += cs_al(3 * 2 * Mp * 8);
     L.total = o;
     return L;
 }
@@ -85,11 +74,6 @@ struct tz_args {
     tz_layout L;
 };
 
-template <typename T> __device__ __forceinline__ T *tz_ptr(const tz_args &g, int pair, size_t off)
-{
-    return reinterpret_cast<T *>(g.base + (size_t)pair * g.stride + off);
-}
-
 __device__ __forceinline__ void tz_wsync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -98,15 +82,14 @@ __device__ __forceinline__ void tz_wsync()
 }
 
 // ---- setup: descriptors by value -> control blocks (no host copy, graph-capturable) --------------------------------------
-__global__ void tz_setup_kernel(tz_desc_table t, tz_args g, int npairs)
+__global__ void tz_setup_kernel(cs_desc_table t, tz_args g, int npairs)
 {
     const int k = threadIdx.x;
     if (k >= npairs) return;
-    const tz_desc d = t.d[k];
-    tz_ctl *c = tz_ptr<tz_ctl>(g, k, g.L.ctl);
-    int m = d.m;
-    if (d.m_dev) { const int v = *d.m_dev; m = v < 0 ? 0 : (v < m ? v : m); }
-    c->a = d.a; c->b = d.b; c->clique_out = d.clique_out;
+    const cs_desc d = t.d[k];
+    tz_ctl *c = cs_ptr<tz_ctl>(g, k, g.L.ctl);
+    const int m = cs_live_m(d);
+    c->a = d.a; c->b = d.b; c->clique_out = (int32_t *)d.out0;
     c->m = m; c->W = tz_words(m);
     c->maxcore = 0; c->lb = 0; c->nU = 0; c->nR = 0; c->target = 0; c->done = 0;
     c->K = 0; c->exact = 1; c->found = 0; c->nbest = 0;
@@ -140,11 +123,11 @@ __device__ __forceinline__ bool tz_edge(float aix, float aiy, float aiz, float b
 __global__ void __launch_bounds__(256) tz_graph_kernel(tz_args g, double thr)
 {
     const int pair = blockIdx.z;
-    const tz_ctl *c = tz_ptr<tz_ctl>(g, pair, g.L.ctl);
+    const tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
     const int m = c->m, i0 = blockIdx.x * 64, chunk = blockIdx.y * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i0 >= m || chunk * 64 >= m) return;
     const float *__restrict__ a = c->a, *__restrict__ b = c->b;
-    unsigned long long *adj = tz_ptr<unsigned long long>(g, pair, g.L.adj);
+    unsigned long long *adj = cs_ptr<unsigned long long>(g, pair, g.L.adj);
     const float thr32 = (float)thr;
     const int j = chunk * 64 + lane;
     const bool jv = j < m;
@@ -191,12 +174,12 @@ __global__ void __launch_bounds__(1024) tz_peel_kernel(tz_args g, double kcore_t
     __shared__ int s_red[16], s_gsize[TZ_GREEDY_WAVES];
     __shared__ int s_seed[TZ_GREEDY_WAVES];
     const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    tz_ctl *c = tz_ptr<tz_ctl>(g, pair, g.L.ctl);
+    tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
     const int m = c->m, W = c->W, Ws = g.Wmax;
     if (m == 0) { if (tid == 0) c->done = 1; return; }
-    const unsigned long long *adj = tz_ptr<unsigned long long>(g, pair, g.L.adj);
-    int32_t *core = tz_ptr<int32_t>(g, pair, g.L.core);
-    unsigned long long *bits = tz_ptr<unsigned long long>(g, pair, g.L.bits);
+    const unsigned long long *adj = cs_ptr<unsigned long long>(g, pair, g.L.adj);
+    int32_t *core = cs_ptr<int32_t>(g, pair, g.L.core);
+    unsigned long long *bits = cs_ptr<unsigned long long>(g, pair, g.L.bits);
     unsigned long long *inc = bits, *ubits = bits + Ws, *fin = bits + 2 * Ws;
 
     // degrees (popcount of the rows) and the alive set
@@ -356,7 +339,7 @@ __global__ void __launch_bounds__(1024) tz_peel_kernel(tz_args g, double kcore_t
         return;
     }
     // compact list of the remaining vertices, ascending
-    int32_t *rlist = tz_ptr<int32_t>(g, pair, g.L.rlist);
+    int32_t *rlist = cs_ptr<int32_t>(g, pair, g.L.rlist);
     if (tid == 0) {
         int off = 0;
         for (int w = 0; w < W; ++w) { const int pc = __popcll(s_alive[w]); s_deg[w] = off; off += pc; }    // (s_deg is free again)
@@ -374,12 +357,12 @@ __global__ void __launch_bounds__(1024) tz_peel_kernel(tz_args g, double kcore_t
 __global__ void __launch_bounds__(256) tz_compact_kernel(tz_args g)
 {
     const int pair = blockIdx.y;
-    const tz_ctl *c = tz_ptr<tz_ctl>(g, pair, g.L.ctl);
+    const tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
     if (c->done) return;
     const int n = c->nR, Wn = tz_words(n), Ws = g.Wmax;
-    const unsigned long long *adj = tz_ptr<unsigned long long>(g, pair, g.L.adj);
-    unsigned long long *cadj = tz_ptr<unsigned long long>(g, pair, g.L.cadj);
-    const int32_t *rlist = tz_ptr<int32_t>(g, pair, g.L.rlist);
+    const unsigned long long *adj = cs_ptr<unsigned long long>(g, pair, g.L.adj);
+    unsigned long long *cadj = cs_ptr<unsigned long long>(g, pair, g.L.cadj);
+    const int32_t *rlist = cs_ptr<int32_t>(g, pair, g.L.rlist);
     for (int r = blockIdx.x; r < n; r += gridDim.x) {
         const unsigned long long *row = adj + (size_t)rlist[r] * Ws;
         for (int w = threadIdx.x; w < Wn; w += 256) {
@@ -409,20 +392,20 @@ __device__ __forceinline__ int tz_lowest(const unsigned long long (&x)[TZ_NWL], 
 __global__ void __launch_bounds__(64) tz_search_kernel(tz_args g, long long node_budget, unsigned long long tick_budget)
 {
     const int pair = blockIdx.x, lane = threadIdx.x;
-    tz_ctl *c = tz_ptr<tz_ctl>(g, pair, g.L.ctl);
+    tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
     const int m = c->m, W = c->W, Ws = g.Wmax;
-    unsigned long long *bits = tz_ptr<unsigned long long>(g, pair, g.L.bits);
+    unsigned long long *bits = cs_ptr<unsigned long long>(g, pair, g.L.bits);
     unsigned long long *inc = bits, *ubits = bits + Ws, *fin = bits + 2 * Ws;
-    int32_t *clique = tz_ptr<int32_t>(g, pair, g.L.clique);
+    int32_t *clique = cs_ptr<int32_t>(g, pair, g.L.clique);
     if (m == 0) { if (lane == 0) { c->K = 0; c->exact = 1; c->nodes = 0; } return; }
     long long nodes = 0;
     int aborted = 0;
     if (!c->done) {
         const int n = c->nR, Wn = tz_words(n);
-        const unsigned long long *cadj = tz_ptr<unsigned long long>(g, pair, g.L.cadj);
-        unsigned long long *stack = tz_ptr<unsigned long long>(g, pair, g.L.stack);
-        int32_t *cstack = tz_ptr<int32_t>(g, pair, g.L.cstack), *bestc = tz_ptr<int32_t>(g, pair, g.L.bestc);
-        const int32_t *rlist = tz_ptr<int32_t>(g, pair, g.L.rlist);
+        const unsigned long long *cadj = cs_ptr<unsigned long long>(g, pair, g.L.cadj);
+        unsigned long long *stack = cs_ptr<unsigned long long>(g, pair, g.L.stack);
+        int32_t *cstack = cs_ptr<int32_t>(g, pair, g.L.cstack), *bestc = cs_ptr<int32_t>(g, pair, g.L.bestc);
+        const int32_t *rlist = cs_ptr<int32_t>(g, pair, g.L.rlist);
         int best = c->target, found = 0;
         for (int w = lane; w < Wn; w += 64) { const int lo = w * 64; stack[w] = (n - lo >= 64) ? ~0ull : ((1ull << (n - lo)) - 1ull); }
         tz_wsync();
@@ -605,12 +588,12 @@ __global__ void __launch_bounds__(TZ_RB) tz_rot_kernel(tz_args g, double nb2, do
     __shared__ double s_red[10][TZ_RB];
     __shared__ double s_R[9];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    tz_ctl *c = tz_ptr<tz_ctl>(g, pair, g.L.ctl);
+    tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
     const int K = c->K;
     if (K < 3) { if (tid == 0) c->status = 1; return; }
     const size_t Mp = (size_t)g.Wmax * 64;
-    const int32_t *clique = tz_ptr<int32_t>(g, pair, g.L.clique);
-    double *tim = tz_ptr<double>(g, pair, g.L.tim), *wgt = tz_ptr<double>(g, pair, g.L.wgt);
+    const int32_t *clique = cs_ptr<int32_t>(g, pair, g.L.clique);
+    double *tim = cs_ptr<double>(g, pair, g.L.tim), *wgt = cs_ptr<double>(g, pair, g.L.wgt);
     const float *a = c->a, *b = c->b;
     double v[10];
     for (int i = 0; i < 10; ++i) v[i] = 0.0;
@@ -659,8 +642,8 @@ __global__ void __launch_bounds__(TZ_RB) tz_rot_kernel(tz_args g, double nb2, do
     }
     // rotation inliers (w >= 0.5; all when GNC did not start) -> participating clique points, ascending, and their x = b - R a
     __shared__ int s_cnt[TZ_RB / 64 + 1];
-    int32_t *pidx = tz_ptr<int32_t>(g, pair, g.L.pidx);
-    double *xv = tz_ptr<double>(g, pair, g.L.xv);
+    int32_t *pidx = cs_ptr<int32_t>(g, pair, g.L.pidx);
+    double *xv = cs_ptr<double>(g, pair, g.L.xv);
     int base = 0;
     for (int k0 = 0; k0 < K; k0 += TZ_RB) {
         const int k = k0 + tid;
@@ -703,13 +686,13 @@ __global__ void __launch_bounds__(256) tz_vote_kernel(tz_args g, double beta)
 {
     __shared__ double s_x[256];
     const int pair = blockIdx.z, axis = blockIdx.y, tid = threadIdx.x;
-    const tz_ctl *c = tz_ptr<tz_ctl>(g, pair, g.L.ctl);
+    const tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
     if (c->status) return;
     const int n = c->n_part;
     if ((int)blockIdx.x * 256 >= 2 * n) return;
     const size_t Mp = (size_t)g.Wmax * 64;
-    const double *x = tz_ptr<double>(g, pair, g.L.xv) + axis * Mp;
-    double *ecost = tz_ptr<double>(g, pair, g.L.ecost) + axis * 2 * Mp;
+    const double *x = cs_ptr<double>(g, pair, g.L.xv) + axis * Mp;
+    double *ecost = cs_ptr<double>(g, pair, g.L.ecost) + axis * 2 * Mp;
     const int e = blockIdx.x * 256 + tid;
     const bool ev = e < 2 * n;
     const int ie = e >> 1, te = e & 1;
@@ -740,16 +723,16 @@ __global__ void __launch_bounds__(256) tz_final_kernel(tz_args g, double beta, l
     __shared__ double s_red[10][TZ_RB];
     __shared__ double s_t[3];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    tz_ctl *c = tz_ptr<tz_ctl>(g, pair, g.L.ctl);
+    tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
     lr_teaser_result *res = results + pair;
     const int status = c->status, n = c->n_part;
     const size_t Mp = (size_t)g.Wmax * 64;
-    const double *xv = tz_ptr<double>(g, pair, g.L.xv);
+    const double *xv = cs_ptr<double>(g, pair, g.L.xv);
     int ntrans = 0;
     if (!status) {
         for (int axis = 0; axis < 3; ++axis) {
             const double *x = xv + axis * Mp;
-            const double *ec = tz_ptr<double>(g, pair, g.L.ecost) + axis * 2 * Mp;
+            const double *ec = cs_ptr<double>(g, pair, g.L.ecost) + axis * 2 * Mp;
             // first minimum: smallest (cost, key)
             double bc = INFINITY, bv = 0; int be = -1;
             for (int e = tid; e < 2 * n; e += 256) {
@@ -839,12 +822,7 @@ extern "C" int lr_teaser_stage_times(float out[4])
 
 static int check_teaser_params(const lr_teaser_params *p, const char *who)
 {
-    if (!p) { lr_set_error("%s: null params", who); return LR_EINVAL; }
-    if (p->struct_size != sizeof(lr_teaser_params)) {
-        lr_set_error("%s: lr_teaser_params.struct_size is %u, this library (lr_version %d) expects %zu -- set it to sizeof(lr_teaser_params) / rebuild against include/lidarreg.h",
-                     who, p->struct_size, lr_version(), sizeof(lr_teaser_params));
-        return LR_EINVAL;
-    }
+    LR_CHECK_STRUCT_SIZE(lr_teaser_params, p, who);
     if (!(p->noise_bound > 0.0 && isfinite(p->noise_bound))) { lr_set_error("%s: noise_bound must be positive and finite", who); return LR_EINVAL; }
     if (!(p->cbar2 > 0.0 && isfinite(p->cbar2))) { lr_set_error("%s: cbar2 must be positive and finite", who); return LR_EINVAL; }
     if (!(p->kcore_threshold > 0.0 && p->kcore_threshold <= 1.0)) { lr_set_error("%s: kcore_threshold must lie in (0, 1]", who); return LR_EINVAL; }
@@ -860,26 +838,16 @@ static int check_teaser_params(const lr_teaser_params *p, const char *who)
     return LR_OK;
 }
 
-extern "C" int lr_teaser_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m,
-                               const int32_t *const *m_dev, const lr_teaser_params *p, lr_teaser_result *results,
-                               int32_t *const *clique_out, void *scratch, size_t scratch_bytes, void *stream)
+// `who`: the entry point the params messages name; the checks of the shared front have always reported as lr_teaser_batch
+static int tz_run(const char *who, int npairs, const float *const *src, const float *const *tgt, const int32_t *m,
+                  const int32_t *const *m_dev, const lr_teaser_params *p, lr_teaser_result *results,
+                  int32_t *const *clique_out, void *scratch, size_t scratch_bytes, void *stream)
 {
-    LR_TRY_HIP(check_teaser_params(p, "lr_teaser_batch"));
-    LR_REQUIRE(npairs >= 1 && npairs <= LR_MAX_BATCH, LR_EINVAL, "lr_teaser_batch: npairs must lie in 1..64");
-    LR_REQUIRE(src && tgt && m && results && scratch, LR_EINVAL, "lr_teaser_batch: null pointer");
-    tz_desc_table t;
-    int mx = 0;
-    for (int k = 0; k < npairs; ++k) {
-        LR_REQUIRE(m[k] >= 0, LR_EINVAL, "lr_teaser_batch: negative correspondence count");
-        LR_REQUIRE(m[k] <= TZ_MAX_M, LR_ESIZE, "lr_teaser_batch: more than 32768 correspondences");
-        LR_REQUIRE(m[k] == 0 || (src[k] && tgt[k]), LR_EINVAL, "lr_teaser_batch: null point array");
-        t.d[k] = tz_desc{ src[k], tgt[k], m_dev ? m_dev[k] : nullptr, clique_out ? clique_out[k] : nullptr, m[k], 0 };
-        mx = m[k] > mx ? m[k] : mx;
-    }
-    for (int k = npairs; k < LR_MAX_BATCH; ++k) t.d[k] = tz_desc{ nullptr, nullptr, nullptr, nullptr, 0, 0 };
-    const size_t per = lr_teaser_scratch_bytes(mx);
-    LR_REQUIRE(scratch_bytes >= per * (size_t)npairs, LR_ESIZE, "lr_teaser_batch: scratch too small (npairs * lr_teaser_scratch_bytes(max m))");
-    LR_REQUIRE(((uintptr_t)scratch & 255) == 0, LR_EINVAL, "lr_teaser_batch: scratch must be 256-byte aligned");
+    static const cs_backend be = { "lr_teaser_batch", "lr_teaser_scratch_bytes", lr_teaser_scratch_bytes, LR_ESIZE };
+    LR_TRY_HIP(check_teaser_params(p, who));
+    cs_front f;
+    LR_TRY_HIP(cs_check_batch(be, npairs, src, tgt, m, m_dev, (void *const *)clique_out, nullptr, results, scratch, scratch_bytes, stream, &f));
+    const int mx = f.mx;
     int dev = 0, khz = 0;
     LR_HIP(hipGetDevice(&dev));
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) khz = 100000;
@@ -887,7 +855,7 @@ extern "C" int lr_teaser_batch(int npairs, const float *const *src, const float 
 
     tz_args g;
     g.base = reinterpret_cast<char *>(scratch);
-    g.stride = per;
+    g.stride = f.per;
     g.Wmax = tz_words(mx < 1 ? 1 : mx);
     g.L = tz_make_layout(mx);
     const double beta = p->noise_bound;
@@ -896,7 +864,7 @@ extern "C" int lr_teaser_batch(int npairs, const float *const *src, const float 
     hipStream_t st = (hipStream_t)stream;
     const bool tm = g_tz_timing && g_tz_ev_ok;
     if (tm) LR_HIP(hipEventRecord(g_tz_ev[0], st));
-    hipLaunchKernelGGL(tz_setup_kernel, dim3(1), dim3(64), 0, st, t, g, npairs);
+    hipLaunchKernelGGL(tz_setup_kernel, dim3(1), dim3(64), 0, st, f.t, g, npairs);
     if (mx > 0)
         hipLaunchKernelGGL(tz_graph_kernel, dim3(lr_cdiv(mx, 64), lr_cdiv(g.Wmax, 4), npairs), dim3(256), 0, st, g, thr);
     if (tm) LR_HIP(hipEventRecord(g_tz_ev[1], st));
@@ -913,9 +881,15 @@ extern "C" int lr_teaser_batch(int npairs, const float *const *src, const float 
     return LR_OK;
 }
 
+extern "C" int lr_teaser_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m,
+                               const int32_t *const *m_dev, const lr_teaser_params *p, lr_teaser_result *results,
+                               int32_t *const *clique_out, void *scratch, size_t scratch_bytes, void *stream)
+{
+    return tz_run("lr_teaser_batch", npairs, src, tgt, m, m_dev, p, results, clique_out, scratch, scratch_bytes, stream);
+}
+
 extern "C" int lr_teaser(const float *src, const float *tgt, int m, const int32_t *m_dev, const lr_teaser_params *p,
                          lr_teaser_result *result, int32_t *clique_out, void *scratch, size_t scratch_bytes, void *stream)
 {
-    LR_TRY_HIP(check_teaser_params(p, "lr_teaser"));
-    return lr_teaser_batch(1, &src, &tgt, &m, &m_dev, p, result, &clique_out, scratch, scratch_bytes, stream);
+    return tz_run("lr_teaser", 1, &src, &tgt, &m, &m_dev, p, result, &clique_out, scratch, scratch_bytes, stream);
 }

@@ -114,6 +114,7 @@ extern "C" int lr_voxel_dedup(const double *coords, int n, int32_t *sel, int32_t
     LR_REQUIRE(scratch_bytes >= lr_voxel_dedup_scratch_bytes(n), LR_ESIZE, "lr_voxel_dedup: scratch too small (lr_voxel_dedup_scratch_bytes)");
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) { LR_HIP(hipMemsetAsync(n_sel, 0, sizeof(int32_t), st)); return LR_OK; }
+    LR_TRY_HIP(lr_check_memory_device(scratch, st, "lr_voxel_dedup", nullptr));      // (n == 0 takes no scratch: nothing to check)
     const size_t cap = vx_capacity(n);
     char *p = reinterpret_cast<char *>(scratch);
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(p); p += cap * 8;

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import FR as fr
-from . import _ext, io_lists, metrics, synth
+from . import _ext, io_lists, metrics, ransac, synth
 
 
 class SyntheticSource:
@@ -289,7 +289,7 @@ _NCORR_OFF = _ext.PairResult.n_corr.offset
 
 @dataclass(frozen=True)
 class EvalRun:
-    """What an evaluation engine (eval_pairs, eval_pairs_serial, teaser.eval_pairs) returns.  It unpacks as (stats, T), the
+    """What an evaluation engine (eval_pairs, eval_pairs_serial, corrset.eval_pairs) returns.  It unpacks as (stats, T), the
     engines' return value before the record existed, so `stats, T = eval_pairs(...)` keeps working."""
     stats: np.ndarray                 # [n,22] float64, the reference's layout (write_row)
     T: np.ndarray                     # [n,4,4] float64
@@ -576,13 +576,9 @@ def eval_pairs_serial(source, indices, args, device=None, in_flight=4, verbose=F
             icp_buf, ev2 = None, None
             if getattr(args, "icp", False):
                 # ICP refinement of the registration result, timed on its own like the reference's icp_timer
-                T_icp = torch.empty(16, dtype=torch.float64, device=dev)
-                res_icp = torch.empty(ctypes.sizeof(_ext.IcpResult), dtype=torch.uint8, device=dev)
-                _ext.check(_ext.lib().lr_icp(wss[s].handle, x0.data_ptr(), n0, x1.data_ptr(), n1, out.data_ptr(), 2 * fr.VOXEL_SIZE, 30,
-                                              1e-6, 1e-6, T_icp.data_ptr(), res_icp.data_ptr(), streams[s].cuda_stream))
+                icp_buf = ransac.icp_launch(wss[s], x0, x1, out.data_ptr(), streams[s].cuda_stream, max_dist=2 * fr.VOXEL_SIZE)
                 ev2 = torch.cuda.Event(enable_timing=True)
                 ev2.record(streams[s])
-                icp_buf = (T_icp, res_icp)
             nn1 = torch.empty((1, n0), dtype=torch.int32, device=dev); c0 = torch.empty_like(nn1); c1 = torch.empty_like(nn1)
             _ext.check(_ext.lib().lr_workspace_lists_at(wss[s].handle, 0, n0, nn1.data_ptr(), None, c0.data_ptr(), c1.data_ptr(), streams[s].cuda_stream))
             n_corr = out[_NCORR_OFF:_NCORR_OFF + 4].view(torch.int32)

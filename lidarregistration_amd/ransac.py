@@ -71,16 +71,22 @@ def refit_dev(xyz0, xyz1, idx1, T, thr=0.6):
     return Tout.cpu().numpy().reshape(4, 4), int(n.item())
 
 
+def icp_launch(ws, xyz0, xyz1, T_ptr, stream, max_dist=0.6, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6):
+    """lr_icp of float32 device clouds from the transform at device pointer T_ptr (16 doubles: a tensor's, or the head of a
+    lr_pair_result), enqueued on `stream` (the current torch stream should be the same: the outputs are allocated on it).  Returns the
+    device tensors (T_icp [16] float64, lr_icp_result bytes); nothing is synchronised."""
+    T_icp = torch.empty(16, dtype=torch.float64, device=xyz0.device)
+    res = torch.empty(ctypes.sizeof(_ext.IcpResult), dtype=torch.uint8, device=xyz0.device)
+    _ext.check(_ext.lib().lr_icp(ws.handle, xyz0.data_ptr(), xyz0.shape[0], xyz1.data_ptr(), xyz1.shape[0], T_ptr, float(max_dist), int(max_iter),
+                                  float(rel_fitness), float(rel_rmse), T_icp.data_ptr(), res.data_ptr(), stream))
+    return T_icp, res
+
+
 def icp_dev(xyz0, xyz1, T_init, max_dist=0.6, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6):
     """Point-to-point ICP refinement (Experiments/test.py:183-189).  Returns (T 4x4 float64 numpy, info dict)."""
     xyz0, xyz1 = _f32(xyz0), _f32(xyz1)
-    ws = workspace(xyz0.shape[0], xyz1.shape[0])
     Tin = torch.as_tensor(np.ascontiguousarray(T_init, np.float64).reshape(16)).to(xyz0.device)
-    Tout = torch.empty(16, dtype=torch.float64, device=xyz0.device)
-    res = torch.zeros(ctypes.sizeof(_ext.IcpResult), dtype=torch.uint8, device=xyz0.device)
-    _ext.check(_ext.lib().lr_icp(ws.handle, xyz0.data_ptr(), xyz0.shape[0], xyz1.data_ptr(), xyz1.shape[0], Tin.data_ptr(),
-                                  float(max_dist), int(max_iter), float(rel_fitness), float(rel_rmse), Tout.data_ptr(), res.data_ptr(),
-                                  _stream()))
+    Tout, res = icp_launch(workspace(xyz0.shape[0], xyz1.shape[0]), xyz0, xyz1, Tin.data_ptr(), _stream(), max_dist, max_iter, rel_fitness, rel_rmse)
     r = _ext.IcpResult.from_buffer_copy(res.cpu().numpy().tobytes())
     return Tout.cpu().numpy().reshape(4, 4), dict(fitness=r.fitness, inlier_rmse=r.inlier_rmse, n_corr=r.n_corr, iterations=r.iterations)
 

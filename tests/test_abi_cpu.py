@@ -163,3 +163,16 @@ def test_the_scoring_contract_has_one_text():
         assert ("1048576" in text) == (name == "lr_contract.h"), f"{name}: the fixed-point scale belongs to lr_contract.h (LR_SCORE_SCALE) alone"
         assert "model_better" not in text, f"{name} still carries model_better"
         assert not re.search(r"__device__[^;{}()]*\bbetter\s*\(", text), f"{name} still defines a device-side better()"
+
+
+# lr_teaser_scratch_bytes / lr_sm_scratch_bytes at m = 0, 1, 63, 64, 65, 257, 4097, 32768, as the library returned them BEFORE the two back
+# ends got a shared front end (csrc/lr_corrset.h): constants read from that build, so that a moved align helper cannot shift an arena
+SCRATCH_M = (0, 1, 63, 64, 65, 257, 4097, 32768)
+SCRATCH_BYTES = {"lr_teaser_scratch_bytes": (12032, 12032, 12032, 12032, 26368, 87808, 7124736, 407650560),
+                 "lr_sm_scratch_bytes": (3328, 3328, 3328, 3328, 6912, 20736, 1231872, 2490624)}
+
+
+@pytest.mark.parametrize("fn", sorted(SCRATCH_BYTES))
+def test_corrset_scratch_sizes_unchanged(libpath, fn):
+    f = getattr(_ext.lib(), fn)
+    assert tuple(f(m) for m in SCRATCH_M) == SCRATCH_BYTES[fn]

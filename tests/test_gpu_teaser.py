@@ -204,6 +204,37 @@ def test_scratch_poisoning(T):
     assert np.array_equal(r0[0], r1[0]) and r0[1] == r1[1] and np.array_equal(r0[2], r1[2])
 
 
+def test_refusals_not_faults(T):
+    """A bad call is refused with its code before anything is launched, and a good call still works afterwards (the mirror of
+    test_gpu_sm.py's test).  m = 257: four full 64-bit words of bitset and a ragged fifth."""
+    import torch
+    from lidarregistration_amd import _ext
+    L = _ext.lib()
+    m = 257
+    a, b = tc.planted(m, 80, 5, noise=0.1)[:2]
+    A, B = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+    need = L.lr_teaser_scratch_bytes(m)
+    scratch = torch.zeros(need, dtype=torch.uint8, device="cuda")
+    res = torch.zeros(ctypes.sizeof(_ext.TeaserResult), dtype=torch.uint8, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+    EINVAL, ESIZE = -1, -4
+
+    def call(p, m=m, nbytes=need):
+        return L.lr_teaser(A.data_ptr(), B.data_ptr(), m, None, ctypes.byref(p), res.data_ptr(), None, scratch.data_ptr(), nbytes, st)
+    assert call(_ext.TeaserParams()) == 0
+    assert call(_ext.TeaserParams(), nbytes=need - 1) == ESIZE and b"scratch too small" in L.lr_last_error()
+    p = _ext.TeaserParams(); p.struct_size -= 4
+    assert call(p) == EINVAL and b"struct_size" in L.lr_last_error()
+    assert call(_ext.TeaserParams(), m=32769, nbytes=1 << 40) == ESIZE and b"32768" in L.lr_last_error()
+    L.lr_debug_fake_current_device(torch.cuda.current_device() + 1)          # (the hook only: no memory or stream of another device)
+    try:
+        assert call(_ext.TeaserParams()) == EINVAL and b"device" in L.lr_last_error()
+    finally:
+        L.lr_debug_fake_current_device(-1)
+    assert call(_ext.TeaserParams()) == 0
+    torch.cuda.synchronize()
+
+
 def _cli(args, cwd, env=None):
     e = dict(os.environ, **(env or {}))
     return subprocess.run([sys.executable, "-m", "test"] + args, cwd=cwd, env=e, capture_output=True, text=True, timeout=900)

@@ -46,3 +46,30 @@ def test_voxel_cell_limits_and_negative_floors(voxel):
 @pytest.mark.parametrize("name", list(ve.stride_clouds()))
 def test_voxel_compaction_strides(voxel, name):
     _held(voxel, ve.stride_clouds()[name])
+
+
+def test_voxel_wrong_device_is_refused(voxel):
+    """lr_voxel_dedup takes caller-owned scratch: with another device current it refuses (LR_EINVAL, before any launch) instead of
+    running its kernels on foreign pointers.  n == 0 takes no scratch and stays LR_OK.  The wrong device is the test hook's."""
+    import torch
+    from lidarregistration_amd import _ext
+    L = _ext.lib()
+    n = 1000
+    c = torch.from_numpy(np.random.default_rng(3).uniform(-40, 40, (n, 3))).cuda()
+    scratch = torch.empty(int(L.lr_voxel_dedup_scratch_bytes(n)), dtype=torch.uint8, device="cuda")
+    sel = torch.empty(n, dtype=torch.int32, device="cuda")
+    cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
+    st = torch.cuda.current_stream().cuda_stream
+
+    def call():
+        return L.lr_voxel_dedup(c.data_ptr(), n, sel.data_ptr(), cnt.data_ptr(), None, scratch.data_ptr(), scratch.numel(), st)
+    assert call() == 0
+    L.lr_debug_fake_current_device(torch.cuda.current_device() + 1)
+    try:
+        assert call() == -1 and b"device" in L.lr_last_error()
+        assert L.lr_voxel_dedup(None, 0, None, cnt.data_ptr(), None, None, L.lr_voxel_dedup_scratch_bytes(0), st) == 0      # (null scratch)
+    finally:
+        L.lr_debug_fake_current_device(-1)
+    assert int(cnt.item()) == 0
+    assert call() == 0
+    assert np.array_equal(sel[:int(cnt.item())].cpu().numpy(), ve.dedup_ref(c.cpu().numpy())[1])

@@ -7,7 +7,6 @@ compatibility evaluations per second (iterations * M^2 per pair), which DESIGN.m
     python tools/sm_bench.py [--batches 1,32] [--reps 5] [--sizes 2048,8192,16384]
 """
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -16,23 +15,18 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from lidarregistration_amd import _ext, sm  # noqa: E402
+from lidarregistration_amd import corrset, sm  # noqa: E402
 from teaser_bench import problem  # noqa: E402
 
 
 def run(m, batch, reps, device):
-    L = _ext.lib()
     probs = [problem(m, 1000 * m + k, device) for k in range(batch)]
-    scratch = torch.empty(L.lr_sm_scratch_bytes(m) * batch, dtype=torch.uint8, device=device)
-    res = torch.zeros(sm.RESULT_BYTES * batch, dtype=torch.uint8, device=device)
-    V = ctypes.c_void_p * batch
-    srcs, tgts = V(*[a.data_ptr() for a, _ in probs]), V(*[b.data_ptr() for _, b in probs])
-    ms = (ctypes.c_int32 * batch)(*[m] * batch)
-    p = sm.params()
+    bc = corrset.BatchCall(sm.SOLVER, [a for a, _ in probs], [b for _, b in probs], outputs=False)
+    p = bc.params
     st = torch.cuda.current_stream()
 
     def call():
-        _ext.check(L.lr_sm_batch(batch, srcs, tgts, ms, None, ctypes.byref(p), res.data_ptr(), None, None, scratch.data_ptr(), scratch.numel(), st.cuda_stream))
+        bc.launch(st.cuda_stream)
 
     call(); torch.cuda.synchronize()                          # warm-up
     times = []
@@ -40,7 +34,7 @@ def run(m, batch, reps, device):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(); call(); e1.record(); e1.synchronize()
         times.append(e0.elapsed_time(e1))
-    infos = [sm._info(sm._result(res, k)) for k in range(batch)]
+    infos = [info for _, info in bc.results()]
     ms_call = float(np.median(times))
     return dict(M=m, batch=batch, call_ms=ms_call, call_ms_min=float(min(times)), pairs_per_s=batch / (ms_call * 1e-3),
                 evals_per_s=batch * p.iterations * float(m) * m / (ms_call * 1e-3), ok=int(sum(i["status"] == 0 for i in infos)), K=infos[0]["K"])

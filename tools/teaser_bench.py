@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from lidarregistration_amd import _ext, teaser  # noqa: E402
+from lidarregistration_amd import _ext, corrset, teaser  # noqa: E402
 
 
 def problem(m, seed, device):
@@ -37,18 +37,11 @@ def problem(m, seed, device):
 def run(m, batch, reps, device):
     L = _ext.lib()
     probs = [problem(m, 1000 * m + k, device) for k in range(batch)]
-    per = L.lr_teaser_scratch_bytes(m)
-    scratch = torch.empty(per * batch, dtype=torch.uint8, device=device)
-    res = torch.zeros(teaser.RESULT_BYTES * batch, dtype=torch.uint8, device=device)
-    V = ctypes.c_void_p * batch
-    srcs, tgts = V(*[a.data_ptr() for a, _ in probs]), V(*[b.data_ptr() for _, b in probs])
-    ms = (ctypes.c_int32 * batch)(*[m] * batch)
-    p = teaser.params()
+    bc = corrset.BatchCall(teaser.SOLVER, [a for a, _ in probs], [b for _, b in probs], outputs=False)
     st = torch.cuda.current_stream()
 
     def call():
-        _ext.check(L.lr_teaser_batch(batch, srcs, tgts, ms, None, ctypes.byref(p), res.data_ptr(), None, scratch.data_ptr(),
-                                     scratch.numel(), st.cuda_stream))
+        bc.launch(st.cuda_stream)
 
     call(); torch.cuda.synchronize()                          # warm-up
     whole, stages = [], []
@@ -61,7 +54,7 @@ def run(m, batch, reps, device):
         check(L.lr_teaser_stage_times(out))
         stages.append(list(out))
     check(L.lr_teaser_timing(0))
-    infos = [teaser._info(teaser._result(res, k)) for k in range(batch)]
+    infos = [info for _, info in bc.results()]
     K = float(np.mean([i["K"] for i in infos])); n_rot = float(np.mean([i["n_rot_inliers"] for i in infos]))
     gnc = float(np.mean([i["gnc_iters"] for i in infos]))
     st_ms = np.median(np.array(stages), 0)
