@@ -410,6 +410,74 @@ LR_API int lr_sm_batch(int npairs, const float *const *src, const float *const *
                        const lr_sm_params *p, lr_sm_result *results, float *const *eig_out, uint8_t *const *labels_out, void *scratch,
                        size_t scratch_bytes, void *stream);
 
+/* ---- f5: voxel-grid down-sampling (one centroid per voxel) and the pair overlap measure -----------------------------------------
+ * lr_voxel_mean replaces Open3D's PointCloud.voxel_down_sample as the reference calls it (BalancedDatasetGenerator/
+ * GenerateBalancedSet.py:143-147 `downsample`; FCGF_FAST/net/refinement_tester.py:69-73) -- NOT lr_voxel_dedup, which is
+ * MinkowskiEngine's "keep the first point of a cell".  lr_overlap / lr_overlap_batch replace overlap_fraction and calc_GT_overlap
+ * (GenerateBalancedSet.py:155-205), the batch serving one source frame against many candidates (find_farthest_overlapping_partner,
+ * :321-371).  Contract (restated in tests/overlap_cpu.py).  All arithmetic is fp64, no fused multiply-add.  Items marked
+ * (recalled) come from memory of Open3D 0.13, which is neither vendored by the reference nor available to this project: unpinned.
+ *  C1 input: xyz [n,3] float64 on the device.  An optional T[16] (device, fp64, row-major) is applied first,
+ *     p_a = ((T[4a] x + T[4a+1] y) + T[4a+2] z) + T[4a+3] (the expression of lr_icp); T == NULL is the identity: no arithmetic is done
+ *     on the point.  Deviation: a point with a non-finite coordinate after the transform is dropped and counted (Open3D would carry
+ *     NaN into the bounds).
+ *  C2 cells (recalled: PointCloud::VoxelDownSample): lo_a = min of p_a over the kept points, vmb_a = lo_a - voxel * 0.5, cell
+ *     c_a = (int)floor((p_a - vmb_a) / voxel) -- a division, so c_a >= 0.  A cloud is refused with status 2 and no output unless
+ *     (hi_a - vmb_a) / voxel < 2^21 on every axis.
+ *  C3 output: one row per occupied cell, rows by ascending index of the cell's first point (scan order, like lr_voxel_dedup; Open3D's
+ *     order is that of an unordered_map, unspecified).  Per row: first = that index; count; centroid = the sum (from +0) of the cell's
+ *     points in ascending point index, left to right, per axis, then divided by (double)count -- the order in which Open3D's
+ *     AccumulatedPoint::AddPoint sees them (recalled).  The same bits on every run, whatever the scratch held; no floating-point atomics.
+ *  C4 overlap: A_ = C3(T A, voxel), B_ = C3(B, voxel); r = radius, or fl(sqrt 2) * voxel when radius == 0 (np.sqrt(2) * voxel_size,
+ *     in double on the host); n_overlap = #{ a in A_ : exists b in B_ with sqrt((dx dx + dy dy) + dz dz) < r }, strict, d = a - b per
+ *     axis, sqrt correctly rounded; frac = n_overlap / |A_|; frac_sym = min(frac, n_overlap / |B_|) -- the SAME A->B numerator in both,
+ *     the reference's own definition (GenerateBalancedSet.py:176-178).  |A_| == 0 or |B_| == 0: status 1, both fractions 0, n_overlap 0
+ *     (the reference divides by zero); a refused cloud (C2): status 2, likewise, and its n?_ds is 0.  Only existence within r is
+ *     asked, so the result does not depend on any order.
+ *  C5 refusals, all LR_EINVAL before any launch, lr_last_error naming the argument: wrong struct_size; voxel_size not positive and
+ *     finite; radius negative or not finite, or not 0 and outside voxel_size / 16 .. 4 voxel_size (one centroid per voxel bounds what
+ *     a search cell of edge r holds: 0.5 and 3 voxel are served, a radius far from the voxel size is not); n < 0 or n > 4194304;
+ *     npairs outside 1..64; null pointers where n > 0 (the scratch and the result / info block are always needed); short or
+ *     misaligned (256 bytes) scratch; scratch that is not memory of the current gfx950 device, or a stream of another device.
+ *     n == 0 is legal (status 1).                                                                                                   */
+typedef struct lr_overlap_params {
+    uint32_t struct_size;        /* = sizeof(lr_overlap_params), checked like lr_ransac_params.struct_size                          */
+    uint32_t reserved;           /* 0                                                                                               */
+    double   voxel_size;         /* 1.0 (GenerateBalancedSet.py:171)                                                                */
+    double   radius;             /* 0: fl(sqrt 2) * voxel_size (:175)                                                               */
+} lr_overlap_params;
+
+/* Written to device memory by lr_overlap / lr_overlap_batch (40 bytes). */
+typedef struct lr_overlap_result {
+    int32_t  status;             /* 0 ok, 1 = a down-sampled cloud is empty, 2 = a cloud exceeds 2^21 cells on an axis              */
+    int32_t  n0_ds, n1_ds;       /* |A_|, |B_|                                                                                      */
+    int32_t  n_overlap;
+    int32_t  n0_dropped, n1_dropped;     /* points with a non-finite coordinate                                                     */
+    double   frac, frac_sym;     /* overlap_frac, overlap_frac_symmetric (:177-178)                                                 */
+} lr_overlap_result;
+
+/* Caller-owned device scratch for a cloud of n points (0 when n is outside 0..4194304). */
+LR_API size_t lr_voxel_mean_scratch_bytes(int n);
+/* GenerateBalancedSet.py:143-147 / refinement_tester.py:69-73 (o3d voxel_down_sample), with the transform of :197 / :243 folded in.
+ * cent [n,3] float64, cent_f32 [n,3] float32 (the float32 rounding of cent: what lr_icp consumes), counts [n], first [n]: nullable,
+ * room for n rows, info[0] rows are written.  info: device int32[4] = { rows, dropped, status, 0 }; status 1 = no point kept,
+ * 2 = refused (C2): no row is written.  scratch: >= lr_voxel_mean_scratch_bytes(n), 256-byte aligned.  Asynchronous on `stream`.      */
+LR_API int lr_voxel_mean(const double *xyz, int n, const double *T, double voxel_size, double *cent, float *cent_f32,
+                         int32_t *counts, int32_t *first, int32_t *info, void *scratch, size_t scratch_bytes, void *stream);
+/* Scratch PER PAIR for clouds of up to max_n0 / max_n1 points (0 when either is outside 0..4194304). */
+LR_API size_t lr_overlap_scratch_bytes(int max_n0, int max_n1);
+/* GenerateBalancedSet.py:155-179 overlap_fraction (T == NULL) and :186-205 calc_GT_overlap (T = GT_mot, applied to cloud 0).
+ * result: device block.  scratch >= lr_overlap_scratch_bytes(n0, n1).                                                               */
+LR_API int lr_overlap(const double *xyz0, int n0, const double *xyz1, int n1, const double *T, const lr_overlap_params *p,
+                      lr_overlap_result *result, void *scratch, size_t scratch_bytes, void *stream);
+/* npairs (1..64) pairs in one sequence of launches (the pair and the cloud are grid dimensions) -- the candidate loop of
+ * GenerateBalancedSet.py:321-371.  xyz0/n0/xyz1/n1/T are HOST arrays of length npairs (T, and its entries, may be NULL), carried by
+ * value into a setup kernel (no copy, no host synchronisation: graph-capturable); results is a DEVICE array of npairs blocks; scratch
+ * >= npairs * lr_overlap_scratch_bytes(max n0, max n1).  The result of pair k is bit-identical to lr_overlap on that pair.          */
+LR_API int lr_overlap_batch(int npairs, const double *const *xyz0, const int32_t *n0, const double *const *xyz1, const int32_t *n1,
+                            const double *const *T, const lr_overlap_params *p, lr_overlap_result *results, void *scratch,
+                            size_t scratch_bytes, void *stream);
+
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */
 LR_API int lr_workspace_timing(lr_workspace *ws, int enable);

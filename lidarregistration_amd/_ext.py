@@ -22,6 +22,7 @@ SYMBOLS = [
     "lr_workspace_clock", "lr_debug_fake_current_device",
     "lr_teaser_scratch_bytes", "lr_teaser", "lr_teaser_batch", "lr_teaser_timing", "lr_teaser_stage_times",
     "lr_sm_scratch_bytes", "lr_sm", "lr_sm_batch",
+    "lr_voxel_mean_scratch_bytes", "lr_voxel_mean", "lr_overlap_scratch_bytes", "lr_overlap", "lr_overlap_batch",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -117,6 +118,22 @@ class SmResult(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("weight_sum", ctypes.c_double)]
 
 
+class OverlapParams(ctypes.Structure):
+    """lr_overlap_params with the reference's settings (GenerateBalancedSet.py:171,175) as defaults; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("voxel_size", ctypes.c_double), ("radius", ctypes.c_double)]
+    DEFAULTS = dict(voxel_size=1.0, radius=0.0)
+
+    def __init__(self, **kw):
+        kw.pop("struct_size", None)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
+
+
+class OverlapResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("n0_ds", ctypes.c_int32), ("n1_ds", ctypes.c_int32), ("n_overlap", ctypes.c_int32),
+                ("n0_dropped", ctypes.c_int32), ("n1_dropped", ctypes.c_int32), ("frac", ctypes.c_double), ("frac_sym", ctypes.c_double)]
+
+
+assert ctypes.sizeof(OverlapParams) == 24 and ctypes.sizeof(OverlapResult) == 40
 assert ctypes.sizeof(TeaserParams) == 72 and ctypes.sizeof(TeaserResult) == 176
 assert ctypes.sizeof(SmParams) == 24 and ctypes.sizeof(SmResult) == 152
 assert ctypes.sizeof(PairResult) == 496 and ctypes.sizeof(RansacParams) == 72 and ctypes.sizeof(PairParams) == 112
@@ -193,6 +210,14 @@ def lib():
         L.lr_sm_scratch_bytes.argtypes = [ci]
         L.lr_sm.argtypes = [vp, vp, ci, vp, ctypes.POINTER(SmParams), vp, vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_sm_batch.argtypes = [ci, pp, pp, ip, pp, ctypes.POINTER(SmParams), vp, pp, pp, vp, ctypes.c_size_t, vp]
+        dp = ctypes.c_double
+        L.lr_voxel_mean_scratch_bytes.restype = ctypes.c_size_t
+        L.lr_voxel_mean_scratch_bytes.argtypes = [ci]
+        L.lr_voxel_mean.argtypes = [vp, ci, vp, dp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.lr_overlap_scratch_bytes.restype = ctypes.c_size_t
+        L.lr_overlap_scratch_bytes.argtypes = [ci, ci]
+        L.lr_overlap.argtypes = [vp, ci, vp, ci, vp, ctypes.POINTER(OverlapParams), vp, vp, ctypes.c_size_t, vp]
+        L.lr_overlap_batch.argtypes = [ci, pp, ip, pp, ip, pp, ctypes.POINTER(OverlapParams), vp, vp, ctypes.c_size_t, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

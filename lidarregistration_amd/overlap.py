@@ -1,0 +1,152 @@
+"""Voxel-grid down-sampling (one centroid per voxel) and the pair overlap measure on the GPU: the cloud-level primitives of the
+reference's balanced-set generator (BalancedDatasetGenerator/GenerateBalancedSet.py) and of its refinement tester
+(FCGF_FAST/net/refinement_tester.py), on top of lr_voxel_mean / lr_overlap / lr_overlap_batch (csrc/lr_overlap.hip).
+
+Two different operations carry similar names here.  ``voxel_down_sample`` (this module) is Open3D's: every occupied voxel is replaced by
+the centroid of its points.  ``voxel.voxel_downsample`` is MinkowskiEngine's de-duplication: the first point of every cell is kept.
+The contract is stated in include/lidarreg.h and DESIGN.md §12; what of it is recalled from Open3D rather than pinned is marked there.
+No CPU fallback.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _ext
+from .matching import _device, _stream
+
+OVERLAP_VOXEL = 1.0         # GenerateBalancedSet.py:171
+MAX_PAIRS = 64              # pairs per lr_overlap_batch call
+
+
+def _f64(X, dev):
+    return torch.as_tensor(X).to(device=dev, dtype=torch.float64).contiguous().reshape(-1, 3)
+
+
+def _T_dev(T, dev):
+    return None if T is None else torch.as_tensor(np.ascontiguousarray(T, np.float64).reshape(16)).to(dev)
+
+
+def _scratch(nbytes, dev, poison):
+    s = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+    if poison is not None:
+        s.fill_(int(poison))
+    return s
+
+
+def voxel_mean_dev(X, voxel_size, T=None, poison=None):
+    """lr_voxel_mean of X [n,3] (evaluated in float64), optionally moved by T (4x4) first.  Returns a dict of device tensors trimmed to
+    the rows -- cent [rows,3] float64, cent_f32 [rows,3] float32, counts, first (int32) -- and rows, dropped, status (ints).
+    poison: fill the scratch with this byte first (test hook)."""
+    dev = _device()
+    x = _f64(X, dev)
+    n = int(x.shape[0])
+    L = _ext.lib()
+    Td = _T_dev(T, dev)
+    m = max(n, 1)
+    cent = torch.empty((m, 3), dtype=torch.float64, device=dev); cent32 = torch.empty((m, 3), dtype=torch.float32, device=dev)
+    counts = torch.empty(m, dtype=torch.int32, device=dev); first = torch.empty(m, dtype=torch.int32, device=dev)
+    info = torch.empty(4, dtype=torch.int32, device=dev)
+    scratch = _scratch(L.lr_voxel_mean_scratch_bytes(n), dev, poison)
+    _ext.check(L.lr_voxel_mean(x.data_ptr() if n else None, n, None if Td is None else Td.data_ptr(), float(voxel_size), cent.data_ptr(),
+                               cent32.data_ptr(), counts.data_ptr(), first.data_ptr(), info.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
+    rows, dropped, status, _ = (int(v) for v in info.cpu())
+    return dict(cent=cent[:rows], cent_f32=cent32[:rows], counts=counts[:rows], first=first[:rows], rows=rows, dropped=dropped, status=status)
+
+
+def voxel_down_sample(X, voxel_size, T=None, return_counts=False):
+    """Open3D's ``PointCloud.voxel_down_sample`` as GenerateBalancedSet.py:143-147 and refinement_tester.py:69-73 call it: the centroid of
+    every occupied voxel, float64 device tensor [rows,3], rows in scan order of each voxel's first point (Open3D's own row order is
+    unspecified).  T (4x4), if given, moves the cloud first.  Points with a non-finite coordinate are dropped.  Not to be confused with
+    ``voxel.voxel_downsample``, which keeps the first point of every cell (MinkowskiEngine)."""
+    r = voxel_mean_dev(X, voxel_size, T)
+    if r["status"] == 2:
+        raise _ext.LidarRegError("voxel_down_sample: the cloud spans 2^21 voxels or more on an axis")
+    return (r["cent"], r["counts"]) if return_counts else r["cent"]
+
+
+def _result(buf, k=0):
+    r = _ext.OverlapResult.from_buffer_copy(buf[k].cpu().numpy().tobytes())
+    return {name: getattr(r, name) for name, _ in _ext.OverlapResult._fields_}
+
+
+def overlap_dev(A, B, T=None, voxel_size=OVERLAP_VOXEL, radius=0.0, poison=None):
+    """lr_overlap on one pair: A [n0,3] (moved by T, 4x4, if given) against B [n1,3].  Returns the lr_overlap_result as a dict."""
+    dev = _device()
+    a, b = _f64(A, dev), _f64(B, dev)
+    n0, n1 = int(a.shape[0]), int(b.shape[0])
+    L = _ext.lib()
+    Td = _T_dev(T, dev)
+    p = _ext.OverlapParams(voxel_size=float(voxel_size), radius=float(radius))
+    res = torch.zeros((1, ctypes.sizeof(_ext.OverlapResult)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(L.lr_overlap_scratch_bytes(n0, n1), dev, poison)
+    _ext.check(L.lr_overlap(a.data_ptr() if n0 else None, n0, b.data_ptr() if n1 else None, n1, None if Td is None else Td.data_ptr(),
+                            ctypes.byref(p), res.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
+    return _result(res)
+
+
+def overlap_batch_dev(pairs, voxel_size=OVERLAP_VOXEL, radius=0.0, poison=None):
+    """ONE lr_overlap_batch call over `pairs`: a list of up to 64 (A, B) or (A, B, T) -- the candidate loop of
+    GenerateBalancedSet.py:321-371 (one source frame against many targets).  Returns the per-pair result dicts."""
+    dev = _device()
+    npairs = len(pairs)
+    L = _ext.lib()
+    As = [_f64(pr[0], dev) for pr in pairs]; Bs = [_f64(pr[1], dev) for pr in pairs]
+    Ts = [_T_dev(pr[2] if len(pr) > 2 else None, dev) for pr in pairs]
+    n0 = [int(a.shape[0]) for a in As]; n1 = [int(b.shape[0]) for b in Bs]
+    ptrs = lambda ts, ns: (ctypes.c_void_p * npairs)(*[t.data_ptr() if n else None for t, n in zip(ts, ns)])
+    tp = (ctypes.c_void_p * npairs)(*[None if t is None else t.data_ptr() for t in Ts])
+    p = _ext.OverlapParams(voxel_size=float(voxel_size), radius=float(radius))
+    res = torch.zeros((max(npairs, 1), ctypes.sizeof(_ext.OverlapResult)), dtype=torch.uint8, device=dev)
+    per = L.lr_overlap_scratch_bytes(max(n0, default=0), max(n1, default=0))
+    scratch = _scratch(per * npairs, dev, poison)
+    _ext.check(L.lr_overlap_batch(npairs, ptrs(As, n0), (ctypes.c_int32 * npairs)(*n0), ptrs(Bs, n1), (ctypes.c_int32 * npairs)(*n1), tp,
+                                  ctypes.byref(p), res.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
+    return [_result(res, k) for k in range(npairs)]
+
+
+def _fractions(r, who):
+    if r["status"] == 2:
+        raise _ext.LidarRegError(f"{who}: a cloud spans 2^21 voxels or more on an axis")
+    return r["frac"], r["frac_sym"]          # status 1 (an empty cloud): (0.0, 0.0), where the reference divides by zero
+
+
+def overlap_fraction(A, B, voxel_size=OVERLAP_VOXEL):
+    """GenerateBalancedSet.py:155-179: (overlap_frac, overlap_frac_symmetric) -- the share of A's voxels (after down-sampling both clouds at
+    `voxel_size`, 1 m there) with a voxel centre of B closer than sqrt(2) voxel, and the minimum of that and the same count over B's
+    voxels (the reference's own "symmetric": one numerator)."""
+    return _fractions(overlap_dev(A, B, None, voxel_size), "overlap_fraction")
+
+
+def calc_GT_overlap(A, B, GT_mot, return_both=False, overlap_measure="symmetric"):
+    """GenerateBalancedSet.py:186-205: the overlap of A moved by GT_mot with B.  return_both: both measures; otherwise the one
+    `overlap_measure` names ('src_to_tgt' | 'symmetric'; config.overlap_measure there)."""
+    frac, sym = _fractions(overlap_dev(A, B, GT_mot, OVERLAP_VOXEL), "calc_GT_overlap")
+    if return_both:
+        return frac, sym
+    assert overlap_measure in ("src_to_tgt", "symmetric"), "overlap_measure should be set to either 'src_to_tgt' or 'symmetric'"
+    return frac if overlap_measure == "src_to_tgt" else sym
+
+
+def refine_inputs(GT_mot_orig, A, B, downsample=True, voxel_size=0.3):
+    """What refine_motion hands to the ICP (GenerateBalancedSet.py:233-243): (a moved by GT_mot_orig, b) as float32 device clouds; the
+    down-sampling and the transform are float64."""
+    dev = _device()
+    a = voxel_down_sample(A, voxel_size) if downsample else _f64(A, dev)
+    b = voxel_down_sample(B, voxel_size) if downsample else _f64(B, dev)
+    M = np.ascontiguousarray(GT_mot_orig, np.float64)
+    x, y, z = a[:, 0], a[:, 1], a[:, 2]
+    a_corr = torch.stack([((float(M[r, 0]) * x + float(M[r, 1]) * y) + float(M[r, 2]) * z) + float(M[r, 3]) for r in range(3)], dim=1)
+    return a_corr.float().contiguous(), b.float().contiguous()
+
+
+def refine_motion(GT_mot_orig, A, B, downsample=True, voxel_size=0.3, refine_GT_Z_only=False):
+    """GenerateBalancedSet.py:220-246, the ICP branch: both clouds down-sampled (Open3D's voxel grid), `a` moved by GT_mot_orig, point-to-point
+    ICP from the identity with max distance 2 voxel_size and Open3D's default criteria (lr_icp), and icp_mot @ GT_mot_orig returned
+    (4x4 float64 numpy).  The Z-only variant (:257-) needs an unbounded nearest neighbour and is not built."""
+    if refine_GT_Z_only:
+        raise NotImplementedError("refine_motion: the Z-only refinement (refine_motion_Z_only) is not built")
+    from .ransac import icp_dev
+    a_corr, b = refine_inputs(GT_mot_orig, A, B, downsample, voxel_size)
+    icp_mot, _ = icp_dev(a_corr, b, np.eye(4), max_dist=2.0 * float(voxel_size))
+    return icp_mot @ np.ascontiguousarray(GT_mot_orig, np.float64)

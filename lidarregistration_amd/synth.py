@@ -111,3 +111,30 @@ def make_pair_dev(N=30000, D=32, rho=0.5, s=1.2, seed=51, device=None, noise=0.0
     xyz1[order1[:k]] = xyz0[src_rows] @ Tt[:3, :3].T + Tt[:3, 3] + noise * torch.randn((k, 3), generator=g, device=device)
     xyz1[order1[k:]] = box(N - k)
     return dict(xyz0=xyz0.contiguous(), xyz1=xyz1.contiguous(), feats0=F0.contiguous(), feats1=F1.contiguous(), T_gt=T)
+
+
+def make_scan_pair(n0=120000, n1=None, seed=51, forward=8.0, yaw_deg=5.0, reach=80.0):
+    """Two raw LiDAR-like frames (float64, like the reference's cloud cache) of one scene seen from two poses `forward` metres and `yaw_deg`
+    apart, and the 4x4 motion frame 0 -> frame 1: range-dependent density (most returns near the sensor), a rolling ground, facades on a
+    7 m street grid.  What the overlap measure and the Open3D-style down-sampling are timed on (tools/overlap_bench.py)."""
+    n1 = n0 if n1 is None else n1
+    rng = np.random.default_rng(seed)
+    a = np.radians(yaw_deg)
+    T = np.eye(4)
+    T[:3, :3] = [[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]]
+    T[:3, 3] = [-forward, 0.3, 0.0]
+
+    def frame(n, pose):
+        r = reach * rng.uniform(size=n) ** 2 + 1.5                       # density falls with range
+        phi = rng.uniform(0, 2 * np.pi, size=n)
+        local = np.stack([r * np.cos(phi), r * np.sin(phi), np.zeros(n)], axis=1)
+        world = (local - pose[:3, 3]) @ pose[:3, :3]                      # inverse of `pose`: scene coordinates of the returns
+        x, y = world[:, 0], world[:, 1]
+        z = 0.3 * np.sin(0.2 * x) * np.cos(0.15 * y) - 1.7
+        wall = rng.uniform(size=n) < 0.35
+        z = np.where(wall, z + rng.uniform(0, 6, size=n), z)
+        x = np.where(wall, np.round(x / 7.0) * 7.0, x)
+        world = np.stack([x, y, z], axis=1) + rng.normal(scale=0.02, size=(n, 3))
+        return world @ pose[:3, :3].T + pose[:3, 3]
+
+    return frame(n0, np.eye(4)), frame(n1, T), T
