@@ -5,23 +5,17 @@
 // matrices + coalesce sort), nn_to_mutual :222-239, mark_best_buddies :207-220,
 // calc_distance_ratio_in_feature_space :89-98 and Grid_Prioritized_Filter :100-205 (200 Python
 // iterations of N-length numpy masks + per-cell argsort).  Everything here is index/compare work on
-// <= N0 elements: HBM/latency-bound, a handful of small launches, no host round trips.
+// <= N0 elements: HBM/latency-bound, a handful of small launches, no host round trips.  The wave scan and the two
+// ordered-compaction steps are the shared ones of lr_prims.h.
 #include "lr_internal.h"
+#include "lr_prims.h"
 #include <math.h>
 
 #define LR_INF __builtin_huge_valf()
 
 // ------------------------------------------------------------------ ordered compaction
-// Two small launches instead of a scan: (1) flags + per-block (256 elements) counts, (2) every block sums the
-// counts of the blocks before it (<= n/256 values, one coalesced read) and scatters its survivors in order.
-__device__ __forceinline__ void block_count(bool k, int32_t *__restrict__ blk_cnt)
-{
-    __shared__ int s_wave[4];
-    const unsigned long long bal = __ballot(k);
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-}
+// Two small launches instead of a scan: (1) flags + per-block (256 elements) counts (lr_block_count), (2) every block sums the
+// counts of the blocks before it and scatters its survivors in order (lr_ordered_slot); both live in lr_prims.h.
 
 // keep[i] = rev[idx1[i]] == i  (torch_intersect, matching.py:67-87, reduced to its gather-compare core)
 __global__ void __launch_bounds__(256)
@@ -33,7 +27,7 @@ mutual_flag_kernel(int n0, const int32_t *__restrict__ idx1, const int32_t *__re
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool k = i < n0 && rev[idx1[i]] == i;
     if (i < n0) is_bb[i] = k ? 1 : 0;
-    block_count(k, blk_cnt);
+    lr_block_count(k, blk_cnt);
 }
 
 __global__ void __launch_bounds__(256)
@@ -43,7 +37,7 @@ count_flags_kernel(int n0, const int32_t *__restrict__ m_dev, const uint8_t *__r
     lr_z(m_dev, z, blockIdx.z); lr_z(flags, z, blockIdx.z); lr_z(blk_cnt, z, blockIdx.z);
     if (m_dev) n0 = min(n0, *m_dev);
     const int i = blockIdx.x * 256 + threadIdx.x;
-    block_count(i < n0 && flags[i] != 0, blk_cnt);
+    lr_block_count(i < n0 && flags[i] != 0, blk_cnt);
 }
 
 // survivors in ascending i == torch coalesce order (matching.py:80-85) / boolean-mask order (matching.py:197-199)
@@ -60,20 +54,10 @@ compact_kernel(int n0, const uint8_t *__restrict__ flags, const int32_t *__restr
     if (z.descs) { const lr_pair_desc d = z.descs[blockIdx.z]; n0 = d.n0; if (xyz0) { xyz0 = d.xyz0; xyz1 = d.xyz1; } }
     lr_z(flags, z, blockIdx.z); lr_z(blk_cnt, z, blockIdx.z); lr_z(idx1, z, blockIdx.z); lr_z(idx2, z, blockIdx.z); lr_z(score, z, blockIdx.z); lr_z(o0, z, blockIdx.z); lr_z(o1, z, blockIdx.z); lr_z(o2, z, blockIdx.z); lr_z(oscore, z, blockIdx.z); lr_z(n_out, z, blockIdx.z); lr_z(n_out2, z, blockIdx.z); lr_z(corr8, z, blockIdx.z); lr_z(counters, z, blockIdx.z); lr_z(m_dev, z, blockIdx.z); lr_z(src0, z, blockIdx.z);
     if (m_dev) n0 = min(n0, *m_dev);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int c = 0;
-    for (int b = tid; b < (int)blockIdx.x; b += 256) c += blk_cnt[b];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-    const int i = blockIdx.x * 256 + tid;
+    const int tid = threadIdx.x, before = lr_blocks_before(blk_cnt), i = blockIdx.x * 256 + tid;
     const bool k = i < n0 && flags[i] != 0;
-    const unsigned long long bal = __ballot(k);
-    if (lane == 0) { s_part[wave] = c; s_wave[wave] = __popcll(bal); }
-    __syncthreads();
-    const int prefix = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-    int woff = 0;
-    for (int w = 0; w < wave; ++w) woff += s_wave[w];
-    const int slot = prefix + woff + __popcll(bal & ((1ull << lane) - 1ull));
+    int prefix;
+    const int slot = lr_ordered_slot(k, before, s_wave, s_part, prefix);
     if (k) {
         if (o0) o0[slot] = src0 ? src0[i] : i;
         if (o1) o1[slot] = idx1[i];
@@ -219,9 +203,7 @@ prosac_scan_kernel(const float *__restrict__ q, int m_max, const int32_t *__rest
     int v[LR_PR_BUCKETS / 1024], sum = 0;
 #pragma unroll
     for (int k = 0; k < LR_PR_BUCKETS / 1024; ++k) { v[k] = s_h[threadIdx.x * (LR_PR_BUCKETS / 1024) + k]; sum += v[k]; }
-    int inc = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
+    const int inc = lr_wave_incl_scan(sum, lane);
     if (lane == 63) s_w[wave] = inc;
     __syncthreads();
     int run = inc - sum;

@@ -10,9 +10,11 @@
 // Each iteration is ONE launch: every thread finds the exact nearest target of its source point in the 27 surrounding
 // cells (fp64), the block reduces the fp64 moments of its pairs, and the last block to finish (agent-scope release /
 // acquire around a ticket counter) sums the partials in fixed order, solves Kabsch, composes the transform and decides
-// convergence.  Later launches of a converged pair return at their first instruction.
+// convergence.  Later launches of a converged pair return at their first instruction.  The wave scan under the bucket
+// offsets is the shared one of lr_prims.h.
 #include "lr_internal.h"
 #include "lr_contract.h"
+#include "lr_prims.h"
 #include <math.h>
 
 #define LR_ICP_NB 32768          // hash buckets (power of two)
@@ -51,9 +53,7 @@ icp_scan_kernel(const int32_t *__restrict__ hist, int32_t *__restrict__ start, l
     for (int k = 0; k < PER; ++k) { local[k] = sum; sum += hist[threadIdx.x * PER + k]; }
     // block-wide exclusive scan of `sum`
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { int t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+    const int incl = lr_wave_incl_scan(sum, lane);
     if (lane == 63) s_w[wave] = incl;
     __syncthreads();
     int woff = 0;

@@ -9,8 +9,8 @@
 // index; each pair owns an arena of the caller's scratch, `stride` bytes apart, headed by the control blocks of its clouds.  Per cloud:
 //   1. transform (fp64, the expression of icp_iter_kernel), finite test, per-axis min / max (integer atomics on an order-preserving
 //      image of the doubles: exact under any order);
-//   2. cell key 3 x 21 bits into an open-addressing table; the slot keeps the smallest point index (atomicMin) and the count (integer
-//      atomicAdd): neither depends on the order the threads run in;
+//   2. cell key 3 x 21 bits into the open-addressing table of lr_cells.h; the slot keeps the smallest point index (atomicMin) and the
+//      count (integer atomicAdd): neither depends on the order the threads run in;
 //   3. flag + ordered compaction: output row of every cell = rank of its first point; first, count;
 //   4. a STABLE cell-major ordering of the point indices: LSD radix sort on the row, 8-bit digits, per-block digit histograms, in-block
 //      ranks from ordered ballots;
@@ -19,12 +19,14 @@
 // The overlap: the target's centroids are bucketed into a hashed grid of cell ~ r (counting sort; order inside a bucket is irrelevant:
 // only existence within r is asked), every source centroid tests the 27 surrounding buckets, counts through integer atomics.
 // No floating-point atomic anywhere; every word a kernel reads has been written by a kernel of the same call (scratch contents are irrelevant).
+// The table, the hash, the compaction steps and the block scan are the shared ones (lr_cells.h, lr_prims.h); this file owns the cell rule
+// -- the floor of (p - vmb) / voxel -- and its kernels over the pairs' arenas (cs_ptr).
 #include "lr_corrset.h"
+#include "lr_cells.h"
 #include <math.h>
 #include <string.h>
 
 #define OV_MAX_N 4194304             // points per cloud (2^22)
-#define OV_EMPTY 0xffffffffffffffffull
 #define OV_CELLS 2097152.0           // 2^21 cells per axis
 #define OV_NOKEY 0x00ffffff          // sort key of a dropped point: behind every row (rows <= n < 2^(8 passes))
 #define OV_LIGHT 32                  // segments up to this long are summed by their own lane
@@ -61,12 +63,6 @@ struct ov_args {
     double voxel, r, g;                  // g: edge of the search grid's cells
 };
 
-static size_t ov_capacity(size_t n)
-{
-    size_t c = 1024;
-    while (c < 2 * (n > 0 ? n : 1)) c <<= 1;
-    return c;
-}
 static size_t ov_buckets(size_t n)
 {
     size_t c = 1024;
@@ -76,7 +72,7 @@ static size_t ov_buckets(size_t n)
 // arena of one cloud of up to n points, from byte `o`
 static ov_layout ov_make_layout(size_t o, size_t n)
 {
-    const size_t nn = n > 0 ? n : 1, cap = ov_capacity(n), nb = (nn + 255) / 256;
+    const size_t nn = n > 0 ? n : 1, cap = lr_cells_capacity(n), nb = (nn + 255) / 256;
     ov_layout L;
     L.P = o;        o += cs_al(nn * 24);
     L.slot_of = o;  o += cs_al(nn * 4);
@@ -125,11 +121,6 @@ __device__ __forceinline__ double ov_dec(unsigned long long e)
 {
     return __longlong_as_double((long long)((e >> 63) ? (e & 0x7fffffffffffffffull) : ~e));
 }
-__device__ __forceinline__ unsigned ov_hash(unsigned long long k)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned)k;
-}
 
 // ---- setup: descriptors by value -> control blocks (no host copy, graph-capturable) ------------------------------------------
 __global__ void ov_setup_kernel(ov_desc_table t, ov_args g, int npairs)
@@ -147,9 +138,7 @@ __global__ void ov_setup_kernel(ov_desc_table t, ov_args g, int npairs)
     for (int q = 0; q < 12; ++q) c->T[q] = c->has_T ? d.T[q] : (q % 5 == 0 ? 1.0 : 0.0);
     for (int a = 0; a < 3; ++a) { c->lo[a] = ~0ull; c->hi[a] = 0ull; c->vmb[a] = 0.0; }
     c->dropped = 0; c->status = 0; c->rows = 0; c->n_overlap = 0;
-    unsigned cap = 1024;
-    while (cap < 2u * (unsigned)(c->n > 0 ? c->n : 1)) cap <<= 1;
-    c->cap_mask = cap - 1;
+    c->cap_mask = (uint32_t)(lr_cells_capacity((size_t)c->n) - 1);
 }
 
 // table and bucket words the later kernels accumulate into
@@ -160,7 +149,7 @@ __global__ void __launch_bounds__(256) ov_init_kernel(ov_args g)
     const size_t cap = c->n > 0 ? (size_t)c->cap_mask + 1 : 0;
     unsigned long long *keys = cs_ptr<unsigned long long>(g, pair, g.L[cl].keys);
     int32_t *first = cs_ptr<int32_t>(g, pair, g.L[cl].first), *cnt = cs_ptr<int32_t>(g, pair, g.L[cl].cnt);
-    for (size_t s = (size_t)blockIdx.x * 256 + threadIdx.x; s < cap; s += (size_t)gridDim.x * 256) { keys[s] = OV_EMPTY; first[s] = 0x7fffffff; cnt[s] = 0; }
+    for (size_t s = (size_t)blockIdx.x * 256 + threadIdx.x; s < cap; s += (size_t)gridDim.x * 256) { keys[s] = LR_CELL_EMPTY; first[s] = 0x7fffffff; cnt[s] = 0; }
     if (cl == 1) {
         int32_t *bc = cs_ptr<int32_t>(g, pair, g.bk_cnt), *bf = cs_ptr<int32_t>(g, pair, g.bk_fill);
         for (size_t s = (size_t)blockIdx.x * 256 + threadIdx.x; s <= g.bk_mask; s += (size_t)gridDim.x * 256) { bc[s] = 0; bf[s] = 0; }
@@ -234,20 +223,11 @@ __global__ void __launch_bounds__(256) ov_insert_kernel(ov_args g)
     int32_t *slot_of = cs_ptr<int32_t>(g, pair, g.L[cl].slot_of);
     if (slot_of[i] < 0) return;                      // dropped
     const double *P = cs_ptr<double>(g, pair, g.L[cl].P);
-    unsigned long long key = 0;
+    unsigned long long ca[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const int ca = (int)floor((P[3 * (size_t)i + a] - c->vmb[a]) / g.voxel);     // 0 <= ca < 2^21 (ov_bounds_kernel)
-        key = (key << 21) | (unsigned long long)(ca & 0x1fffff);
-    }
-    unsigned long long *keys = cs_ptr<unsigned long long>(g, pair, g.L[cl].keys);
-    const unsigned mask = c->cap_mask;
-    unsigned s = ov_hash(key) & mask;
-    for (;;) {                                       // at most n of the >= 2 n slots are ever taken: an empty one is met
-        const unsigned long long prev = atomicCAS(&keys[s], OV_EMPTY, key);
-        if (prev == OV_EMPTY || prev == key) break;
-        s = (s + 1) & mask;
-    }
+    for (int a = 0; a < 3; ++a)                      // 0 <= cell < 2^21 (ov_bounds_kernel)
+        ca[a] = (unsigned long long)((int)floor((P[3 * (size_t)i + a] - c->vmb[a]) / g.voxel) & 0x1fffff);
+    const unsigned s = lr_cells_claim(cs_ptr<unsigned long long>(g, pair, g.L[cl].keys), c->cap_mask, lr_cells_pack(ca[0], ca[1], ca[2]));
     atomicMin(&cs_ptr<int32_t>(g, pair, g.L[cl].first)[s], i);
     atomicAdd(&cs_ptr<int32_t>(g, pair, g.L[cl].cnt)[s], 1);
     slot_of[i] = (int32_t)s;
@@ -257,23 +237,16 @@ __global__ void __launch_bounds__(256) ov_insert_kernel(ov_args g)
 __device__ __forceinline__ bool ov_is_first(const ov_args &g, int pair, int cl, int i, int n, int &slot)
 {
     slot = -1;
-    if (i >= n) return false;
-    slot = cs_ptr<int32_t>(g, pair, g.L[cl].slot_of)[i];
-    return slot >= 0 && cs_ptr<int32_t>(g, pair, g.L[cl].first)[slot] == i;
+    return i < n && lr_cells_is_first(cs_ptr<int32_t>(g, pair, g.L[cl].first), cs_ptr<int32_t>(g, pair, g.L[cl].slot_of), i, slot);
 }
 
 __global__ void __launch_bounds__(256) ov_flag_kernel(ov_args g)
 {
-    __shared__ int s_w[4];
     const int pair = blockIdx.z, cl = blockIdx.y;
     const int n = ov_ctl(g, pair, cl)->n_live;
     if ((int)blockIdx.x * 256 >= n) return;
     int slot;
-    const bool k = ov_is_first(g, pair, cl, blockIdx.x * 256 + threadIdx.x, n, slot);
-    const unsigned long long bal = __ballot(k);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) cs_ptr<int32_t>(g, pair, g.L[cl].blk)[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    lr_block_count(ov_is_first(g, pair, cl, blockIdx.x * 256 + threadIdx.x, n, slot), cs_ptr<int32_t>(g, pair, g.L[cl].blk));
 }
 
 __global__ void __launch_bounds__(256) ov_compact_kernel(ov_args g)
@@ -283,28 +256,16 @@ __global__ void __launch_bounds__(256) ov_compact_kernel(ov_args g)
     ov_cloud *c = ov_ctl(g, pair, cl);
     const int n = c->n_live;
     if ((int)blockIdx.x * 256 >= n) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int32_t *blk = cs_ptr<int32_t>(g, pair, g.L[cl].blk);
-    int pre = 0;
-    for (int b = tid; b < (int)blockIdx.x; b += 256) pre += blk[b];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) pre += __shfl_xor(pre, m);
-    const int i = blockIdx.x * 256 + tid;
-    int slot;
+    const int before = lr_blocks_before(cs_ptr<int32_t>(g, pair, g.L[cl].blk)), i = blockIdx.x * 256 + threadIdx.x;
+    int slot, prefix;
     const bool k = ov_is_first(g, pair, cl, i, n, slot);
-    const unsigned long long bal = __ballot(k);
-    if (lane == 0) { s_p[wave] = pre; s_w[wave] = __popcll(bal); }
-    __syncthreads();
-    const int prefix = s_p[0] + s_p[1] + s_p[2] + s_p[3];
-    int woff = 0;
-    for (int w = 0; w < wave; ++w) woff += s_w[w];
-    const int row = prefix + woff + __popcll(bal & ((1ull << lane) - 1ull));
+    const int row = lr_ordered_slot(k, before, s_w, s_p, prefix);
     if (k) {
         cs_ptr<int32_t>(g, pair, g.L[cl].rowof)[slot] = row;
         cs_ptr<int32_t>(g, pair, g.L[cl].firstrow)[row] = i;
         cs_ptr<int32_t>(g, pair, g.L[cl].counts)[row] = cs_ptr<int32_t>(g, pair, g.L[cl].cnt)[slot];
     }
-    if ((int)blockIdx.x == (n - 1) / 256 && tid == 0) c->rows = prefix + s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    if ((int)blockIdx.x == (n - 1) / 256 && threadIdx.x == 0) c->rows = prefix + s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
 
 // ---- 4. stable LSD radix sort of the point indices on their row ----------------------------------------------------------------
@@ -358,39 +319,11 @@ __global__ void __launch_bounds__(256) ov_sort_hist_kernel(ov_args g, int pass)
     cs_ptr<int32_t>(g, pair, g.L[cl].hist)[(size_t)d * nb + blockIdx.x] = (s_cnt[d] + s_cnt[256 + d]) + (s_cnt[512 + d] + s_cnt[768 + d]);
 }
 
-// exclusive scan of a[0..len) in place by one block of 1024 threads, 4096 entries per round
-__device__ void ov_block_exscan(int32_t *a, size_t len)
-{
-    __shared__ int s_w[16];
-    __shared__ int s_carry;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) s_carry = 0;
-    __syncthreads();
-    for (size_t base = 0; base < len; base += 4096) {
-        int v[4], sum = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const size_t t = base + 4 * (size_t)tid + k; v[k] = t < len ? a[t] : 0; sum += v[k]; }
-        int incl = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const int u = __shfl_up(incl, d); if (lane >= d) incl += u; }
-        if (lane == 63) s_w[wave] = incl;
-        __syncthreads();
-        int run = s_carry;
-        for (int w = 0; w < wave; ++w) run += s_w[w];
-        run += incl - sum;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const size_t t = base + 4 * (size_t)tid + k; if (t < len) a[t] = run; run += v[k]; }
-        __syncthreads();
-        if (tid == 1023) s_carry = run;
-        __syncthreads();
-    }
-}
-
 __global__ void __launch_bounds__(1024) ov_sort_scan_kernel(ov_args g)
 {
     const int pair = blockIdx.z, cl = blockIdx.y;
     const int n = ov_ctl(g, pair, cl)->n_live;
-    ov_block_exscan(cs_ptr<int32_t>(g, pair, g.L[cl].hist), (size_t)256 * ((n + 255) / 256));
+    lr_block_exscan(cs_ptr<int32_t>(g, pair, g.L[cl].hist), (size_t)256 * ((n + 255) / 256));
 }
 
 __global__ void __launch_bounds__(256) ov_sort_scatter_kernel(ov_args g, int pass)
@@ -493,7 +426,7 @@ __device__ __forceinline__ void ov_qcell(const double *p, const double *o, doubl
 }
 __device__ __forceinline__ uint32_t ov_bucket(long long x, long long y, long long z, uint32_t mask)
 {
-    return ov_hash((unsigned long long)x * 73856093ull ^ (unsigned long long)y * 19349663ull ^ (unsigned long long)z * 83492791ull) & mask;
+    return (uint32_t)lr_mix64((unsigned long long)x * 73856093ull ^ (unsigned long long)y * 19349663ull ^ (unsigned long long)z * 83492791ull) & mask;
 }
 
 __global__ void __launch_bounds__(256) ov_bhist_kernel(ov_args g)
@@ -510,7 +443,7 @@ __global__ void __launch_bounds__(256) ov_bhist_kernel(ov_args g)
 __global__ void __launch_bounds__(1024) ov_bscan_kernel(ov_args g)
 {
     if (ov_ctl(g, blockIdx.z, 1)->rows == 0) return;
-    ov_block_exscan(cs_ptr<int32_t>(g, blockIdx.z, g.bk_cnt), (size_t)g.bk_mask + 1);
+    lr_block_exscan(cs_ptr<int32_t>(g, blockIdx.z, g.bk_cnt), (size_t)g.bk_mask + 1);
 }
 
 __global__ void __launch_bounds__(256) ov_bscatter_kernel(ov_args g)

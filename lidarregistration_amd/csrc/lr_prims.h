@@ -1,0 +1,91 @@
+// The integer building blocks the cloud-level kernels share (lr_filter.hip, lr_icp.hip, lr_voxel.hip, lr_overlap.hip, lr_sm.hip,
+// lr_teaser.hip; not part of the ABI): wave and block scans, flag counting and ordered compaction, the 64-bit mix hash.  Device only,
+// inlined, no state; a wave is 64 lanes.  lr_nn16.hip and lr_ransac.hip keep their own spellings: the helper re-schedules their kernels.
+#pragma once
+#include <hip/hip_runtime.h>
+
+// inclusive scan of v over the wave, lane = this thread's lane (int, long long)
+template <typename T> __device__ __forceinline__ T lr_wave_incl_scan(T v, int lane)
+{
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const T o = __shfl_up(v, d); if (lane >= d) v += o; }
+    return v;
+}
+
+// Flag + ordered compaction in blocks of 256, two small launches instead of a scan: (1) flags + per-block counts, (2) every block sums
+// the counts of the blocks before it (<= n/256 values, one coalesced read) and scatters its survivors in order.
+// (1) blk_cnt[blockIdx.x] = flags set in this block
+__device__ __forceinline__ void lr_block_count(bool flag, int32_t *__restrict__ blk_cnt)
+{
+    __shared__ int s_wave[4];
+    const unsigned long long bal = __ballot(flag);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+}
+// (2) this wave's share of the flags set in the blocks before this one (taken before the caller loads its flag), then this thread's output
+// position in ascending-index order across the grid's x dimension (meaningful where flag is set); prefix = flags set in the blocks before
+// this one.  s_w, s_p: four LDS words each, the caller's; s_w keeps the waves' counts of this block (prefix + their sum = the grand total).
+__device__ __forceinline__ int lr_blocks_before(const int32_t *__restrict__ blk_cnt)
+{
+    int c = 0;
+    for (int b = threadIdx.x; b < (int)blockIdx.x; b += 256) c += blk_cnt[b];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+    return c;
+}
+__device__ __forceinline__ int lr_ordered_slot(bool flag, int before, int *s_w, int *s_p, int &prefix)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long bal = __ballot(flag);
+    if (lane == 0) { s_p[wave] = before; s_w[wave] = __popcll(bal); }
+    __syncthreads();
+    prefix = s_p[0] + s_p[1] + s_p[2] + s_p[3];
+    int woff = 0;
+    for (int w = 0; w < wave; ++w) woff += s_w[w];
+    return prefix + woff + __popcll(bal & ((1ull << lane) - 1ull));
+}
+// exclusive prefix of a flag over a block of NT threads in thread order, and the block's total; s_cnt: NT / 64 LDS words, the caller's
+template <int NT> __device__ __forceinline__ int lr_block_rank(bool flag, int *s_cnt, int &total)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long bal = __ballot(flag);
+    __syncthreads();
+    if (lane == 0) s_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    int off = 0, tot = 0;
+    for (int w = 0; w < NT / 64; ++w) { const int n = s_cnt[w]; off += w < wave ? n : 0; tot += n; }
+    total = tot;
+    return off + __popcll(bal & ((1ull << lane) - 1ull));
+}
+// exclusive scan of a[0..len) in place by one block of 1024 threads, 4096 entries per round
+__device__ __forceinline__ void lr_block_exscan(int32_t *a, size_t len)
+{
+    __shared__ int s_w[16];
+    __shared__ int s_carry;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid == 0) s_carry = 0;
+    __syncthreads();
+    for (size_t base = 0; base < len; base += 4096) {
+        int v[4], sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const size_t t = base + 4 * (size_t)tid + k; v[k] = t < len ? a[t] : 0; sum += v[k]; }
+        const int incl = lr_wave_incl_scan(sum, lane);
+        if (lane == 63) s_w[wave] = incl;
+        __syncthreads();
+        int run = s_carry;
+        for (int w = 0; w < wave; ++w) run += s_w[w];
+        run += incl - sum;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const size_t t = base + 4 * (size_t)tid + k; if (t < len) a[t] = run; run += v[k]; }
+        __syncthreads();
+        if (tid == 1023) s_carry = run;
+        __syncthreads();
+    }
+}
+// 64-bit finaliser mix (MurmurHash3's fmix64): every input bit reaches every output bit
+__device__ __forceinline__ unsigned long long lr_mix64(unsigned long long k)
+{
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
+    return k ^ (k >> 33);
+}

@@ -16,11 +16,13 @@
 //   sm_norm_kernel     one block per pair: row sums over the chunks (ascending, fp64), the norm by a fixed-order tree, v back into the
 //                      records
 //   sm_select_kernel   one block per pair: the K-th largest v by four radix passes over the float bits (v >= 0: integer order is float
-//                      order), ties at the cut by ascending index; labels and the ascending index list
+//                      order), ties at the cut by ascending index; labels and the ascending index list (in-block ranks: lr_block_rank
+//                      of lr_prims.h, the header of the integer steps the cloud-level kernels share)
 //   sm_fit_kernel      one block per pair: weighted fp64 centroids and covariance in a fixed order, Horn's solver of lr_contract.h
 // No floating-point atomics anywhere: every sum has one order, which depends on the pair's own M (and the device's compute-unit count)
 // only -- never on the batch the pair is in, on scheduling or on what the scratch held.
 #include "lr_corrset.h"
+#include "lr_prims.h"
 #include "lr_contract.h"
 #include <math.h>
 
@@ -247,20 +249,6 @@ __global__ void __launch_bounds__(SM_NB) sm_norm_kernel(sm_args g, int last)
 }
 
 // ---- selection --------------------------------------------------------------------------------------------------------------------
-// exclusive prefix of a flag over the block in thread order, and the block's total
-__device__ __forceinline__ int sm_block_prefix(bool f, int *s_cnt, int &total)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const unsigned long long bal = __ballot(f);
-    __syncthreads();
-    if (lane == 0) s_cnt[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int w = 0; w < SM_NB / 64; ++w) { const int n = s_cnt[w]; off += w < wave ? n : 0; tot += n; }
-    total = tot;
-    return off + __popcll(bal & ((1ull << lane) - 1ull));
-}
-
 __global__ void __launch_bounds__(SM_NB) sm_select_kernel(sm_args g)
 {
     __shared__ int s_hist[256];
@@ -304,9 +292,9 @@ __global__ void __launch_bounds__(SM_NB) sm_select_kernel(sm_args g)
         const uint32_t bits = live ? rec[(size_t)i * 8 + 6] : 0u;
         const bool eq = live && bits == prefix, gt = live && bits > prefix;
         int tot_eq, tot_sel;
-        const int rank = n_eq + sm_block_prefix(eq, s_cnt, tot_eq);
+        const int rank = n_eq + lr_block_rank<SM_NB>(eq, s_cnt, tot_eq);
         const bool take = gt || (eq && rank < need);
-        const int pos = n_sel + sm_block_prefix(take, s_cnt, tot_sel);
+        const int pos = n_sel + lr_block_rank<SM_NB>(take, s_cnt, tot_sel);
         if (take) sel[pos] = i;
         if (i < mh) {
             if (labels) labels[i] = take ? 1 : 0;

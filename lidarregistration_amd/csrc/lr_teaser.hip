@@ -11,13 +11,15 @@
 //                                      of the vertices adjacent to all others of that set (they join the clique).
 //                 tz_compact_kernel    adjacency of what is left, re-indexed compactly.
 //                 tz_search_kernel     one wave per pair: bitset branch and bound with a greedy-colouring bound, explicit stack in
-//                                      scratch, bounded by a node budget and a device-clock budget; writes the clique in ascending order.
+//                                      scratch, bounded by a node budget and a device-clock budget; writes the clique in ascending order
+//                                      (the wave scan of the extraction is lr_prims.h's, the header of the shared integer steps).
 //   3. rotation   tz_rot_kernel        one workgroup per pair, fp64: GNC-TLS over the chain TIMs, 3x3 SVD on one lane.
 //   4. translation tz_vote_kernel      every endpoint of the adaptive voting evaluated on its own (no sort: the consensus set at an
 //                                      endpoint is the set of intervals whose entry key <= its key < their exit key), then
 //                 tz_final_kernel      first minimum per axis, translation inliers, result block.
 // All reductions run in a fixed order, so a pair's result does not depend on the batch it is in or on scheduling.
 #include "lr_corrset.h"
+#include "lr_prims.h"
 #include <math.h>
 
 #define TZ_MAX_M CS_MAX_M
@@ -481,8 +483,7 @@ __global__ void __launch_bounds__(64) tz_search_kernel(tz_args g, long long node
         const int w = w0 + lane;
         unsigned long long x = w < W ? fin[w] : 0ull;
         const int pc = __popcll(x);
-        int incl = pc;
-        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o); if (lane >= o) incl += u; }
+        const int incl = lr_wave_incl_scan(pc, lane);
         int o = base + incl - pc;
         while (x) { const int v = w * 64 + __ffsll((long long)x) - 1; x &= x - 1; clique[o] = v; if (out) out[o] = v; ++o; }
         base += __shfl(incl, 63);

@@ -6,14 +6,15 @@
 // floored to integer cells and one point per occupied cell is kept -- the FIRST one in input order -- with the kept indices
 // returned in ascending order, so that xyz[sel] keeps the scan order of the cloud.
 //
-// Structure (HBM-bound integer work, three small launches): open-addressing hash table over the packed cell key
-// (3 x 21 bits), 2..4 slots per point; every point claims its cell's slot with a 64-bit compare-and-swap and lowers the
-// slot's point index with atomicMin (so the result does not depend on the order the threads run in); a point is kept iff it
-// is its cell's minimum; ordered compaction = per-block counts + prefix + scatter.
+// Structure (HBM-bound integer work, three small launches): every point claims the slot of its packed cell key (3 x 21 bits) in the
+// open-addressing table of lr_cells.h and lowers the slot's point index with atomicMin (so the result does not depend on the order the
+// threads run in); a point is kept iff it is its cell's minimum; ordered compaction = per-block counts + prefix + scatter.  The table,
+// the hash and the compaction steps are the shared ones (lr_cells.h, lr_prims.h); this file owns the cell rule -- the floor of the
+// coordinate, biased by 2^20 -- and its three kernels over plain arrays.
 #include "lr_internal.h"
+#include "lr_cells.h"
 #include <math.h>
 
-#define LR_VX_EMPTY 0xffffffffffffffffull
 #define LR_VX_BIAS (1 << 20)          // cells are stored biased: |cell| < 2^20 per axis
 
 __device__ __forceinline__ unsigned long long vx_key(const double *__restrict__ c, int i, bool &ok)
@@ -22,13 +23,7 @@ __device__ __forceinline__ unsigned long long vx_key(const double *__restrict__ 
     ok = fabs(fx) < (double)LR_VX_BIAS && fabs(fy) < (double)LR_VX_BIAS && fabs(fz) < (double)LR_VX_BIAS;     // false for NaN / inf too
     const unsigned long long x = (unsigned long long)((long long)fx + LR_VX_BIAS), y = (unsigned long long)((long long)fy + LR_VX_BIAS),
                              z = (unsigned long long)((long long)fz + LR_VX_BIAS);
-    return ok ? (x << 42) | (y << 21) | z : 0ull;
-}
-
-__device__ __forceinline__ unsigned vx_hash(unsigned long long k)
-{
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned)k;
+    return ok ? lr_cells_pack(x, y, z) : 0ull;
 }
 
 __global__ void __launch_bounds__(256)
@@ -40,12 +35,7 @@ voxel_insert_kernel(const double *__restrict__ coords, int n, unsigned long long
     bool ok;
     const unsigned long long k = vx_key(coords, i, ok);
     if (!ok) { slot_of[i] = -1; return; }           // outside the representable grid / non-finite: dropped
-    unsigned s = vx_hash(k) & cap_mask;
-    for (;;) {
-        const unsigned long long prev = atomicCAS(&keys[s], LR_VX_EMPTY, k);
-        if (prev == LR_VX_EMPTY || prev == k) break;
-        s = (s + 1) & cap_mask;
-    }
+    const unsigned s = lr_cells_claim(keys, cap_mask, k);
     atomicMin(&first[s], i);
     slot_of[i] = (int32_t)s;
 }
@@ -54,14 +44,10 @@ __global__ void __launch_bounds__(256)
 voxel_flag_kernel(int n, const int32_t *__restrict__ first, const int32_t *__restrict__ slot_of, uint8_t *__restrict__ keep,
                   int32_t *__restrict__ blk_cnt)
 {
-    __shared__ int s_w[4];
     const int i = blockIdx.x * 256 + threadIdx.x;
     bool k = false;
-    if (i < n) { const int s = slot_of[i]; k = s >= 0 && first[s] == i; keep[i] = k ? 1 : 0; }
-    const unsigned long long bal = __ballot(k);
-    if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    if (i < n) { int s; k = lr_cells_is_first(first, slot_of, i, s); keep[i] = k ? 1 : 0; }
+    lr_block_count(k, blk_cnt);
 }
 
 __global__ void __launch_bounds__(256)
@@ -69,20 +55,10 @@ voxel_compact_kernel(const double *__restrict__ coords, int n, const uint8_t *__
                      int32_t *__restrict__ sel, int32_t *__restrict__ cells, int32_t *__restrict__ n_sel)
 {
     __shared__ int s_w[4], s_p[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int c = 0;
-    for (int b = tid; b < (int)blockIdx.x; b += 256) c += blk_cnt[b];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-    const int i = blockIdx.x * 256 + tid;
+    const int before = lr_blocks_before(blk_cnt), i = blockIdx.x * 256 + threadIdx.x;
     const bool k = i < n && keep[i] != 0;
-    const unsigned long long bal = __ballot(k);
-    if (lane == 0) { s_p[wave] = c; s_w[wave] = __popcll(bal); }
-    __syncthreads();
-    const int prefix = s_p[0] + s_p[1] + s_p[2] + s_p[3];
-    int woff = 0;
-    for (int w = 0; w < wave; ++w) woff += s_w[w];
-    const int slot = prefix + woff + __popcll(bal & ((1ull << lane) - 1ull));
+    int prefix;
+    const int slot = lr_ordered_slot(k, before, s_w, s_p, prefix);
     if (k) {
         sel[slot] = i;
         if (cells) {
@@ -90,19 +66,12 @@ voxel_compact_kernel(const double *__restrict__ coords, int n, const uint8_t *__
             for (int a = 0; a < 3; ++a) cells[3 * (size_t)slot + a] = (int32_t)floor(coords[3 * (size_t)i + a]);
         }
     }
-    if (blockIdx.x == gridDim.x - 1 && tid == 0) *n_sel = prefix + s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-static size_t vx_capacity(int n)
-{
-    size_t c = 1024;
-    while (c < 2 * (size_t)(n > 0 ? n : 1)) c <<= 1;
-    return c;
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_sel = prefix + s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
 
 extern "C" size_t lr_voxel_dedup_scratch_bytes(int n)
 {
-    const size_t cap = vx_capacity(n), nn = (size_t)(n > 0 ? n : 1);
+    const size_t nn = (size_t)(n > 0 ? n : 1), cap = lr_cells_capacity(nn);
     return cap * 8 + cap * 4 + nn * 4 + ((nn + 255) & ~size_t(255)) + (nn / 256 + 2) * 4 + 1024;
 }
 
@@ -115,7 +84,7 @@ extern "C" int lr_voxel_dedup(const double *coords, int n, int32_t *sel, int32_t
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) { LR_HIP(hipMemsetAsync(n_sel, 0, sizeof(int32_t), st)); return LR_OK; }
     LR_TRY_HIP(lr_check_memory_device(scratch, st, "lr_voxel_dedup", nullptr));      // (n == 0 takes no scratch: nothing to check)
-    const size_t cap = vx_capacity(n);
+    const size_t cap = lr_cells_capacity((size_t)n);
     char *p = reinterpret_cast<char *>(scratch);
     unsigned long long *keys = reinterpret_cast<unsigned long long *>(p); p += cap * 8;
     int32_t *first = reinterpret_cast<int32_t *>(p); p += cap * 4;

@@ -176,3 +176,21 @@ SCRATCH_BYTES = {"lr_teaser_scratch_bytes": (12032, 12032, 12032, 12032, 26368, 
 def test_corrset_scratch_sizes_unchanged(libpath, fn):
     f = getattr(_ext.lib(), fn)
     assert tuple(f(m) for m in SCRATCH_M) == SCRATCH_BYTES[fn]
+
+
+# lr_voxel_dedup_scratch_bytes(n), lr_voxel_mean_scratch_bytes(n), lr_overlap_scratch_bytes(n, n) around the block size, the table's
+# doublings and the largest cloud, as the library returned them BEFORE the voxel and overlap kernels got a shared cell table and shared
+# primitives (csrc/lr_cells.h, csrc/lr_prims.h): constants read from that build, so that the one capacity rule cannot shift an arena
+CELLS_N = (0, 1, 255, 256, 257, 511, 512, 513, 4097, 30000, 4194304)
+CELLS_BYTES = {"lr_voxel_dedup_scratch_bytes": (13580, 13580, 14596, 14604, 14864, 15880, 15888, 28436, 218444, 938140, 121701384),
+               "lr_voxel_mean_scratch_bytes": (24320, 24320, 40704, 40704, 43776, 60160, 60160, 83712, 642816, 3593216, 486605568),
+               "lr_overlap_scratch_bytes": (56576, 56576, 95232, 95232, 101632, 140288, 140288, 187648, 1449216, 8168192, 1107428352)}
+
+
+@pytest.mark.parametrize("fn", sorted(CELLS_BYTES))
+def test_cell_table_scratch_sizes_unchanged(libpath, fn):
+    f = getattr(_ext.lib(), fn)
+    call = (lambda n: f(n, n)) if fn == "lr_overlap_scratch_bytes" else f
+    assert tuple(call(n) for n in CELLS_N) == CELLS_BYTES[fn]
+    if fn != "lr_voxel_dedup_scratch_bytes":
+        assert call(4194305) == 0                       # one point more than a cloud may have: refused

@@ -106,6 +106,36 @@ def test_nullable_outputs(lr):
     assert tuple(info.cpu().numpy()) == (ref_cloud("scan_1025_v1")["rows"], 0, 0, 0)
 
 
+def test_two_entry_points_one_table(lr):
+    """lr_voxel_dedup and lr_voxel_mean share the cell table (csrc/lr_cells.h) but not the cell rule: floor(p) in one, floor((p - vmb) /
+    voxel) in the other.  777 points (3 full blocks and a partial one), coordinates multiples of 2^-8 in [0.5, 40), every axis with
+    minimum exactly k + 0.5, voxel 1: vmb = min - 0.5 is an integer, so floor(p - vmb) = floor(p) - vmb exactly and both entry points see
+    the same partition into cells.  Then the same with the second half a copy of the first: every cell is hit at least twice."""
+    from lidarregistration_amd import voxel
+    rng = np.random.default_rng(777)
+    lo, hi = np.array([0.5, 3.5, 7.5]), np.array([40.0, 9.0, 10.0])
+    X = np.floor((lo + rng.random((777, 3)) * (hi - lo)) * 256.0) / 256.0
+    X[5, 0], X[300, 1], X[387, 2] = lo                                    # the minima, all in the first half
+    assert (X.min(0) == lo).all() and (X >= 0.5).all() and (X < 40.0).all() and (X * 256.0 == np.floor(X * 256.0)).all()
+    twice = np.concatenate([X[:388], X[:388], X[:1]])
+    for cloud in (X, twice):
+        assert cloud.shape == (777, 3) and (cloud.min(0) == lo).all()
+        # the plain definition: cells in order of their first point, points per cell
+        _, idx, inv = np.unique(np.floor(cloud).astype(np.int64), axis=0, return_index=True, return_inverse=True)
+        order = np.argsort(idx)
+        rank = np.empty_like(order); rank[order] = np.arange(len(order))
+        want_first, want_counts = idx[order], np.bincount(rank[inv.reshape(-1)], minlength=len(order))
+        cells, sel = voxel.sparse_quantize(cloud)
+        r = lr.ov.voxel_mean_dev(cloud, 1.0)
+        first, counts = r["first"].cpu().numpy(), r["counts"].cpu().numpy()
+        assert (r["status"], r["dropped"]) == (0, 0)
+        assert np.array_equal(first, sel.cpu().numpy()) and np.array_equal(first, want_first)
+        assert r["rows"] == len(sel) == len(want_first)
+        assert counts.sum() == 777 and np.array_equal(counts, want_counts)
+        assert np.array_equal(cells.cpu().numpy(), np.floor(cloud[want_first]).astype(np.int32))
+    assert (counts >= 2).all() and (first < 388).all()                     # (the doubled cloud)
+
+
 @pytest.mark.parametrize("name", sorted(PAIRS))
 def test_overlap_equals_the_restatement(lr, name):
     p, ref = PAIRS[name], ref_pair(name)

@@ -1,10 +1,10 @@
 """One call of every entry point of liblidarreg.so that launches kernels, at dim 32 and dim 3: the workload behind
-profiles/host_context_trace.txt.  Run it under `rocprofv3 --kernel-trace -- python tools/entry_point_trace.py`, once per library
+profiles/host_context_trace.txt and profiles/prims_trace.txt.  Run it under `rocprofv3 --kernel-trace -- python tools/entry_point_trace.py`, once per library
 (LIDARREG_LIB names an alternate build), and compare the two kernel traces with tools/trace_compare.py."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from lidarregistration_amd import FR, _ext, matching, ransac, synth
+from lidarregistration_amd import FR, _ext, matching, overlap, ransac, sm, synth, teaser, voxel
 from types import SimpleNamespace as Args      # (FR.pair_params supplies the reference's defaults for what is not given)
 
 t = torch.from_numpy
@@ -34,5 +34,16 @@ ransac.icp_dev(A, B, T)
 # descriptors narrower than 32: the coordinates themselves
 FR.read_result(FR.register_pair_dev(A, B, A.contiguous(), B.contiguous(), FR.pair_params(Args(mode="MNN", codebase="open3D", iters=2048, ransac_n=3, o3d_conf=1.0))))
 matching.nn_top2_dev(A, B)
+# the cloud-level primitives: lr_voxel_dedup, lr_voxel_mean, lr_overlap, lr_overlap_batch over three ragged pairs
+clouds = [(t(p["xyz0"]).double(), t(p["xyz1"]).double(), p["T_gt"]) for p in host]
+voxel.sparse_quantize(clouds[0][0] / 0.3)
+overlap.voxel_mean_dev(clouds[0][0], 0.3, clouds[0][2])
+overlap.overlap_dev(*clouds[0])
+overlap.overlap_batch_dev(clouds)
+# the correspondence-set solvers over the mutual pairs, cut to three ragged sets: lr_sm_batch, lr_teaser_batch
+src, tgt = A[o0.long()].contiguous(), B[o1.long()].contiguous()
+sets = [len(src), 300, 65]
+sm.sm_batch_dev([src[:m] for m in sets], [tgt[:m] for m in sets])
+teaser.teaser_batch_dev([src[:m] for m in sets], [tgt[:m] for m in sets])
 torch.cuda.synchronize()
 print("entry_point_trace: done")
