@@ -478,6 +478,71 @@ LR_API int lr_overlap_batch(int npairs, const double *const *xyz0, const int32_t
                             const double *const *T, const lr_overlap_params *p, lr_overlap_result *results, void *scratch,
                             size_t scratch_bytes, void *stream);
 
+/* ---- f6: the exact 3-D nearest neighbour and the Z-only refinement of a ground-truth motion ------------------------------------------
+ * lr_nn3 replaces the balanced-set generator's NN (GenerateBalancedSet.py:149-153: cKDTree(B).query(A, k = 1)) -- unbounded and exact,
+ * unlike the radius-bounded searches of lr_icp and lr_overlap; lr_refine_z replaces refine_motion_Z_only (:257-291).  Contract (restated
+ * in tests/refine_z_cpu.py).  All arithmetic is fp64, no fused multiply-add.
+ *  N1 inputs: xyz0 [n0,3] (queries), xyz1 [n1,3] (target), float64 on the device, n in 0 .. 4194304.
+ *  N2 distance: d2(i,j) = (dx dx + dy dy) + dz dz on the differences a - b per axis.
+ *  N3 outputs: idx[i] = the j of the least d2 over the finite target points, the LOWEST j on equal computed d2; dist[i] = the correctly
+ *     rounded square root of that d2.
+ *  N4 a target point with a non-finite coordinate is never a neighbour; a non-finite query gets idx -1, dist +inf.  Both kinds are
+ *     counted in info (the reference raises ValueError).
+ *  N5 n1 == 0 or no finite target: every idx -1, every dist +inf, status 1.  Legal.
+ *  N6 cell: edge of the search grid's cells.  0 = automatic: the finest edge E 2^(-k/2), k = 0 .. 80, E the longest edge of the
+ *     target's bounding box, whose grid over that box has at most max(4096, 4 n1) cells.  cell > 0: that edge, doubled until the grid
+ *     has at most that many cells.  A tuning knob only: THE RESULT DOES NOT DEPEND ON IT.
+ *  Z  lr_refine_z: A_ = T A by C1 above (T == NULL: A as it is), dz = 0; the target's grid is built once.  Each of up to max_repeats
+ *     repeats: (1) ind = N(A_, B); (2) pair i is valid iff ind >= 0 and sqrt(dx dx + dy dy) <= xy_gate (root correctly rounded,
+ *     non-strict); (3) z_i = A_z - B_z, w_i = 1 / |z_i| (+inf at 0); (4) med = numpy's median of the valid w: the middle element, or
+ *     (lo + hi) / 2 of the two middle ones -- found by an exact radix select on the bit patterns; (5) w_i = min(w_i, med);
+ *     (6) mean = S(w z) / S(w), the products rounded separately, S the fixed two-level sum: the terms sit at their source index (an
+ *     invalid pair is +0.0), every run of 1024 consecutive indices is summed left to right from +0, then the run sums left to right;
+ *     (7) every A_z becomes fl(A_z - mean), dz = fl(dz - mean); (8) stop after this repeat if |mean| < min_change.
+ *     Deviations: no valid pair -> status 1, dz stays as accumulated, the loop stops (the reference takes the median of nothing: NaN);
+ *     med == +inf (at least half the valid pairs coincide in z) -> status 2, the step is 0, the loop stops (the reference computes
+ *     inf * 0 = NaN).  The same bits on every run, whatever the scratch held; no floating-point atomics; no host synchronisation
+ *     (the repeats of a finished call return at their first instruction): graph-capturable.
+ *  Refusals, all LR_EINVAL before any launch, lr_last_error naming the argument: wrong struct_size; cell negative or not finite;
+ *     max_repeats outside 1..64; xy_gate not positive and finite; min_change negative or not finite; n0 / n1 outside 0..4194304; null
+ *     pointers where n > 0 (scratch, info / result always needed); short or misaligned (256 bytes) scratch; scratch that is not memory
+ *     of the current gfx950 device, or a stream of another device.                                                                   */
+typedef struct lr_nn3_params {
+    uint32_t struct_size;        /* = sizeof(lr_nn3_params)                                                                         */
+    uint32_t reserved;           /* 0                                                                                               */
+    double   cell;               /* 0 = automatic (N6)                                                                              */
+} lr_nn3_params;
+
+typedef struct lr_refine_z_params {
+    uint32_t struct_size;        /* = sizeof(lr_refine_z_params)                                                                    */
+    int32_t  max_repeats;        /* 10 (MAX_REPEATS, :264); 1..64                                                                   */
+    double   xy_gate;            /* voxel_size (:273)                                                                               */
+    double   min_change;         /* 1e-6 (MIN_CHANGE, :265)                                                                         */
+    double   cell;               /* 0 = automatic (N6)                                                                              */
+} lr_refine_z_params;
+
+/* Written to device memory by lr_refine_z (40 bytes). */
+typedef struct lr_refine_z_result {
+    int32_t  status;             /* 0 ok, 1 = a repeat had no valid pair, 2 = a repeat's median weight was +inf                     */
+    int32_t  repeats;            /* repeats run, the stopping one included                                                          */
+    int32_t  n_valid;            /* valid pairs of the last repeat                                                                  */
+    int32_t  n0_dropped, n1_dropped;     /* points with a non-finite coordinate (cloud 0: after T)                                  */
+    int32_t  reserved;           /* 0                                                                                               */
+    double   dz;                 /* what to add to the motion's [2,3] (:289)                                                        */
+    double   last_step;          /* mean_z_dist of the last repeat (0 with status 1 / 2)                                            */
+} lr_refine_z_result;
+
+/* Caller-owned device scratch for n0 queries against n1 target points (0 when either is outside 0..4194304). */
+LR_API size_t lr_nn3_scratch_bytes(int n0, int n1);
+/* idx [n0] int32, dist [n0] float64: device.  info: device int32[4] = { status (N5), non-finite queries, non-finite target points,
+ * queries resolved by the second phase (a statistic) }.  Asynchronous on `stream`.                                                   */
+LR_API int lr_nn3(const double *xyz0, int n0, const double *xyz1, int n1, const lr_nn3_params *p, int32_t *idx, double *dist,
+                  int32_t *info, void *scratch, size_t scratch_bytes, void *stream);
+LR_API size_t lr_refine_z_scratch_bytes(int n0, int n1);
+/* T: device, fp64, row-major 4x4, nullable; result: device block.  scratch >= lr_refine_z_scratch_bytes(n0, n1).                    */
+LR_API int lr_refine_z(const double *xyz0, int n0, const double *xyz1, int n1, const double *T, const lr_refine_z_params *p,
+                       lr_refine_z_result *result, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */
 LR_API int lr_workspace_timing(lr_workspace *ws, int enable);

@@ -23,6 +23,7 @@ SYMBOLS = [
     "lr_teaser_scratch_bytes", "lr_teaser", "lr_teaser_batch", "lr_teaser_timing", "lr_teaser_stage_times",
     "lr_sm_scratch_bytes", "lr_sm", "lr_sm_batch",
     "lr_voxel_mean_scratch_bytes", "lr_voxel_mean", "lr_overlap_scratch_bytes", "lr_overlap", "lr_overlap_batch",
+    "lr_nn3_scratch_bytes", "lr_nn3", "lr_refine_z_scratch_bytes", "lr_refine_z",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -133,6 +134,32 @@ class OverlapResult(ctypes.Structure):
                 ("n0_dropped", ctypes.c_int32), ("n1_dropped", ctypes.c_int32), ("frac", ctypes.c_double), ("frac_sym", ctypes.c_double)]
 
 
+class Nn3Params(ctypes.Structure):
+    """lr_nn3_params; cell 0 = automatic (the result does not depend on it); struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("cell", ctypes.c_double)]
+
+    def __init__(self, **kw):
+        kw.pop("struct_size", None)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **kw)
+
+
+class RefineZParams(ctypes.Structure):
+    """lr_refine_z_params with the reference's settings (GenerateBalancedSet.py:264-265, voxel 0.3 at :298) as defaults; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_repeats", ctypes.c_int32), ("xy_gate", ctypes.c_double), ("min_change", ctypes.c_double),
+                ("cell", ctypes.c_double)]
+    DEFAULTS = dict(max_repeats=10, xy_gate=0.3, min_change=1e-6, cell=0.0)
+
+    def __init__(self, **kw):
+        kw.pop("struct_size", None)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
+
+
+class RefineZResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("repeats", ctypes.c_int32), ("n_valid", ctypes.c_int32), ("n0_dropped", ctypes.c_int32),
+                ("n1_dropped", ctypes.c_int32), ("reserved", ctypes.c_int32), ("dz", ctypes.c_double), ("last_step", ctypes.c_double)]
+
+
+assert ctypes.sizeof(Nn3Params) == 16 and ctypes.sizeof(RefineZParams) == 32 and ctypes.sizeof(RefineZResult) == 40
 assert ctypes.sizeof(OverlapParams) == 24 and ctypes.sizeof(OverlapResult) == 40
 assert ctypes.sizeof(TeaserParams) == 72 and ctypes.sizeof(TeaserResult) == 176
 assert ctypes.sizeof(SmParams) == 24 and ctypes.sizeof(SmResult) == 152
@@ -218,6 +245,12 @@ def lib():
         L.lr_overlap_scratch_bytes.argtypes = [ci, ci]
         L.lr_overlap.argtypes = [vp, ci, vp, ci, vp, ctypes.POINTER(OverlapParams), vp, vp, ctypes.c_size_t, vp]
         L.lr_overlap_batch.argtypes = [ci, pp, ip, pp, ip, pp, ctypes.POINTER(OverlapParams), vp, vp, ctypes.c_size_t, vp]
+        L.lr_nn3_scratch_bytes.restype = ctypes.c_size_t
+        L.lr_nn3_scratch_bytes.argtypes = [ci, ci]
+        L.lr_nn3.argtypes = [vp, ci, vp, ci, ctypes.POINTER(Nn3Params), vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.lr_refine_z_scratch_bytes.restype = ctypes.c_size_t
+        L.lr_refine_z_scratch_bytes.argtypes = [ci, ci]
+        L.lr_refine_z.argtypes = [vp, ci, vp, ci, vp, ctypes.POINTER(RefineZParams), vp, vp, ctypes.c_size_t, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

@@ -1,6 +1,7 @@
-"""Voxel-grid down-sampling (one centroid per voxel) and the pair overlap measure on the GPU: the cloud-level primitives of the
-reference's balanced-set generator (BalancedDatasetGenerator/GenerateBalancedSet.py) and of its refinement tester
-(FCGF_FAST/net/refinement_tester.py), on top of lr_voxel_mean / lr_overlap / lr_overlap_batch (csrc/lr_overlap.hip).
+"""Voxel-grid down-sampling (one centroid per voxel), the pair overlap measure, the exact nearest neighbour and the refinement of a
+ground-truth motion on the GPU: the cloud-level primitives of the reference's balanced-set generator
+(BalancedDatasetGenerator/GenerateBalancedSet.py) and of its refinement tester (FCGF_FAST/net/refinement_tester.py), on top of
+lr_voxel_mean / lr_overlap / lr_overlap_batch (csrc/lr_overlap.hip) and lr_nn3 / lr_refine_z (csrc/lr_nn3.hip).
 
 Two different operations carry similar names here.  ``voxel_down_sample`` (this module) is Open3D's: every occupied voxel is replaced by
 the centroid of its points.  ``voxel.voxel_downsample`` is MinkowskiEngine's de-duplication: the first point of every cell is kept.
@@ -143,10 +144,92 @@ def refine_inputs(GT_mot_orig, A, B, downsample=True, voxel_size=0.3):
 def refine_motion(GT_mot_orig, A, B, downsample=True, voxel_size=0.3, refine_GT_Z_only=False):
     """GenerateBalancedSet.py:220-246, the ICP branch: both clouds down-sampled (Open3D's voxel grid), `a` moved by GT_mot_orig, point-to-point
     ICP from the identity with max distance 2 voxel_size and Open3D's default criteria (lr_icp), and icp_mot @ GT_mot_orig returned
-    (4x4 float64 numpy).  The Z-only variant (:257-) needs an unbounded nearest neighbour and is not built."""
+    (4x4 float64 numpy).  The Z-only variant (:257-) is not reached through this flag: refine_GT(..., z_only=True) dispatches to
+    refine_motion_Z_only."""
     if refine_GT_Z_only:
-        raise NotImplementedError("refine_motion: the Z-only refinement (refine_motion_Z_only) is not built")
+        raise NotImplementedError("refine_motion: this is the ICP branch; the Z-only refinement is refine_GT(..., z_only=True) / refine_motion_Z_only")
     from .ransac import icp_dev
     a_corr, b = refine_inputs(GT_mot_orig, A, B, downsample, voxel_size)
     icp_mot, _ = icp_dev(a_corr, b, np.eye(4), max_dist=2.0 * float(voxel_size))
     return icp_mot @ np.ascontiguousarray(GT_mot_orig, np.float64)
+
+
+def nearest_neighbour_dev(A, B, cell=0.0, poison=None):
+    """lr_nn3: for every point of A [n0,3] its exact nearest neighbour among B [n1,3] (float64, unbounded; the lowest index on equal
+    distance).  Returns a dict: dist [n0] float64 and idx [n0] int32 device tensors (idx -1 / dist inf: a non-finite query, or no finite
+    target), status (1: no finite target), n0_dropped, n1_dropped, n_far (queries resolved by the second phase).  cell: edge of the
+    search grid, 0 = automatic; the result does not depend on it."""
+    dev = _device()
+    a, b = _f64(A, dev), _f64(B, dev)
+    n0, n1 = int(a.shape[0]), int(b.shape[0])
+    L = _ext.lib()
+    idx = torch.empty(max(n0, 1), dtype=torch.int32, device=dev); dist = torch.empty(max(n0, 1), dtype=torch.float64, device=dev)
+    info = torch.empty(4, dtype=torch.int32, device=dev)
+    p = _ext.Nn3Params(cell=float(cell))
+    scratch = _scratch(L.lr_nn3_scratch_bytes(n0, n1), dev, poison)
+    _ext.check(L.lr_nn3(a.data_ptr() if n0 else None, n0, b.data_ptr() if n1 else None, n1, ctypes.byref(p), idx.data_ptr(), dist.data_ptr(),
+                        info.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
+    status, d0, d1, far = (int(v) for v in info.cpu())
+    return dict(dist=dist[:n0], idx=idx[:n0], status=status, n0_dropped=d0, n1_dropped=d1, n_far=far)
+
+
+def nearest_neighbour(A, B):
+    """GenerateBalancedSet.py:149-153 `NN`: (d float64 [n0], inds int64 [n0]) as numpy arrays -- cKDTree(B).query(A, k=1).  Where the
+    reference raises on non-finite input, such a query gets (inf, -1) and such a target point is never a neighbour."""
+    r = nearest_neighbour_dev(A, B)
+    return r["dist"].cpu().numpy(), r["idx"].cpu().numpy().astype(np.int64)
+
+
+def refine_z_dev(A, B, T=None, xy_gate=0.3, max_repeats=10, min_change=1e-6, cell=0.0, poison=None):
+    """lr_refine_z: A [n0,3] (moved by T, 4x4, if given) against B [n1,3], the clouds as given.  Returns the lr_refine_z_result as a dict."""
+    dev = _device()
+    a, b = _f64(A, dev), _f64(B, dev)
+    n0, n1 = int(a.shape[0]), int(b.shape[0])
+    L = _ext.lib()
+    Td = _T_dev(T, dev)
+    p = _ext.RefineZParams(xy_gate=float(xy_gate), max_repeats=int(max_repeats), min_change=float(min_change), cell=float(cell))
+    res = torch.zeros((1, ctypes.sizeof(_ext.RefineZResult)), dtype=torch.uint8, device=dev)
+    scratch = _scratch(L.lr_refine_z_scratch_bytes(n0, n1), dev, poison)
+    _ext.check(L.lr_refine_z(a.data_ptr() if n0 else None, n0, b.data_ptr() if n1 else None, n1, None if Td is None else Td.data_ptr(),
+                             ctypes.byref(p), res.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
+    r = _ext.RefineZResult.from_buffer_copy(res[0].cpu().numpy().tobytes())
+    return {name: getattr(r, name) for name, _ in _ext.RefineZResult._fields_}
+
+
+def refine_motion_Z_only(raw_mot, A, B, voxel_size, return_info=False):
+    """GenerateBalancedSet.py:257-291: raw_mot with [2,3] + dz, dz from the IRLS over the z distances of the nearest-neighbour pairs
+    that lie within voxel_size in xy (lr_refine_z, at most 10 repeats, stop below 1e-6).  The clouds are used as given.  Returns a NEW
+    4x4 float64 numpy matrix (the reference adds dz into its caller's array); return_info: (matrix, result block as a dict).  Status 1
+    (no valid pair) and 2 (half the pairs coincide in z), where the reference returns NaN, leave dz as accumulated so far."""
+    M = np.array(raw_mot, dtype=np.float64, copy=True).reshape(4, 4)
+    r = refine_z_dev(A, B, M, xy_gate=float(voxel_size))
+    M[2, 3] += r["dz"]
+    return (M, r) if return_info else M
+
+
+def refine_GT(GT_mot_orig, A, B, downsample=True, voxel_size=0.3, z_only=False):
+    """GenerateBalancedSet.py:233-246, both branches (z_only = config.refine_GT_Z_only, True for the reference's NuScenes and
+    LyftLEVEL5): the clouds down-sampled (Open3D's voxel grid) unless downsample is False, then refine_motion_Z_only on the float64
+    centroids, or the ICP branch (refine_motion: float32 clouds into lr_icp)."""
+    if not z_only:
+        return refine_motion(GT_mot_orig, A, B, downsample, voxel_size)
+    dev = _device()
+    a = voxel_down_sample(A, voxel_size) if downsample else _f64(A, dev)
+    b = voxel_down_sample(B, voxel_size) if downsample else _f64(B, dev)
+    return refine_motion_Z_only(GT_mot_orig, a, b, voxel_size)
+
+
+def refine_session(clouds, raw_motions, voxel_size=0.3, z_only=False):
+    """GenerateBalancedSet.py:293-319 `refine_session_GT`, the host loop: clouds[i] [n_i,3], raw_motions[i] the 4x4 motion of frame i to
+    frame i + 1.  Every frame is down-sampled once; returns the list of positions (4x4 float64 numpy), positions[0] the identity."""
+    assert len(raw_motions) == len(clouds) - 1, "one raw motion per consecutive pair of frames"
+    B_ = voxel_down_sample(clouds[0], voxel_size)
+    B_pos = np.eye(4, dtype=np.float64)
+    positions = [B_pos]
+    for i in range(1, len(clouds)):
+        A_, A_pos = B_, B_pos
+        B_ = voxel_down_sample(clouds[i], voxel_size)
+        mot = refine_GT(raw_motions[i - 1], A_, B_, downsample=False, voxel_size=voxel_size, z_only=z_only)
+        B_pos = mot @ A_pos
+        positions.append(B_pos)
+    return positions
