@@ -543,6 +543,76 @@ LR_API size_t lr_refine_z_scratch_bytes(int n0, int n1);
 LR_API int lr_refine_z(const double *xyz0, int n0, const double *xyz1, int n1, const double *T, const lr_refine_z_params *p,
                        lr_refine_z_result *result, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- f7: Best-Buddies refinement (BBR-F) and hybrid-search point normals on the exact nearest neighbour -------------------------------
+ * lr_bbrf replaces FCGF_FAST/net/BBR_F.py:267-322 (100 Adam steps on six pose parameters over the mutual nearest neighbours of two
+ * clouds under a symmetric point-to-plane loss); lr_normals replaces its calc_normals (:236-241, Open3D estimate_normals with
+ * KDTreeSearchParamHybrid).  Contract (restated in tests/bbrf_cpu.py).  All arithmetic is fp64, no fused multiply-add;
+ * (PQ) of two 3x3 matrices is (P[a][0] Q[0][b] + P[a][1] Q[1][b]) + P[a][2] Q[2][b]; M.v of a matrix and a vector is
+ * (M[a][0] x + M[a][1] y) + M[a][2] z; u.v is (u0 v0 + u1 v1) + u2 v2.  The parameters p = (theta, phi, psi, tx, ty, tz), Adam's
+ * moments and the powers of beta start at 0, 0 and 1.  For iteration k = 0 .. n_iter - 1:
+ *  B1 log row k = (p, loss, n_pairs) of this iteration.
+ *  B2 W = Rz(psi) (Ry(phi) Rx(theta)), Rx = [1 0 0; 0 c -s; 0 s c], Ry = [c 0 s; 0 1 0; -s 0 c], Rz = [c -s 0; s c 0; 0 0 1]
+ *     (BBR_F.py:69-85).  sin and cos are fixed polynomials: z = x x; q = c_17, q = q z + c_k for k = 15, 13 .. 3, sin x = x + (x z) q;
+ *     q = c_16, q = q z + c_k for k = 14, 12 .. 2, cos x = 1 + z q; c_k = fl(+-1 / k!), the Taylor signs (truncation below 2^-60 on
+ *     |x| <= 0.5).  The derivative matrices are dW/dtheta = Rz (Ry dRx), dW/dphi = Rz (dRy Rx), dW/dpsi = dRz (Ry Rx) with
+ *     dRx = [0 0 0; 0 -s -c; 0 c -s], dRy = [-s 0 c; 0 0 0; -c 0 -s], dRz = [-s -c 0; c -s 0; 0 0 0].
+ *  B3 B'_j = (W.B_j) + t per axis (C1 of lr_overlap), nB'_j = W.nB_j.  A never moves.
+ *  B4 f = N(A, B'), r = N(B', A) by contract N of lr_nn3; (i, f_i) is a pair iff f_i >= 0 and r[f_i] == i.
+ *  B5 per pair: s = -1 if nA_i.nB'_j < 0, else +1; m = nA_i + s nB'_j; d = A_i - B'_j; dot = d.m; term = |dot| if |dot| > 1e-15, else
+ *     1e-15.  loss = S(terms) / n_pairs, S the two-level sum Z6 of lr_refine_z over the source index i (a non-pair is +0.0).
+ *  B6 gradient: a pair with fl(dot dot) < 1e-30 contributes +0.0; else g = sg e, sg = -1 if dot < 0, else +1, with
+ *     e = -m_a for t_a and e = d.(s (dW/dq.nB_j)) - (dW/dq.B_j).m for an angle q.  grad = S(g) / n_pairs, six sums.
+ *  B7 Adam (torch's rule), t = k + 1: pw1 = pw1 beta1, pw2 = pw2 beta2; m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2)(g g);
+ *     p = p - (lr / (1 - pw1)) (m / (sqrt(v) / sqrt(1 - pw2) + eps)); roots and quotients correctly rounded.  An angle that then is
+ *     not within [-0.5, 0.5]: status 3, the loop stops.
+ *  B8 best_iter = the first iteration of least loss (a NaN loss is never the least); B_to_A = [W t; 0 1] from that row's parameters by
+ *     B2; T = [W^T, -(W^T.t); 0 1].  No iteration with a pair: the identity, best_iter -1, best_loss +inf.
+ *  Deviations from the reference: parameters and moments are fp64 (float32 there); an iteration without a pair logs loss +inf, sets
+ *     status 1 and stops the loop with the best so far (the reference takes the mean of nothing); the inverse is the rigid one.
+ *  Log rows past iters_run are +0.0.  The same bits on every run, whatever the scratch held; no floating-point atomics; no host
+ *  synchronisation (the launches of a finished call return at their first instruction): graph-capturable.
+ *  Refusals, all LR_EINVAL before any launch, lr_last_error naming the argument: wrong struct_size; n_iter outside 1..1000; a learning
+ *     rate or eps not positive and finite; a beta outside [0, 1); cell negative or not finite; n0 / n1 outside 0..4194304; null pointers
+ *     where n > 0 (scratch and result always needed); short or misaligned (256 bytes) scratch; scratch that is not memory of the
+ *     current gfx950 device, or a stream of another device.  n0 == 0 or n1 == 0 is legal (status 1).
+ *  Normals [upstream-recalled from Open3D 0.13, parity unpinned]: the neighbours of point i are the at most max_nn finite points of
+ *     least (d2, index) with d2 <= fl(radius radius), d2 by N2, i itself included.  Fewer than 3: (0, 0, 1).  Else the sums of x, y, z,
+ *     xx, xy, xz, yy, yz, zz over the neighbours in (d2, index) order from +0, each divided by their number, cov(a,b) = E[ab] - E[a] E[b];
+ *     eigenvectors by 8 sweeps of cyclic Jacobi over (0,1), (0,2), (1,2) -- a_pq != 0: th = (a_qq - a_pp) / (2 a_pq),
+ *     t = sign(th) / (|th| + sqrt(th th + 1)) (sign(0) = +1), c = 1 / sqrt(t t + 1), s = t c; a_pp -= t a_pq, a_qq += t a_pq, a_pq = 0,
+ *     (a_rp, a_rq) = (c a_rp - s a_rq, s a_rp + c a_rq), the same on the columns p, q of V (from the identity) -- the normal is the column
+ *     of V with the least diagonal entry (the lowest index on ties) divided by its norm sqrt((xx + yy) + zz); a norm that is not > 0
+ *     gives (0, 0, 1).  The sign is the solver's.  A non-finite point gets (0, 0, 1) and is counted in info.                         */
+typedef struct lr_bbrf_params {
+    uint32_t struct_size;        /* = sizeof(lr_bbrf_params)                                                                        */
+    int32_t  n_iter;             /* 100 (BBR_F.py:272); 1..1000                                                                     */
+    double   angles_lr, trans_lr;        /* 2e-4 each (:273-274)                                                                    */
+    double   beta1, beta2, eps;  /* 0.9, 0.999, 1e-8 (torch.optim.Adam's defaults)                                                  */
+    double   cell;               /* 0 = automatic (N6)                                                                              */
+} lr_bbrf_params;
+
+/* Written to device memory by lr_bbrf (280 bytes). */
+typedef struct lr_bbrf_result {
+    double   T[16];              /* A -> B, row-major                                                                               */
+    double   B_to_A[16];
+    int32_t  status;             /* 0 ok, 1 = an iteration had no pair, 3 = an angle left [-0.5, 0.5]                               */
+    int32_t  best_iter;          /* -1: none                                                                                        */
+    double   best_loss;
+    int32_t  n_pairs_best;
+    int32_t  iters_run;          /* log rows written, the stopping one included                                                     */
+} lr_bbrf_result;
+
+/* Caller-owned device scratch (0 when n0 / n1 is outside 0..4194304 or n_iter outside 1..1000). */
+LR_API size_t lr_bbrf_scratch_bytes(int n0, int n1, int n_iter);
+/* xyzA, nrmA [n0,3], xyzB, nrmB [n1,3]: device float64; result: device block; log: device float64 [n_iter, 8], nullable.           */
+LR_API int lr_bbrf(const double *xyzA, const double *nrmA, int n0, const double *xyzB, const double *nrmB, int n1,
+                   const lr_bbrf_params *params, lr_bbrf_result *result, double *log, void *scratch, size_t scratch_bytes, void *stream);
+LR_API size_t lr_normals_scratch_bytes(int n);
+/* normals_out [n,3] device float64; info: device int32[4] = { 1 if no finite point, non-finite points, points with fewer than 3
+ * neighbours, 0 }.  radius positive and finite, max_nn in 1..32.                                                                  */
+LR_API int lr_normals(const double *xyz, int n, double radius, int max_nn, double *normals_out, int32_t *info, void *scratch,
+                      size_t scratch_bytes, void *stream);
+
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */
 LR_API int lr_workspace_timing(lr_workspace *ws, int enable);

@@ -24,6 +24,7 @@ SYMBOLS = [
     "lr_sm_scratch_bytes", "lr_sm", "lr_sm_batch",
     "lr_voxel_mean_scratch_bytes", "lr_voxel_mean", "lr_overlap_scratch_bytes", "lr_overlap", "lr_overlap_batch",
     "lr_nn3_scratch_bytes", "lr_nn3", "lr_refine_z_scratch_bytes", "lr_refine_z",
+    "lr_bbrf_scratch_bytes", "lr_bbrf", "lr_normals_scratch_bytes", "lr_normals",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -159,6 +160,23 @@ class RefineZResult(ctypes.Structure):
                 ("n1_dropped", ctypes.c_int32), ("reserved", ctypes.c_int32), ("dz", ctypes.c_double), ("last_step", ctypes.c_double)]
 
 
+class BbrfParams(ctypes.Structure):
+    """lr_bbrf_params with the reference's settings (BBR_F.py:271-275, torch.optim.Adam's defaults) as defaults; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_iter", ctypes.c_int32), ("angles_lr", ctypes.c_double), ("trans_lr", ctypes.c_double),
+                ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("cell", ctypes.c_double)]
+    DEFAULTS = dict(n_iter=100, angles_lr=2e-4, trans_lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, cell=0.0)
+
+    def __init__(self, **kw):
+        kw.pop("struct_size", None)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
+
+
+class BbrfResult(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_double * 16), ("B_to_A", ctypes.c_double * 16), ("status", ctypes.c_int32), ("best_iter", ctypes.c_int32),
+                ("best_loss", ctypes.c_double), ("n_pairs_best", ctypes.c_int32), ("iters_run", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(BbrfParams) == 56 and ctypes.sizeof(BbrfResult) == 280
 assert ctypes.sizeof(Nn3Params) == 16 and ctypes.sizeof(RefineZParams) == 32 and ctypes.sizeof(RefineZResult) == 40
 assert ctypes.sizeof(OverlapParams) == 24 and ctypes.sizeof(OverlapResult) == 40
 assert ctypes.sizeof(TeaserParams) == 72 and ctypes.sizeof(TeaserResult) == 176
@@ -251,6 +269,12 @@ def lib():
         L.lr_refine_z_scratch_bytes.restype = ctypes.c_size_t
         L.lr_refine_z_scratch_bytes.argtypes = [ci, ci]
         L.lr_refine_z.argtypes = [vp, ci, vp, ci, vp, ctypes.POINTER(RefineZParams), vp, vp, ctypes.c_size_t, vp]
+        L.lr_bbrf_scratch_bytes.restype = ctypes.c_size_t
+        L.lr_bbrf_scratch_bytes.argtypes = [ci, ci, ci]
+        L.lr_bbrf.argtypes = [vp, vp, ci, vp, vp, ci, ctypes.POINTER(BbrfParams), vp, vp, vp, ctypes.c_size_t, vp]
+        L.lr_normals_scratch_bytes.restype = ctypes.c_size_t
+        L.lr_normals_scratch_bytes.argtypes = [ci]
+        L.lr_normals.argtypes = [vp, ci, dp, ci, vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

@@ -16,67 +16,10 @@
 // remaining launches return at their first instruction.  No floating-point atomic; every word read was written by a kernel of the call.
 #include "lr_corrset.h"
 #include "lr_prims.h"
+#include "lr_nn3.h"
 #include <math.h>
 #include <string.h>
 
-#define NN_MAX_N 4194304             // points per cloud (2^22)
-#define NN_SHELL_CAP 3               // phase 1 walks shells 0..3 (up to 343 cells behind 119 ranges)
-#define NN_MARGIN (1.0 - 1.0 / 524288.0)     // 1 - 2^-19
-#define NN_OPEN (-2)                 // idx of a query phase 1 left open
-#define NN_RUN 1024                  // run length of the two-level sum (contract Z6)
-#define NN_FAR_BLOCKS 2048
-
-struct nn_ctl {
-    unsigned long long lo[3], hi[3];         // order-preserving images of the target's min / max
-    double blo[3], bhi[3], cell;
-    int32_t dim[3], ncell;
-    int32_t n1_live, n1_dropped, n0_dropped, n_strag;
-    // lr_refine_z
-    int32_t done, repeats, n_valid, status;
-    double dz, pending, last_step, med;
-    unsigned long long hi_key;
-};
-static_assert(sizeof(nn_ctl) <= 512, "nn_ctl outgrew its slot");
-
-struct nn_layout { size_t table, pts, pidx, blk, strag, idx, P0, zd, w, hist, part, end; };
-struct nn_args {
-    char *base;
-    size_t stride;                           // (cs_ptr's form; always one arena)
-    nn_layout L;
-    const double *xyz0, *xyz1, *T;
-    int32_t n0, n1, ncell_max, refine;
-    double cell_user;
-    int32_t *idx_out;                        // lr_nn3: the caller's; lr_refine_z: scratch
-    double *dist_out;                        // lr_nn3 only
-    double gate, min_change;
-    int32_t max_repeats;
-    lr_refine_z_result *res;
-};
-
-static size_t nn_cells_max(size_t n1) { return 4 * n1 > 4096 ? 4 * n1 : 4096; }
-static size_t nn_make_layout(nn_layout *L, size_t n0, size_t n1, int refine)
-{
-    const size_t m0 = n0 > 0 ? n0 : 1, m1 = n1 > 0 ? n1 : 1;
-    size_t o = 512;
-    L->table = o; o += cs_al(nn_cells_max(n1) * 4);
-    L->pts = o;   o += cs_al(m1 * 24);
-    L->pidx = o;  o += cs_al(m1 * 4);
-    L->blk = o;   o += cs_al((m0 / 256 + 2) * 4);
-    L->strag = o; o += cs_al(m0 * 4);
-    L->idx = L->P0 = L->zd = L->w = L->hist = L->part = o;
-    if (refine) {
-        L->idx = o;  o += cs_al(m0 * 4);
-        L->P0 = o;   o += cs_al(m0 * 24);
-        L->zd = o;   o += cs_al(m0 * 8);
-        L->w = o;    o += cs_al(m0 * 8);
-        L->hist = o; o += cs_al(8 * 256 * 4);
-        L->part = o; o += cs_al((m0 / NN_RUN + 1) * 16);
-    }
-    L->end = o;
-    return o;
-}
-
-__device__ __forceinline__ nn_ctl *nn_c(const nn_args &g) { return cs_ptr<nn_ctl>(g, 0, 0); }
 // total order of the doubles as unsigned integers (ov_enc / ov_dec of lr_overlap.hip, which this change leaves as it is)
 __device__ __forceinline__ unsigned long long nn_enc(double v)
 {
@@ -87,14 +30,6 @@ __device__ __forceinline__ double nn_dec(unsigned long long e)
 {
     return __longlong_as_double((long long)((e >> 63) ? (e & 0x7fffffffffffffffull) : ~e));
 }
-// clamped cell of a coordinate: 0 .. dim - 1, NaN and everything below the grid to 0
-__device__ __forceinline__ int nn_cell(double p, double lo, double cell, int dim)
-{
-    double v = floor((p - lo) / cell);
-    if (!(v >= 0.0)) v = 0.0;
-    if (!(v <= (double)(dim - 1))) v = (double)(dim - 1);
-    return (int)v;
-}
 // (d2, j) argmin: smaller d2, then smaller j; j = -1 (nothing yet) loses to every j
 __device__ __forceinline__ void nn_take(double d2, int j, double &best, int &bj)
 {
@@ -104,6 +39,7 @@ __device__ __forceinline__ void nn_take(double d2, int j, double &best, int &bj)
 // ---- the grid ------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) nn_init_kernel(nn_args g)
 {
+    if (nn_stopped(g)) return;
     int32_t *table = cs_ptr<int32_t>(g, 0, g.L.table);
     for (size_t s = (size_t)blockIdx.x * 256 + threadIdx.x; s < (size_t)g.ncell_max; s += (size_t)gridDim.x * 256) table[s] = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -118,6 +54,7 @@ __global__ void __launch_bounds__(256) nn_init_kernel(nn_args g)
 
 __global__ void __launch_bounds__(256) nn_bounds_kernel(nn_args g)
 {
+    if (nn_stopped(g)) return;
     nn_ctl *c = nn_c(g);
     const int j = blockIdx.x * 256 + threadIdx.x;
     double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
@@ -160,6 +97,7 @@ __device__ static bool nn_fits(const double ext[3], double cell, double cap, int
 // max(4096, 4 n1) cells; cell > 0: that edge, doubled until the grid fits.  A box without extent is one cell.
 __global__ void nn_grid_kernel(nn_args g)
 {
+    if (nn_stopped(g)) return;
     if (threadIdx.x != 0) return;
     nn_ctl *c = nn_c(g);
     c->n1_live = g.n1 - c->n1_dropped;
@@ -203,6 +141,7 @@ __device__ __forceinline__ int nn_lin(const nn_ctl *c, const double *p)
 
 __global__ void __launch_bounds__(256) nn_count_kernel(nn_args g)
 {
+    if (nn_stopped(g)) return;
     const nn_ctl *c = nn_c(g);
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= g.n1) return;
@@ -213,12 +152,14 @@ __global__ void __launch_bounds__(256) nn_count_kernel(nn_args g)
 
 __global__ void __launch_bounds__(1024) nn_scan_kernel(nn_args g)
 {
+    if (nn_stopped(g)) return;
     lr_block_exscan(cs_ptr<int32_t>(g, 0, g.L.table), (size_t)nn_c(g)->ncell);
 }
 
 // after this kernel table[c] = end of cell c; its start is table[c - 1] (0 for c = 0)
 __global__ void __launch_bounds__(256) nn_scatter_kernel(nn_args g)
 {
+    if (nn_stopped(g)) return;
     const nn_ctl *c = nn_c(g);
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= g.n1) return;
@@ -253,6 +194,7 @@ __device__ __forceinline__ bool nn_settled(double best, double ex2, int s, doubl
 
 __global__ void __launch_bounds__(256) nn_walk_kernel(nn_args g)
 {
+    if (nn_stopped(g)) return;
     nn_ctl *c = nn_c(g);
     if (g.refine && c->done) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -319,6 +261,7 @@ __global__ void __launch_bounds__(256) nn_walk_kernel(nn_args g)
 // the open queries in index order; block 0 also clears the words the repeat's later kernels accumulate into
 __global__ void __launch_bounds__(256) nn_strag_kernel(nn_args g)
 {
+    if (nn_stopped(g)) return;
     __shared__ int s_w[4], s_p[4];
     nn_ctl *c = nn_c(g);
     if (g.refine && c->done) return;
@@ -339,6 +282,7 @@ __global__ void __launch_bounds__(256) nn_strag_kernel(nn_args g)
 // ---- phase 2: one wave per open query streams the bucketed target ------------------------------------------------------------------
 __global__ void __launch_bounds__(256) nn_far_kernel(nn_args g)
 {
+    if (nn_stopped(g)) return;
     const nn_ctl *c = nn_c(g);
     if (g.refine && c->done) return;
     const int ns = c->n_strag, n1 = c->n1_live, lane = threadIdx.x & 63;
@@ -601,7 +545,18 @@ static int nn_check_common(const char *who, const double *xyz0, int n0, const do
     return LR_OK;
 }
 
-static void nn_launch_grid(const nn_args &g, hipStream_t st)
+void nn_set_args(nn_args *g, void *arena, const double *xyz0, int n0, const double *xyz1, int n1, double cell, int32_t *idx_out,
+                 const int32_t *stop)
+{
+    memset(g, 0, sizeof *g);
+    g->stride = nn_make_layout(&g->L, (size_t)n0, (size_t)n1, 0);
+    g->base = reinterpret_cast<char *>(arena);
+    g->xyz0 = xyz0; g->xyz1 = xyz1; g->n0 = n0; g->n1 = n1;
+    g->ncell_max = (int32_t)nn_cells_max((size_t)n1);
+    g->cell_user = cell; g->idx_out = idx_out; g->stop = stop;
+}
+
+void nn_launch_grid(const nn_args &g, hipStream_t st)
 {
     const int nb1 = lr_cdiv(g.n1 > 0 ? g.n1 : 1, 256);
     const int ib = lr_cdiv(g.ncell_max, 256) < 1024 ? lr_cdiv(g.ncell_max, 256) : 1024;
@@ -613,7 +568,7 @@ static void nn_launch_grid(const nn_args &g, hipStream_t st)
     hipLaunchKernelGGL(nn_scatter_kernel, dim3(nb1), dim3(256), 0, st, g);
 }
 
-static void nn_launch_search(const nn_args &g, hipStream_t st)
+void nn_launch_search(const nn_args &g, hipStream_t st)
 {
     const int nb0 = lr_cdiv(g.n0 > 0 ? g.n0 : 1, 256);
     const int fb = lr_cdiv(g.n0 > 0 ? g.n0 : 1, 4) < NN_FAR_BLOCKS ? lr_cdiv(g.n0 > 0 ? g.n0 : 1, 4) : NN_FAR_BLOCKS;
