@@ -71,12 +71,13 @@ def move(B, nB, p):
     return Bp, rot3(W, nB), W, dW
 
 
-def best_buddies(A, Bp):
-    """B4: (f, keep): f = N(A, B'), keep[i] iff f_i >= 0 and N(B', A)[f_i] == i."""
+def best_buddies(A, Bp, search=None):
+    """B4: (f, keep): f = N(A, B'), keep[i] iff f_i >= 0 and N(B', A)[f_i] == i.  search: refine_z_cpu.nn (the default) or nn_tree."""
+    search = refine_z_cpu.nn if search is None else search
     if len(A) == 0 or len(Bp) == 0:
         return np.full(len(A), -1, np.int64), np.zeros(len(A), bool)
-    f = refine_z_cpu.nn(A, Bp)[1]
-    r = refine_z_cpu.nn(Bp, A)[1]
+    f = search(A, Bp)[1]
+    r = search(Bp, A)[1]
     keep = (f >= 0) & (r[np.where(f >= 0, f, 0)] == np.arange(len(A)))
     return f, keep
 
@@ -108,11 +109,11 @@ def pair_terms(A, nA, B, nB, Bp, nBp, dW, f, keep):
     return out, dot
 
 
-def loss_and_grad(A, nA, B, nB, p, f=None, keep=None):
+def loss_and_grad(A, nA, B, nB, p, f=None, keep=None, search=None):
     """(loss, grad[6], n_pairs, f, keep) at p; f / keep given: the pair set held fixed."""
     Bp, nBp, W, dW = move(B, nB, p)
     if f is None:
-        f, keep = best_buddies(A, Bp)
+        f, keep = best_buddies(A, Bp, search)
     n_pairs = int(keep.sum())
     terms, _ = pair_terms(A, nA, B, nB, Bp, nBp, dW, f, keep)
     if n_pairs == 0:
@@ -164,9 +165,9 @@ def pose(p):
     return M, T
 
 
-def bbrf(A, nA, B, nB, n_iter=100, angles_lr=2e-4, trans_lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, trace=None):
+def bbrf(A, nA, B, nB, n_iter=100, angles_lr=2e-4, trans_lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, trace=None, search=None):
     """Contract B.  Returns (result dict, log [n_iter, 8]); rows past iters_run stay +0.0.  trace: a list that receives per iteration
-    dict(f, keep, grad)."""
+    dict(f, keep, grad).  search: the nearest-neighbour restatement, refine_z_cpu.nn (the default) or nn_tree."""
     f64 = lambda X: np.ascontiguousarray(X, np.float64).reshape(-1, 3)
     A, nA, B, nB = f64(A), f64(nA), f64(B), f64(nB)
     log = np.zeros((n_iter, 8))
@@ -174,7 +175,7 @@ def bbrf(A, nA, B, nB, n_iter=100, angles_lr=2e-4, trans_lr=2e-4, beta1=0.9, bet
     adam = Adam([angles_lr] * 3 + [trans_lr] * 3, beta1, beta2, eps)
     status, best_iter, best_loss, n_best, best_p, iters_run = 0, -1, math.inf, 0, [0.0] * 6, 0
     for k in range(n_iter):
-        loss, g, n_pairs, f, keep = loss_and_grad(A, nA, B, nB, p)
+        loss, g, n_pairs, f, keep = loss_and_grad(A, nA, B, nB, p, search=search)
         log[k, :6] = p; log[k, 6] = loss; log[k, 7] = n_pairs
         iters_run = k + 1
         if trace is not None:

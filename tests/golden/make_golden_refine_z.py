@@ -11,7 +11,13 @@ largest valid |z_dist| of the first repeat (the tolerance's scale) and a checksu
 1e-8 away from its threshold (check_conditions, asserted here and in tests/test_refine_z_cpu.py), so that the last-bit differences
 between the reference's matrix product and the contract's transform cannot flip one.
 
+tests/golden/g20_refine_z_large.npz holds the same for the 120 000-raw-point scan pair (tests/large_cases.py::golden_case, 75 199 x 74 958
+centroids; seed 51, the generator's default, met every margin: no other seed was tried), with a SHA-256 of the first repeat's ind in place
+of the array.  Its conditions are checked on the restatement over nn_tree (tests/refine_z_cpu.py), which the brute-force search cannot
+serve at this size.  It is written by a call of its own, so that g18_refine_z.npz keeps its bytes:
+
     python tests/golden/make_golden_refine_z.py
+    python tests/golden/make_golden_refine_z.py large
 """
 import functools
 import os
@@ -63,21 +69,45 @@ def reference_generator():
     return ns
 
 
+def record(gen, p):
+    """The reference's refinement on one pair: (dz, per-repeat means)."""
+    for v in LOG.values():
+        del v[:]
+    raw = np.array(p["T"], np.float64)
+    res = gen.refine_motion_Z_only(raw.copy(), p["A"].copy(), p["B"].copy(), p["gate"])
+    means = np.array(LOG["means"])
+    dz = 0
+    for m in means:
+        dz -= m                                              # (:284, the same subtractions)
+    assert len(means) == len(LOG["nvalid"]) == len(LOG["ind"]) and res[2, 3] == raw[2, 3] + dz
+    return dz, means
+
+
+def main_large():
+    sys.path.insert(0, ROOT)
+    from tests import large_cases, refine_z_cases
+    gen = reference_generator()
+    name, p = large_cases.GOLDEN_NAME, large_cases.golden_case()
+    dz, means = record(gen, p)
+    mine, trace = large_cases.golden_trace()
+    margins = refine_z_cases.check_conditions(p, name, trace=trace)
+    out = {name + "/dz": np.float64(dz), name + "/means": means, name + "/nvalid": np.array(LOG["nvalid"], np.int32),
+           name + "/zmax": np.float64(LOG["zmax"][0]), name + "/sha256": np.array(refine_z_cases.checksum(p["A"], p["B"], p["T"])),
+           name + "/ind0_sha256": np.array(large_cases.index_hash(LOG["ind"][0]))}
+    print(f"{name:18s} n0={len(p['A']):6d} n1={len(p['B']):6d} repeats={len(means):2d} valid={LOG['nvalid'][0]:6d} dz={dz:+.9f} "
+          f"restated {mine['dz']:+.9f} (diff {mine['dz'] - dz:+.2e}) margins nn {margins[0]:.1e} gate {margins[1]:.1e} stop {margins[2]:.1e}")
+    path = os.path.join(HERE, "g20_refine_z_large.npz")
+    np.savez_compressed(path, **out)
+    print("1 case ->", path, os.path.getsize(path), "bytes")
+
+
 def main():
     sys.path.insert(0, ROOT)
     from tests import refine_z_cases, refine_z_cpu
     gen = reference_generator()
     out = {}
     for name, p in refine_z_cases.golden_cases().items():
-        for v in LOG.values():
-            del v[:]
-        raw = np.array(p["T"], np.float64)
-        res = gen.refine_motion_Z_only(raw.copy(), p["A"].copy(), p["B"].copy(), p["gate"])
-        means = np.array(LOG["means"])
-        dz = 0
-        for m in means:
-            dz -= m                                          # (:284, the same subtractions)
-        assert len(means) == len(LOG["nvalid"]) == len(LOG["ind"]) and res[2, 3] == raw[2, 3] + dz
+        dz, means = record(gen, p)
         margins = refine_z_cases.check_conditions(p, name)
         mine = refine_z_cpu.refine_z(p["A"], p["B"], p["T"], p["gate"])
         out[name + "/dz"] = np.float64(dz)
@@ -94,4 +124,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main_large() if sys.argv[1:] == ["large"] else main()

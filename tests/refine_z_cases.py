@@ -58,10 +58,11 @@ def golden_trace(name):
     return refine_z_cpu.refine_z(p["A"], p["B"], p["T"], p["gate"], trace=trace), trace
 
 
-def check_conditions(p, name, min_change=1e-6):
+def check_conditions(p, name, min_change=1e-6, trace=None):
     """In every repeat: nearest and second-nearest distance of every query, every xy distance and the gate, |mean| and MIN_CHANGE lie
-    at least MIN_GAP apart -- a perturbation of 1e-10 cannot flip a decision.  Returns the three margins."""
-    _, trace = golden_trace(name)
+    at least MIN_GAP apart -- a perturbation of 1e-10 cannot flip a decision.  Returns the three margins.  trace: the restatement's per-repeat trace where it is not golden_trace(name)'s."""
+    if trace is None:
+        _, trace = golden_trace(name)
     nn_gap = min(float((t["d_second"] - t["d"]).min()) for t in trace)
     gate = min(float(np.abs(t["xy"][t["ind"] >= 0] - p["gate"]).min()) for t in trace)
     stop = min(abs(abs(t["mean"]) - min_change) for t in trace)

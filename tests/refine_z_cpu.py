@@ -65,6 +65,51 @@ def nn(A, B, chunk=64, second=False):
     return out + (np.sqrt(d2b),) if second else out
 
 
+TREE_K = 8          # candidates per query of nn_tree
+TREE_CLEAR = 1e-9   # the k-th tree distance must exceed the best by this relative margin (the tree's own arithmetic is good to a few ulp)
+
+
+def nn_tree(A, B, second=False, stats=None):
+    """N1-N5 as nn returns them, in O(n log n): scipy's k-d tree proposes TREE_K candidates per finite query, the contract's d2 (N2) is
+    re-evaluated on them and the minimum taken.  A target outside the candidates is at least the k-th tree distance d_k away, so the
+    candidates hold the answer whenever d_k > d_1 (1 + 1e-9) (with `second`: d_2 in place of d_1) and d_k lies in 1e-150 .. 1e150, where
+    squares neither underflow nor overflow.  Every other query -- and every query whose best d2 is attained by two candidates, so that
+    the lowest-index rule is only ever applied by nn's argmin -- is resolved by nn itself, brute force over all targets; with fewer
+    than TREE_K live targets all queries are.  stats: a dict that receives fallback = the number of queries resolved by brute force."""
+    A = np.ascontiguousarray(A, np.float64).reshape(-1, 3); B = np.ascontiguousarray(B, np.float64).reshape(-1, 3)
+    n0 = len(A)
+    okB = np.isfinite(B).all(axis=1); okA = np.isfinite(A).all(axis=1)
+    live, q = np.flatnonzero(okB), np.flatnonzero(okA)
+    idx = np.full(n0, -1, np.int64); d = np.full(n0, np.inf); db = np.full(n0, np.inf)
+    brute = q
+    if len(live) >= TREE_K and len(q):
+        from scipy.spatial import cKDTree
+        Bl, Aq = B[live], A[q]
+        dt, jt = cKDTree(Bl).query(Aq, k=TREE_K, workers=min(16, os.cpu_count() or 1))
+        C = Bl[jt]                                                           # [nq, k, 3]
+        with np.errstate(over="ignore", invalid="ignore"):
+            M = Aq[:, None, 0] - C[:, :, 0]; M *= M
+            t = Aq[:, None, 1] - C[:, :, 1]; t *= t; M += t
+            t = Aq[:, None, 2] - C[:, :, 2]; t *= t; M += t
+            near = dt[:, 1] if second else dt[:, 0]
+            clear = (dt[:, -1] > near * (1.0 + TREE_CLEAR)) & (dt[:, -1] > 1e-150) & (dt[:, -1] < 1e150)
+        best = M.min(axis=1)
+        clear &= (M == best[:, None]).sum(axis=1) == 1
+        r = np.flatnonzero(clear)
+        idx[q[r]] = live[jt[r, np.argmin(M[r], axis=1)]]; d[q[r]] = np.sqrt(best[r])
+        if second:
+            db[q[r]] = np.sqrt(np.partition(M[r], 1, axis=1)[:, 1])
+        brute = q[~clear]
+    if len(brute) and len(live):
+        out = nn(A[brute], B, second=second)
+        d[brute], idx[brute] = out[0], out[1]
+        if second:
+            db[brute] = out[3]
+    if stats is not None:
+        stats["fallback"] = int(len(brute)) if len(live) else 0
+    info = dict(status=0 if len(live) else 1, n0_dropped=int((~okA).sum()), n1_dropped=int((~okB).sum()))
+    return (d, idx, info, db) if second else (d, idx, info)
+
 def two_level_sum(t):
     """Z6's S: every run of 1024 consecutive terms summed left to right from +0, then the run sums left to right."""
     t = np.ascontiguousarray(t, np.float64)
@@ -84,18 +129,20 @@ def median(w):
         return (lo + hi) / 2.0
 
 
-def refine_z(A, B, T=None, xy_gate=0.3, max_repeats=10, min_change=1e-6, trace=None):
-    """Contract Z.  Returns the result block as a dict.  trace: a list that receives, per repeat, dict(ind, valid, mean, xy, d, d_second)."""
+def refine_z(A, B, T=None, xy_gate=0.3, max_repeats=10, min_change=1e-6, trace=None, search=None):
+    """Contract Z.  Returns the result block as a dict.  trace: a list that receives, per repeat, dict(ind, valid, mean, xy, d, d_second).
+    search: the nearest-neighbour restatement to use, nn (the default) or nn_tree."""
+    search = nn if search is None else search
     A_ = transform(A, T)
     B = np.ascontiguousarray(B, np.float64).reshape(-1, 3)
     dz, status, repeats, n_valid, mean = 0.0, 0, 0, 0, 0.0
     n0_dropped = n1_dropped = 0
     for _ in range(max_repeats):
         if trace is None:
-            d, ind, info = nn(A_, B)
+            d, ind, info = search(A_, B)
             d_second = None
         else:
-            d, ind, info, d_second = nn(A_, B, second=True)
+            d, ind, info, d_second = search(A_, B, second=True)
         if repeats == 0:
             n0_dropped, n1_dropped = info["n0_dropped"], info["n1_dropped"]
         repeats += 1
