@@ -613,6 +613,52 @@ LR_API size_t lr_normals_scratch_bytes(int n);
 LR_API int lr_normals(const double *xyz, int n, double radius, int max_nn, double *normals_out, int32_t *info, void *scratch,
                       size_t scratch_bytes, void *stream);
 
+/* ---- f8: balanced-set selection -----------------------------------------------------------------------------------------------------
+ * lr_balanced_select replaces the rejection loop of BalancedDatasetGenerator/GenerateBalancedSet.py (select_balanced_set :544-562 around
+ * select_sample :466-507 and to_points_in_hyper_cube :456-464).  Contract S (restated in tests/balanced_cpu.py).  All
+ * arithmetic is fp64, no fused multiply-add.  State: an alive flag per candidate, n_sel[s] per session (from 0), the constant n_cands[s]
+ * (the candidates session s had at load).  For attempt k with the draw r_k[6]:
+ *   S1  m_c / M_c = the least / greatest value of column c of `fields` over the alive candidates; p_ic = (f_ic - m_c) / (M_c - m_c).
+ *   S2  q_c = (r_c - p_ic) (r_c - p_ic); s = ((((q_0 + q_1) + q_2) + q_3) + q_4) + q_5; d_i = sqrt(s), correctly rounded.
+ *   S3  the group: the alive candidates with d_i < thresh, strictly.  Empty: a miss -- the attempt is consumed, the state stays.
+ *   S4  fullness_i = (double)n_sel[s_i] / (double)n_cands[s_i]; selected: the lexicographic minimum of (fullness_i, d_i, i) over the group.
+ *   S5  n_sel[s]++, the candidate dies and its index is appended to `out`; the next attempt sees S1 over the rest.
+ * Stop (result.status): 0 = n_request candidates are selected (with n_request 0: at once, nothing consumed); 1 = the draws of this call
+ * are used up; 2 = a column's M_c - m_c is not a positive finite number (one alive candidate, a constant column, a non-finite field: the
+ * reference divides by zero there and never ends) -- before the first attempt, or straight after the commit that caused it, which is
+ * kept and counted (also when it was the n_request-th); 3 = a session id outside 0..n_sessions-1, n_cands[s] < 1 for a session that
+ * occurs, or a resumed state that does not add up; 4 = params.max_rounds rounds ran (only with max_rounds > 0).  After status 1 or 4
+ * the state is left in the caller's buffers -- alive, n_sel, out, result -- and a call with resume = 1 and the draws from
+ * result.consumed on continues exactly where this one stopped (the scratch need not be kept).                                       */
+#define LR_SELECT_MAX_ROUNDS 65536
+typedef struct lr_select_params {
+    uint32_t struct_size;        /* = sizeof(lr_select_params)                                                                      */
+    int32_t  n_request;          /* candidates to select in all, over every resumed call: 0..n                                      */
+    double   thresh;             /* 0.1 (GenerateBalancedSet.py:474); positive and finite                                           */
+    int32_t  resume;             /* 0: every candidate alive, every count 0; 1: alive, n_sel, out and result hold an earlier call's */
+    int32_t  max_rounds;         /* 0: as many rounds as the draws can need (<= 65536, else the call is refused); else 1..65536     */
+} lr_select_params;
+
+/* Device block, read and written by lr_balanced_select (136 bytes). */
+typedef struct lr_select_result {
+    int32_t  status;
+    int32_t  n_selected;         /* entries of `out`, over every resumed call                                                       */
+    int64_t  attempts, misses;   /* draws consumed / of them without a selection, over every resumed call                           */
+    int64_t  consumed;           /* draws of THIS call consumed                                                                     */
+    int32_t  rounds;             /* rounds that did something, over every resumed call                                              */
+    int32_t  rescales;           /* commits after which a column's least or greatest value was another one                          */
+    double   lo[6], hi[6];       /* m_c, M_c over the alive candidates                                                              */
+} lr_select_result;
+
+/* Caller-owned device scratch (0 when n is outside 0..4194304). */
+LR_API size_t lr_balanced_select_scratch_bytes(int n);
+/* fields [n,6] float64, session [n] int32 (dense ids 0..n_sessions-1), n_cands [n_sessions] int32, draws [n_draws,6] float64, alive [n]
+ * uint8, n_sel [n_sessions] int32, out [n_request] int32, result: all device memory.  n 0..4194304, n_sessions 1..65536, n_draws 0..2^40.
+ * No host synchronisation; capturable into a graph.                                                                                 */
+LR_API int lr_balanced_select(const double *fields, const int32_t *session, const int32_t *n_cands, int n, int n_sessions,
+                              const double *draws, long long n_draws, const lr_select_params *params, uint8_t *alive, int32_t *n_sel,
+                              int32_t *out, lr_select_result *result, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */
 LR_API int lr_workspace_timing(lr_workspace *ws, int enable);

@@ -25,6 +25,7 @@ SYMBOLS = [
     "lr_voxel_mean_scratch_bytes", "lr_voxel_mean", "lr_overlap_scratch_bytes", "lr_overlap", "lr_overlap_batch",
     "lr_nn3_scratch_bytes", "lr_nn3", "lr_refine_z_scratch_bytes", "lr_refine_z",
     "lr_bbrf_scratch_bytes", "lr_bbrf", "lr_normals_scratch_bytes", "lr_normals",
+    "lr_balanced_select_scratch_bytes", "lr_balanced_select",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -176,6 +177,24 @@ class BbrfResult(ctypes.Structure):
                 ("best_loss", ctypes.c_double), ("n_pairs_best", ctypes.c_int32), ("iters_run", ctypes.c_int32)]
 
 
+class SelectParams(ctypes.Structure):
+    """lr_select_params with the reference's threshold (GenerateBalancedSet.py:474) as default; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_request", ctypes.c_int32), ("thresh", ctypes.c_double), ("resume", ctypes.c_int32),
+                ("max_rounds", ctypes.c_int32)]
+    DEFAULTS = dict(n_request=0, thresh=0.1, resume=0, max_rounds=0)
+
+    def __init__(self, **kw):
+        kw.pop("struct_size", None)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
+
+
+class SelectResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("n_selected", ctypes.c_int32), ("attempts", ctypes.c_int64), ("misses", ctypes.c_int64),
+                ("consumed", ctypes.c_int64), ("rounds", ctypes.c_int32), ("rescales", ctypes.c_int32), ("lo", ctypes.c_double * 6),
+                ("hi", ctypes.c_double * 6)]
+
+
+assert ctypes.sizeof(SelectParams) == 24 and ctypes.sizeof(SelectResult) == 136
 assert ctypes.sizeof(BbrfParams) == 56 and ctypes.sizeof(BbrfResult) == 280
 assert ctypes.sizeof(Nn3Params) == 16 and ctypes.sizeof(RefineZParams) == 32 and ctypes.sizeof(RefineZResult) == 40
 assert ctypes.sizeof(OverlapParams) == 24 and ctypes.sizeof(OverlapResult) == 40
@@ -275,6 +294,9 @@ def lib():
         L.lr_normals_scratch_bytes.restype = ctypes.c_size_t
         L.lr_normals_scratch_bytes.argtypes = [ci]
         L.lr_normals.argtypes = [vp, ci, dp, ci, vp, vp, vp, ctypes.c_size_t, vp]
+        L.lr_balanced_select_scratch_bytes.restype = ctypes.c_size_t
+        L.lr_balanced_select_scratch_bytes.argtypes = [ci]
+        L.lr_balanced_select.argtypes = [vp, vp, vp, ci, ci, vp, ctypes.c_longlong, ctypes.POINTER(SelectParams), vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

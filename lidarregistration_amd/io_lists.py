@@ -23,7 +23,8 @@ def read_pair_list(path):
     with open(path) as f:
         header = f.readline().split()
     rows = np.loadtxt(path, skiprows=1, ndmin=2)
-    assert header[:3] == ["session_ind", "i", "j"] and header[3] == "mot0", f"unexpected header in {path}"
+    # the published lists name the index columns `i j`, the generator's writer (GenerateBalancedSet.py:397-398, balanced.save_set) `src_ind tgt_ind`
+    assert header[0] == "session_ind" and header[1:3] in (["i", "j"], ["src_ind", "tgt_ind"]) and header[3] == "mot0", f"unexpected header in {path}"
     overlap = rows[:, header.index("overlap")] if "overlap" in header else None
     return dict(session=rows[:, 0].astype(np.int64), src=rows[:, 1].astype(np.int64), tgt=rows[:, 2].astype(np.int64),
                 T_gt=rows[:, 3:19].reshape(-1, 4, 4).copy(), overlap=overlap)

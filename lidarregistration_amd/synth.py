@@ -113,6 +113,21 @@ def make_pair_dev(N=30000, D=32, rho=0.5, s=1.2, seed=51, device=None, noise=0.0
     return dict(xyz0=xyz0.contiguous(), xyz1=xyz1.contiguous(), feats0=F0.contiguous(), feats1=F1.contiguous(), T_gt=T)
 
 
+def _scan_frame(rng, n, pose, reach):
+    """One frame of make_scan_pair's scene seen from `pose` (4x4, scene -> frame), in the frame's coordinates."""
+    r = reach * rng.uniform(size=n) ** 2 + 1.5                       # density falls with range
+    phi = rng.uniform(0, 2 * np.pi, size=n)
+    local = np.stack([r * np.cos(phi), r * np.sin(phi), np.zeros(n)], axis=1)
+    world = (local - pose[:3, 3]) @ pose[:3, :3]                      # inverse of `pose`: scene coordinates of the returns
+    x, y = world[:, 0], world[:, 1]
+    z = 0.3 * np.sin(0.2 * x) * np.cos(0.15 * y) - 1.7
+    wall = rng.uniform(size=n) < 0.35
+    z = np.where(wall, z + rng.uniform(0, 6, size=n), z)
+    x = np.where(wall, np.round(x / 7.0) * 7.0, x)
+    world = np.stack([x, y, z], axis=1) + rng.normal(scale=0.02, size=(n, 3))
+    return world @ pose[:3, :3].T + pose[:3, 3]
+
+
 def make_scan_pair(n0=120000, n1=None, seed=51, forward=8.0, yaw_deg=5.0, reach=80.0):
     """Two raw LiDAR-like frames (float64, like the reference's cloud cache) of one scene seen from two poses `forward` metres and `yaw_deg`
     apart, and the 4x4 motion frame 0 -> frame 1: range-dependent density (most returns near the sensor), a rolling ground, facades on a
@@ -124,17 +139,53 @@ def make_scan_pair(n0=120000, n1=None, seed=51, forward=8.0, yaw_deg=5.0, reach=
     T[:3, :3] = [[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]]
     T[:3, 3] = [-forward, 0.3, 0.0]
 
-    def frame(n, pose):
-        r = reach * rng.uniform(size=n) ** 2 + 1.5                       # density falls with range
-        phi = rng.uniform(0, 2 * np.pi, size=n)
-        local = np.stack([r * np.cos(phi), r * np.sin(phi), np.zeros(n)], axis=1)
-        world = (local - pose[:3, 3]) @ pose[:3, :3]                      # inverse of `pose`: scene coordinates of the returns
-        x, y = world[:, 0], world[:, 1]
-        z = 0.3 * np.sin(0.2 * x) * np.cos(0.15 * y) - 1.7
-        wall = rng.uniform(size=n) < 0.35
-        z = np.where(wall, z + rng.uniform(0, 6, size=n), z)
-        x = np.where(wall, np.round(x / 7.0) * 7.0, x)
-        world = np.stack([x, y, z], axis=1) + rng.normal(scale=0.02, size=(n, 3))
-        return world @ pose[:3, :3].T + pose[:3, 3]
+    return _scan_frame(rng, n0, np.eye(4), reach), _scan_frame(rng, n1, T, reach), T
 
-    return frame(n0, np.eye(4)), frame(n1, T), T
+
+class SyntheticSessions:
+    """A dataset of make_session drives with the members the balanced-set generator asks of a full dataset (balanced.py): load_PC,
+    get_relative_motion, session_length, indexing_from, total_num_of_clouds, sessions_list, time_step, name, phase."""
+
+    def __init__(self, sessions, name="Synthetic", phase="test", time_step=0.1):
+        self.sessions = dict(sessions)                  # session index -> make_session's dict
+        self.sessions_list = list(self.sessions)
+        self.name, self.phase, self.time_step = name, phase, float(time_step)
+
+    def indexing_from(self):
+        return 0
+
+    def session_length(self, session_ind):
+        return len(self.sessions[session_ind]["clouds"])
+
+    def total_num_of_clouds(self):
+        return sum(len(s["clouds"]) for s in self.sessions.values())
+
+    def load_PC(self, session_ind, i):
+        return self.sessions[session_ind]["clouds"][i]
+
+    def get_relative_motion(self, session_ind, i, j):
+        """4x4 motion frame i -> frame j."""
+        poses = self.sessions[session_ind]["poses"]
+        return poses[j] @ np.linalg.inv(poses[i])
+
+
+def make_session(n_frames=40, n_points=6000, seed=51, step=2.5, yaw_step_deg=1.5, reach=80.0):
+    """A short synthetic drive: n_frames scans (float64 [n_points,3]) of make_scan_pair's static scene from poses `step` metres and
+    `yaw_step_deg` apart along a curve whose curvature swings slowly, with a little pitch, roll and heave.  dict(clouds, poses): poses[i] maps scene coordinates to frame i, so
+    frame i -> frame j is poses[j] @ inv(poses[i]).  SyntheticSessions({0: make_session(...)}) is a dataset without any download."""
+    rng = np.random.default_rng(seed)
+    clouds, poses = [], []
+    pose = np.eye(4)
+    for i in range(n_frames):
+        poses.append(pose.copy())
+        clouds.append(_scan_frame(rng, n_points, pose, reach))
+        a = np.radians(yaw_step_deg * np.cos(2.0 * np.pi * i / 25.0))
+        b, c = np.radians(0.3 * np.sin(0.5 * i)), np.radians(0.2 * np.cos(0.9 * i))      # a little pitch and roll: no motion field stays constant
+        Rz = np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+        Ry = np.array([[np.cos(b), 0, np.sin(b)], [0, 1, 0], [-np.sin(b), 0, np.cos(b)]])
+        Rx = np.array([[1, 0, 0], [0, np.cos(c), -np.sin(c)], [0, np.sin(c), np.cos(c)]])
+        hop = np.eye(4)
+        hop[:3, :3] = Rz @ Ry @ Rx
+        hop[:3, 3] = [-step, 0.02 * np.sin(0.7 * i), 0.03 * np.sin(0.4 * i)]
+        pose = hop @ pose
+    return dict(clouds=clouds, poses=poses)
