@@ -84,7 +84,16 @@ class PairParams(ctypes.Structure):
             self.ransac.struct_size = ctypes.sizeof(RansacParams)
 
 
-class TeaserParams(ctypes.Structure):
+class KeywordParams(ctypes.Structure):
+    """A params struct filled by keyword over its DEFAULTS; struct_size (always this build's size: a passed one is dropped) is filled in."""
+    DEFAULTS = {}
+
+    def __init__(self, **kw):
+        kw.pop("struct_size", None)
+        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
+
+
+class TeaserParams(KeywordParams):
     """lr_teaser_params with the reference's settings (TEASER_plus_plus.py:78-93) as defaults; struct_size is filled in."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("max_iterations", ctypes.c_int32), ("noise_bound", ctypes.c_double),
                 ("cbar2", ctypes.c_double), ("kcore_threshold", ctypes.c_double), ("gnc_factor", ctypes.c_double),
@@ -92,10 +101,6 @@ class TeaserParams(ctypes.Structure):
                 ("rotation_tim_graph", ctypes.c_int32), ("estimate_scaling", ctypes.c_int32)]
     DEFAULTS = dict(max_iterations=10000, noise_bound=0.3, cbar2=1.0, kcore_threshold=0.5, gnc_factor=1.4, cost_threshold=1e-16,
                     node_budget=10 ** 7, time_budget_ms=10000.0)
-
-    def __init__(self, **kw):
-        kw.pop("struct_size", None)
-        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
 
 
 class TeaserResult(ctypes.Structure):
@@ -105,15 +110,11 @@ class TeaserResult(ctypes.Structure):
                 ("pad1", ctypes.c_int32)]
 
 
-class SmParams(ctypes.Structure):
+class SmParams(KeywordParams):
     """lr_sm_params with the settings the reference runs SM() with (baseline_KITTI.py:51-52) as defaults; struct_size is filled in."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("iterations", ctypes.c_int32), ("inlier_threshold", ctypes.c_double),
                 ("top_ratio", ctypes.c_double)]
     DEFAULTS = dict(iterations=10, inlier_threshold=0.6, top_ratio=0.05)
-
-    def __init__(self, **kw):
-        kw.pop("struct_size", None)
-        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
 
 
 class SmResult(ctypes.Structure):
@@ -121,14 +122,10 @@ class SmResult(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("weight_sum", ctypes.c_double)]
 
 
-class OverlapParams(ctypes.Structure):
+class OverlapParams(KeywordParams):
     """lr_overlap_params with the reference's settings (GenerateBalancedSet.py:171,175) as defaults; struct_size is filled in."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("voxel_size", ctypes.c_double), ("radius", ctypes.c_double)]
     DEFAULTS = dict(voxel_size=1.0, radius=0.0)
-
-    def __init__(self, **kw):
-        kw.pop("struct_size", None)
-        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
 
 
 class OverlapResult(ctypes.Structure):
@@ -136,24 +133,16 @@ class OverlapResult(ctypes.Structure):
                 ("n0_dropped", ctypes.c_int32), ("n1_dropped", ctypes.c_int32), ("frac", ctypes.c_double), ("frac_sym", ctypes.c_double)]
 
 
-class Nn3Params(ctypes.Structure):
+class Nn3Params(KeywordParams):
     """lr_nn3_params; cell 0 = automatic (the result does not depend on it); struct_size is filled in."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("cell", ctypes.c_double)]
 
-    def __init__(self, **kw):
-        kw.pop("struct_size", None)
-        super().__init__(struct_size=ctypes.sizeof(type(self)), **kw)
 
-
-class RefineZParams(ctypes.Structure):
+class RefineZParams(KeywordParams):
     """lr_refine_z_params with the reference's settings (GenerateBalancedSet.py:264-265, voxel 0.3 at :298) as defaults; struct_size is filled in."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("max_repeats", ctypes.c_int32), ("xy_gate", ctypes.c_double), ("min_change", ctypes.c_double),
                 ("cell", ctypes.c_double)]
     DEFAULTS = dict(max_repeats=10, xy_gate=0.3, min_change=1e-6, cell=0.0)
-
-    def __init__(self, **kw):
-        kw.pop("struct_size", None)
-        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
 
 
 class RefineZResult(ctypes.Structure):
@@ -161,15 +150,11 @@ class RefineZResult(ctypes.Structure):
                 ("n1_dropped", ctypes.c_int32), ("reserved", ctypes.c_int32), ("dz", ctypes.c_double), ("last_step", ctypes.c_double)]
 
 
-class BbrfParams(ctypes.Structure):
+class BbrfParams(KeywordParams):
     """lr_bbrf_params with the reference's settings (BBR_F.py:271-275, torch.optim.Adam's defaults) as defaults; struct_size is filled in."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_iter", ctypes.c_int32), ("angles_lr", ctypes.c_double), ("trans_lr", ctypes.c_double),
                 ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double), ("cell", ctypes.c_double)]
     DEFAULTS = dict(n_iter=100, angles_lr=2e-4, trans_lr=2e-4, beta1=0.9, beta2=0.999, eps=1e-8, cell=0.0)
-
-    def __init__(self, **kw):
-        kw.pop("struct_size", None)
-        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
 
 
 class BbrfResult(ctypes.Structure):
@@ -177,15 +162,11 @@ class BbrfResult(ctypes.Structure):
                 ("best_loss", ctypes.c_double), ("n_pairs_best", ctypes.c_int32), ("iters_run", ctypes.c_int32)]
 
 
-class SelectParams(ctypes.Structure):
+class SelectParams(KeywordParams):
     """lr_select_params with the reference's threshold (GenerateBalancedSet.py:474) as default; struct_size is filled in."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_request", ctypes.c_int32), ("thresh", ctypes.c_double), ("resume", ctypes.c_int32),
                 ("max_rounds", ctypes.c_int32)]
     DEFAULTS = dict(n_request=0, thresh=0.1, resume=0, max_rounds=0)
-
-    def __init__(self, **kw):
-        kw.pop("struct_size", None)
-        super().__init__(struct_size=ctypes.sizeof(type(self)), **{**self.DEFAULTS, **kw})
 
 
 class SelectResult(ctypes.Structure):
@@ -232,6 +213,9 @@ def lib():
             raise LidarRegError(f"cannot load {LIB_PATH}: {e}") from e
         L.lr_last_error.restype = ctypes.c_char_p
         L.lr_workspace_bytes.restype = ctypes.c_size_t
+        for name in SYMBOLS:
+            if name.endswith("_scratch_bytes"):
+                getattr(L, name).restype = ctypes.c_size_t
         L.lr_workspace_bytes.argtypes = [ctypes.c_void_p]
         L.lr_workspace_poison.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.lr_workspace_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
@@ -253,7 +237,6 @@ def lib():
         L.lr_workspace_lists_batch.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
         L.lr_inlier_mask.argtypes = [vp, vp, vp, ci, vp, ctypes.c_float, vp, vp, vp]
         L.lr_workspace_mask_at.argtypes = [vp, ci, vp, vp, ci, ctypes.c_float, vp, vp, vp]
-        L.lr_voxel_dedup_scratch_bytes.restype = ctypes.c_size_t
         L.lr_voxel_dedup_scratch_bytes.argtypes = [ci]
         L.lr_voxel_dedup.argtypes = [vp, ci, vp, vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_workspace_create_batch.argtypes = [ctypes.POINTER(ctypes.c_void_p), ci, ci, ci, ci, ci]
@@ -264,37 +247,28 @@ def lib():
         L.lr_workspace_timing.argtypes = [vp, ci]
         if hasattr(L, "lr_workspace_clock"):      # (absent only from older builds loaded through the LIDARREG_LIB development hook)
             L.lr_workspace_clock.argtypes = [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong), ci]
-        L.lr_teaser_scratch_bytes.restype = ctypes.c_size_t
         L.lr_teaser_scratch_bytes.argtypes = [ci]
         L.lr_teaser.argtypes = [vp, vp, ci, vp, ctypes.POINTER(TeaserParams), vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_teaser_batch.argtypes = [ci, pp, pp, ip, pp, ctypes.POINTER(TeaserParams), vp, pp, vp, ctypes.c_size_t, vp]
         L.lr_teaser_timing.argtypes = [ci]
         L.lr_teaser_stage_times.argtypes = [ctypes.POINTER(ctypes.c_float * 4)]
-        L.lr_sm_scratch_bytes.restype = ctypes.c_size_t
         L.lr_sm_scratch_bytes.argtypes = [ci]
         L.lr_sm.argtypes = [vp, vp, ci, vp, ctypes.POINTER(SmParams), vp, vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_sm_batch.argtypes = [ci, pp, pp, ip, pp, ctypes.POINTER(SmParams), vp, pp, pp, vp, ctypes.c_size_t, vp]
         dp = ctypes.c_double
-        L.lr_voxel_mean_scratch_bytes.restype = ctypes.c_size_t
         L.lr_voxel_mean_scratch_bytes.argtypes = [ci]
         L.lr_voxel_mean.argtypes = [vp, ci, vp, dp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
-        L.lr_overlap_scratch_bytes.restype = ctypes.c_size_t
         L.lr_overlap_scratch_bytes.argtypes = [ci, ci]
         L.lr_overlap.argtypes = [vp, ci, vp, ci, vp, ctypes.POINTER(OverlapParams), vp, vp, ctypes.c_size_t, vp]
         L.lr_overlap_batch.argtypes = [ci, pp, ip, pp, ip, pp, ctypes.POINTER(OverlapParams), vp, vp, ctypes.c_size_t, vp]
-        L.lr_nn3_scratch_bytes.restype = ctypes.c_size_t
         L.lr_nn3_scratch_bytes.argtypes = [ci, ci]
         L.lr_nn3.argtypes = [vp, ci, vp, ci, ctypes.POINTER(Nn3Params), vp, vp, vp, vp, ctypes.c_size_t, vp]
-        L.lr_refine_z_scratch_bytes.restype = ctypes.c_size_t
         L.lr_refine_z_scratch_bytes.argtypes = [ci, ci]
         L.lr_refine_z.argtypes = [vp, ci, vp, ci, vp, ctypes.POINTER(RefineZParams), vp, vp, ctypes.c_size_t, vp]
-        L.lr_bbrf_scratch_bytes.restype = ctypes.c_size_t
         L.lr_bbrf_scratch_bytes.argtypes = [ci, ci, ci]
         L.lr_bbrf.argtypes = [vp, vp, ci, vp, vp, ci, ctypes.POINTER(BbrfParams), vp, vp, vp, ctypes.c_size_t, vp]
-        L.lr_normals_scratch_bytes.restype = ctypes.c_size_t
         L.lr_normals_scratch_bytes.argtypes = [ci]
         L.lr_normals.argtypes = [vp, ci, dp, ci, vp, vp, vp, ctypes.c_size_t, vp]
-        L.lr_balanced_select_scratch_bytes.restype = ctypes.c_size_t
         L.lr_balanced_select_scratch_bytes.argtypes = [ci]
         L.lr_balanced_select.argtypes = [vp, vp, vp, ci, ci, vp, ctypes.c_longlong, ctypes.POINTER(SelectParams), vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]

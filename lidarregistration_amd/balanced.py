@@ -20,9 +20,9 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import _ext, overlap
+from . import _ext, devmem, overlap
+from .devmem import as_dict, ptr, read_struct
 from .matching import _device, _stream
-from .overlap import _scratch
 
 THRESH = 0.1                # GenerateBalancedSet.py:474
 SELECT_T = 1024             # attempts per round of lr_balanced_select (SEL_T in csrc/lr_select.hip)
@@ -72,13 +72,6 @@ def to_points_in_hyper_cube(cands):
 
 
 # ---- the selection ----------------------------------------------------------------------------------------------------------------------
-def _result(state):
-    r = _ext.SelectResult.from_buffer_copy(state["res"].cpu().numpy().tobytes())
-    out = {name: getattr(r, name) for name, _ in _ext.SelectResult._fields_}
-    out["lo"], out["hi"] = np.array(r.lo), np.array(r.hi)
-    return out
-
-
 def select_balanced_launch(fields, session, n_cands, n_request, draws, state=None, thresh=THRESH, max_rounds=0, poison=None):
     """The device call of select_balanced_dev without the read-back (no host synchronisation: capturable into a graph).  fields [n,6]
     float64, session [n] int32, n_cands [S] int32, draws [k,6] float64: device tensors are used as they are.  Returns the state: a dict of
@@ -94,8 +87,7 @@ def select_balanced_launch(fields, session, n_cands, n_request, draws, state=Non
                      out=torch.full((max(int(n_request), 1),), -1, dtype=torch.int32, device=dev),
                      res=torch.zeros(ctypes.sizeof(_ext.SelectResult), dtype=torch.uint8, device=dev), resume=0)
     p = _ext.SelectParams(n_request=int(n_request), thresh=float(thresh), resume=int(state["resume"]), max_rounds=int(max_rounds))
-    scratch = _scratch(L.lr_balanced_select_scratch_bytes(n), dev, poison)
-    ptr = lambda x, k: x.data_ptr() if k else None
+    scratch = devmem.scratch(L.lr_balanced_select_scratch_bytes(n), dev, poison)
     _ext.check(L.lr_balanced_select(ptr(f, n), ptr(s, n), nc.data_ptr(), n, ns, ptr(d, nd), nd, ctypes.byref(p), state["alive"].data_ptr(),
                                     state["n_sel"].data_ptr(), state["out"].data_ptr(), state["res"].data_ptr(), scratch.data_ptr(), scratch.numel(),
                                     _stream()))
@@ -110,7 +102,7 @@ def select_balanced_dev(fields, session, n_cands, n_request, draws, state=None, 
     n_selected, attempts, misses, consumed, rounds, rescales, lo, hi) and order: the original indices selected so far, in selection
     order (numpy int32)."""
     state = select_balanced_launch(fields, session, n_cands, n_request, draws, state, thresh, max_rounds, poison)
-    state.update(_result(state))
+    state.update(as_dict(read_struct(state["res"], _ext.SelectResult)))
     state["order"] = state["out"][:state["n_selected"]].cpu().numpy()
     return state
 

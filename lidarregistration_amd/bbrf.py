@@ -10,32 +10,25 @@ from time import time
 import numpy as np
 import torch
 
-from . import _ext
+from . import _ext, devmem
+from .devmem import as_dict, f64, ptr, read_struct
 from .matching import _device, _stream
-from .overlap import _f64, _scratch, voxel_down_sample
+from .overlap import voxel_down_sample
 
 NUM_SAMPLES = 30000         # BBR_F.py:269
 REFINE_VOXEL = 0.3          # the refinement tester's voxel_size
 
 
-def _fields(struct):
-    out = {}
-    for name, _ in struct._fields_:
-        v = getattr(struct, name)
-        out[name] = np.array(v, np.float64).reshape(4, 4) if name in ("T", "B_to_A") else v
-    return out
-
-
 def normals_dev(X, radius=0.01, max_nn=13, poison=None):
     """lr_normals of X [n,3] (float64).  Returns (normals [n,3] float64 device tensor, dict(status, n_dropped, n_default))."""
     dev = _device()
-    x = _f64(X, dev)
+    x = f64(X, dev)
     n = int(x.shape[0])
     L = _ext.lib()
     out = torch.empty((max(n, 1), 3), dtype=torch.float64, device=dev)
     info = torch.empty(4, dtype=torch.int32, device=dev)
-    scratch = _scratch(L.lr_normals_scratch_bytes(n), dev, poison)
-    _ext.check(L.lr_normals(x.data_ptr() if n else None, n, float(radius), int(max_nn), out.data_ptr(), info.data_ptr(),
+    scratch = devmem.scratch(L.lr_normals_scratch_bytes(n), dev, poison)
+    _ext.check(L.lr_normals(ptr(x, n), n, float(radius), int(max_nn), out.data_ptr(), info.data_ptr(),
                             scratch.data_ptr(), scratch.numel(), _stream()))
     status, dropped, default, _ = (int(v) for v in info.cpu())
     return out[:n], dict(status=status, n_dropped=dropped, n_default=default)
@@ -51,19 +44,17 @@ def bbr_f_dev(A, B, nA, nB, poison=None, want_log=True, **params):
     """lr_bbrf on tensors or arrays A, nA [n0,3], B, nB [n1,3] (evaluated in float64); params: the fields of lr_bbrf_params.  Returns
     (result dict with T and B_to_A as 4x4 numpy arrays, log [n_iter, 8] float64 device tensor or None)."""
     dev = _device()
-    a, b, na, nb = _f64(A, dev), _f64(B, dev), _f64(nA, dev), _f64(nB, dev)
+    a, b, na, nb = f64(A, dev), f64(B, dev), f64(nA, dev), f64(nB, dev)
     n0, n1 = int(a.shape[0]), int(b.shape[0])
     assert na.shape[0] == n0 and nb.shape[0] == n1, "one normal per point"
     L = _ext.lib()
     p = _ext.BbrfParams(**params)
     res = torch.zeros(ctypes.sizeof(_ext.BbrfResult), dtype=torch.uint8, device=dev)
     log = torch.full((max(int(p.n_iter), 1), 8), math.nan, dtype=torch.float64, device=dev) if want_log else None
-    scratch = _scratch(L.lr_bbrf_scratch_bytes(n0, n1, max(1, min(int(p.n_iter), 1000))), dev, poison)
-    ptr = lambda t, n: t.data_ptr() if n else None
+    scratch = devmem.scratch(L.lr_bbrf_scratch_bytes(n0, n1, max(1, min(int(p.n_iter), 1000))), dev, poison)
     _ext.check(L.lr_bbrf(ptr(a, n0), ptr(na, n0), n0, ptr(b, n1), ptr(nb, n1), n1, ctypes.byref(p), res.data_ptr(),
-                         None if log is None else log.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
-    r = _ext.BbrfResult.from_buffer_copy(res.cpu().numpy().tobytes())
-    return _fields(r), log
+                         ptr(log), scratch.data_ptr(), scratch.numel(), _stream()))
+    return as_dict(read_struct(res, _ext.BbrfResult)), log
 
 
 def _downsample(X, X_normals, num_samples):

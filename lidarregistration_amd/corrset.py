@@ -11,13 +11,9 @@ import numpy as np
 import torch
 
 from . import FR as fr
-from . import _ext, harness, ransac
+from . import _ext, devmem, harness, ransac
+from .devmem import ptr, read_struct
 from .matching import _f32, _stream
-
-
-def scratch(nbytes, device):
-    """256-byte aligned device scratch (torch's allocator aligns to 512)."""
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
 @dataclass(frozen=True)
@@ -47,14 +43,11 @@ class BatchCall:
         self.tgts = [_f32(t).reshape(-1, 3) for t in tgts]
         dev = self.srcs[0].device
         self.ms = [int(s.shape[0]) for s in self.srcs] if ms is None else [int(v) for v in ms]
-        self.scratch = scratch(getattr(L, solver.scratch_bytes)(max(self.ms)) * self.n, dev)
-        if poison is not None:
-            self.scratch.fill_(int(poison))
+        self.scratch = devmem.scratch(getattr(L, solver.scratch_bytes)(max(self.ms)) * self.n, dev, poison)
         self.res = torch.zeros(ctypes.sizeof(solver.result) * self.n, dtype=torch.uint8, device=dev)
         self.outs = [[torch.full((max(m, 1),), fill, dtype=dt, device=dev) for m in self.ms] if outputs else None for dt, fill in solver.outputs]
         self.m_devs = m_devs
         self.params = solver.params(**kw)
-        ptr = lambda t: None if t is None else t.data_ptr()
         if single:
             assert self.n == 1
             self._fn = getattr(L, solver.single)
@@ -81,9 +74,8 @@ class BatchCall:
 
     def results(self):
         """[(T 4x4 float64, info dict)] per pair (the copy synchronises with the current stream)."""
-        size = ctypes.sizeof(self.solver.result)
-        host = self.res.cpu().numpy().tobytes()
-        rs = [self.solver.result.from_buffer_copy(host[k * size:(k + 1) * size]) for k in range(self.n)]
+        host = self.res.cpu()
+        rs = [read_struct(host, self.solver.result, k) for k in range(self.n)]
         return [(np.array(r.T[:], np.float64).reshape(4, 4), self.solver.info(r)) for r in rs]
 
 

@@ -11,7 +11,6 @@
 // step (run sums in order, loss, Adam, log row, running argmin, stop flags, the next W).  The control block's first word ends the loop:
 // every later launch, the grid's and the search's included, returns at its first instruction.  No floating-point atomic; every word read
 // was written by a kernel of the call.
-#include "lr_corrset.h"
 #include "lr_prims.h"
 #include "lr_nn3.h"
 #include <math.h>
@@ -46,18 +45,18 @@ static size_t bb_make_layout(bb_layout *L, size_t n0, size_t n1)
     const size_t m0 = n0 > 0 ? n0 : 1, m1 = n1 > 0 ? n1 : 1;
     nn_layout nl;
     size_t o = 1024;
-    L->Bp = o;      o += cs_al(m1 * 24);
-    L->nBp = o;     o += cs_al(m1 * 24);
-    L->f = o;       o += cs_al(m0 * 4);
-    L->r = o;       o += cs_al(m1 * 4);
-    L->part = o;    o += cs_al((m0 / NN_RUN + 1) * 64);
+    L->Bp = o;      o += lr_al(m1 * 24);
+    L->nBp = o;     o += lr_al(m1 * 24);
+    L->f = o;       o += lr_al(m0 * 4);
+    L->r = o;       o += lr_al(m1 * 4);
+    L->part = o;    o += lr_al((m0 / NN_RUN + 1) * 64);
     L->arena_f = o; o += nn_make_layout(&nl, n0, n1, 0);         // queries A, target B'
     L->arena_b = o; o += nn_make_layout(&nl, n1, n0, 0);         // queries B', target A
     L->end = o;
     return o;
 }
 
-__device__ __forceinline__ bb_ctl *bb_c(const bb_args &g) { return cs_ptr<bb_ctl>(g, 0, 0); }
+__device__ __forceinline__ bb_ctl *bb_c(const bb_args &g) { return lr_ptr<bb_ctl>(g, 0, 0); }
 
 // ---- B2 ----------------------------------------------------------------------------------------------------------------------------
 #define BB_F3 6.0
@@ -180,7 +179,7 @@ __global__ void __launch_bounds__(256) bb_xform_kernel(bb_args g)
     if (j >= g.n1) return;
     const double x = g.B[3 * (size_t)j], y = g.B[3 * (size_t)j + 1], z = g.B[3 * (size_t)j + 2];
     const double nx = g.nB[3 * (size_t)j], ny = g.nB[3 * (size_t)j + 1], nz = g.nB[3 * (size_t)j + 2];
-    double *Bp = cs_ptr<double>(g, 0, g.L.Bp) + 3 * (size_t)j, *nBp = cs_ptr<double>(g, 0, g.L.nBp) + 3 * (size_t)j;
+    double *Bp = lr_ptr<double>(g, 0, g.L.Bp) + 3 * (size_t)j, *nBp = lr_ptr<double>(g, 0, g.L.nBp) + 3 * (size_t)j;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         Bp[a] = bb_row(c->W, a, x, y, z) + c->t[a];
@@ -195,8 +194,8 @@ __global__ void __launch_bounds__(256) bb_pair_kernel(bb_args g)
     if (c->done) return;
     const int lane = threadIdx.x & 63, run = blockIdx.x * 4 + (threadIdx.x >> 6), nruns = (g.n0 + NN_RUN - 1) / NN_RUN;
     if (run >= nruns) return;
-    const int32_t *f = cs_ptr<int32_t>(g, 0, g.L.f), *r = cs_ptr<int32_t>(g, 0, g.L.r);
-    const double *Bp = cs_ptr<double>(g, 0, g.L.Bp), *nBp = cs_ptr<double>(g, 0, g.L.nBp);
+    const int32_t *f = lr_ptr<int32_t>(g, 0, g.L.f), *r = lr_ptr<int32_t>(g, 0, g.L.r);
+    const double *Bp = lr_ptr<double>(g, 0, g.L.Bp), *nBp = lr_ptr<double>(g, 0, g.L.nBp);
     const int begin = run * NN_RUN, end = begin + NN_RUN < g.n0 ? begin + NN_RUN : g.n0;
     double sum[7] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
     int count = 0;
@@ -237,7 +236,7 @@ __global__ void __launch_bounds__(256) bb_pair_kernel(bb_args g)
         }
     }
     if (lane == 0) {
-        double *part = cs_ptr<double>(g, 0, g.L.part) + 8 * (size_t)run;
+        double *part = lr_ptr<double>(g, 0, g.L.part) + 8 * (size_t)run;
 #pragma unroll
         for (int k = 0; k < 7; ++k) part[k] = sum[k];
         part[7] = (double)count;
@@ -250,7 +249,7 @@ __global__ void __launch_bounds__(64) bb_step_kernel(bb_args g, int k)
     bb_ctl *c = bb_c(g);
     if (c->done) return;
     const int lane = threadIdx.x, nruns = (g.n0 + NN_RUN - 1) / NN_RUN;
-    const double *part = cs_ptr<double>(g, 0, g.L.part);
+    const double *part = lr_ptr<double>(g, 0, g.L.part);
     double sum[8] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
     for (int base = 0; base < nruns; base += 64) {
         const int cnt = nruns - base < 64 ? nruns - base : 64;
@@ -345,8 +344,8 @@ __global__ void __launch_bounds__(256) nm_kernel(nm_args a)
         double nrm[3] = { 0.0, 0.0, 1.0 };
         bad = !(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]));
         if (!bad) {
-            const int32_t *table = cs_ptr<int32_t>(g, 0, g.L.table), *pidx = cs_ptr<int32_t>(g, 0, g.L.pidx);
-            const double *pts = cs_ptr<double>(g, 0, g.L.pts);
+            const int32_t *table = lr_ptr<int32_t>(g, 0, g.L.table), *pidx = lr_ptr<int32_t>(g, 0, g.L.pidx);
+            const double *pts = lr_ptr<double>(g, 0, g.L.pts);
             const int dx = c->dim[0], dy = c->dim[1], dz = c->dim[2];
             const int cx = nn_cell(q[0], c->blo[0], c->cell, dx), cy = nn_cell(q[1], c->blo[1], c->cell, dy), cz = nn_cell(q[2], c->blo[2], c->cell, dz);
             const int z0 = cz > 0 ? cz - 1 : 0, z1 = cz + 1 < dz ? cz + 1 : dz - 1, y0 = cy > 0 ? cy - 1 : 0, y1 = cy + 1 < dy ? cy + 1 : dy - 1;
@@ -428,33 +427,28 @@ extern "C" size_t lr_normals_scratch_bytes(int n)
     return nn_make_layout(&L, (size_t)n, (size_t)n, 0);
 }
 
-#define BB_REQUIRE(cond, msg) do { if (!(cond)) { lr_set_error("%s: " msg, who); return LR_EINVAL; } } while (0)
-
 extern "C" int lr_bbrf(const double *xyzA, const double *nrmA, int n0, const double *xyzB, const double *nrmB, int n1,
                        const lr_bbrf_params *p, lr_bbrf_result *result, double *log, void *scratch, size_t scratch_bytes, void *stream)
 {
     const char *who = "lr_bbrf";
     LR_CHECK_STRUCT_SIZE(lr_bbrf_params, p, who);
-    BB_REQUIRE(p->n_iter >= 1 && p->n_iter <= BB_MAX_ITER, "n_iter must lie in 1..1000");
-    BB_REQUIRE(p->angles_lr > 0.0 && isfinite(p->angles_lr), "angles_lr must be positive and finite");
-    BB_REQUIRE(p->trans_lr > 0.0 && isfinite(p->trans_lr), "trans_lr must be positive and finite");
-    BB_REQUIRE(p->beta1 >= 0.0 && p->beta1 < 1.0, "beta1 must lie in [0, 1)");
-    BB_REQUIRE(p->beta2 >= 0.0 && p->beta2 < 1.0, "beta2 must lie in [0, 1)");
-    BB_REQUIRE(p->eps > 0.0 && isfinite(p->eps), "eps must be positive and finite");
-    BB_REQUIRE(p->cell == 0.0 || (p->cell > 0.0 && isfinite(p->cell)), "cell must be 0 (automatic) or positive and finite");
-    BB_REQUIRE(n0 >= 0 && n0 <= NN_MAX_N && n1 >= 0 && n1 <= NN_MAX_N, "n0 / n1 must lie in 0..4194304");
-    BB_REQUIRE(n0 == 0 || xyzA, "null xyzA");
-    BB_REQUIRE(n0 == 0 || nrmA, "null nrmA");
-    BB_REQUIRE(n1 == 0 || xyzB, "null xyzB");
-    BB_REQUIRE(n1 == 0 || nrmB, "null nrmB");
-    BB_REQUIRE(result, "null result");
-    BB_REQUIRE(scratch, "null scratch");
+    LR_REFUSE_UNLESS(p->n_iter >= 1 && p->n_iter <= BB_MAX_ITER, LR_EINVAL, "n_iter must lie in 1..1000");
+    LR_REFUSE_UNLESS(p->angles_lr > 0.0 && isfinite(p->angles_lr), LR_EINVAL, "angles_lr must be positive and finite");
+    LR_REFUSE_UNLESS(p->trans_lr > 0.0 && isfinite(p->trans_lr), LR_EINVAL, "trans_lr must be positive and finite");
+    LR_REFUSE_UNLESS(p->beta1 >= 0.0 && p->beta1 < 1.0, LR_EINVAL, "beta1 must lie in [0, 1)");
+    LR_REFUSE_UNLESS(p->beta2 >= 0.0 && p->beta2 < 1.0, LR_EINVAL, "beta2 must lie in [0, 1)");
+    LR_REFUSE_UNLESS(p->eps > 0.0 && isfinite(p->eps), LR_EINVAL, "eps must be positive and finite");
+    LR_REFUSE_UNLESS(p->cell == 0.0 || (p->cell > 0.0 && isfinite(p->cell)), LR_EINVAL, "cell must be 0 (automatic) or positive and finite");
+    LR_REFUSE_UNLESS(n0 >= 0 && n0 <= NN_MAX_N && n1 >= 0 && n1 <= NN_MAX_N, LR_EINVAL, "n0 / n1 must lie in 0..4194304");
+    LR_REFUSE_UNLESS(n0 == 0 || xyzA, LR_EINVAL, "null xyzA");
+    LR_REFUSE_UNLESS(n0 == 0 || nrmA, LR_EINVAL, "null nrmA");
+    LR_REFUSE_UNLESS(n1 == 0 || xyzB, LR_EINVAL, "null xyzB");
+    LR_REFUSE_UNLESS(n1 == 0 || nrmB, LR_EINVAL, "null nrmB");
+    LR_REFUSE_UNLESS(result, LR_EINVAL, "null result");
     bb_args g;
     memset(&g, 0, sizeof g);
     const size_t need = bb_make_layout(&g.L, (size_t)n0, (size_t)n1);
-    if (scratch_bytes < need) { lr_set_error("%s: scratch too small (lr_bbrf_scratch_bytes(n0, n1, n_iter))", who); return LR_EINVAL; }
-    BB_REQUIRE(((uintptr_t)scratch & 255) == 0, "scratch must be 256-byte aligned");
-    LR_TRY_HIP(lr_check_memory_device(scratch, (hipStream_t)stream, who, nullptr));
+    LR_TRY_HIP(lr_check_scratch(who, scratch, scratch_bytes, need, "lr_bbrf_scratch_bytes(n0, n1, n_iter)", LR_EINVAL, stream, nullptr));
     g.base = reinterpret_cast<char *>(scratch); g.stride = need;
     g.A = xyzA; g.nA = nrmA; g.B = xyzB; g.nB = nrmB; g.n0 = n0; g.n1 = n1; g.n_iter = p->n_iter;
     g.lr_a = p->angles_lr; g.lr_t = p->trans_lr; g.beta1 = p->beta1; g.beta2 = p->beta2; g.eps = p->eps;
@@ -485,21 +479,18 @@ extern "C" int lr_normals(const double *xyz, int n, double radius, int max_nn, d
                           size_t scratch_bytes, void *stream)
 {
     const char *who = "lr_normals";
-    BB_REQUIRE(radius > 0.0 && isfinite(radius) && isfinite(radius * radius), "radius must be positive and finite");
-    BB_REQUIRE(max_nn >= 1 && max_nn <= BB_MAX_NN, "max_nn must lie in 1..32");
-    BB_REQUIRE(n >= 0 && n <= NN_MAX_N, "n must lie in 0..4194304");
-    BB_REQUIRE(n == 0 || xyz, "null xyz");
-    BB_REQUIRE(n == 0 || normals_out, "null normals_out");
-    BB_REQUIRE(info, "null info");
-    BB_REQUIRE(scratch, "null scratch");
+    LR_REFUSE_UNLESS(radius > 0.0 && isfinite(radius) && isfinite(radius * radius), LR_EINVAL, "radius must be positive and finite");
+    LR_REFUSE_UNLESS(max_nn >= 1 && max_nn <= BB_MAX_NN, LR_EINVAL, "max_nn must lie in 1..32");
+    LR_REFUSE_UNLESS(n >= 0 && n <= NN_MAX_N, LR_EINVAL, "n must lie in 0..4194304");
+    LR_REFUSE_UNLESS(n == 0 || xyz, LR_EINVAL, "null xyz");
+    LR_REFUSE_UNLESS(n == 0 || normals_out, LR_EINVAL, "null normals_out");
+    LR_REFUSE_UNLESS(info, LR_EINVAL, "null info");
     nm_args a;
     memset(&a, 0, sizeof a);
     // the cell is a little longer than the radius: two points within the radius then sit in the same or in adjacent cells whatever the
     // rounding of the cell quotients (below 2^-29 of a cell at up to 2^22 cells per axis)
     nn_set_args(&a.nn, scratch, xyz, n, xyz, n, radius * (1.0 + 1.0 / 65536.0), nullptr, nullptr);
-    if (scratch_bytes < a.nn.stride) { lr_set_error("%s: scratch too small (lr_normals_scratch_bytes(n))", who); return LR_EINVAL; }
-    BB_REQUIRE(((uintptr_t)scratch & 255) == 0, "scratch must be 256-byte aligned");
-    LR_TRY_HIP(lr_check_memory_device(scratch, (hipStream_t)stream, who, nullptr));
+    LR_TRY_HIP(lr_check_scratch(who, scratch, scratch_bytes, a.nn.stride, "lr_normals_scratch_bytes(n)", LR_EINVAL, stream, nullptr));
     a.xyz = xyz; a.n = n; a.max_nn = max_nn; a.r2 = radius * radius; a.out = normals_out; a.info = info;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(nm_info_kernel, dim3(1), dim3(64), 0, st, a, 0);

@@ -1,8 +1,9 @@
 // The grid and the search launches of the exact 3-D nearest neighbour (lr_nn3.hip), for the translation units that run them inside a
 // sequence of their own (lr_bbrf.hip).  Internal: not part of the ABI.  The layout and the control block are what lr_nn3 / lr_refine_z
-// use; *_scratch_bytes of either must not move when this file changes.
+// use; *_scratch_bytes of either must not move when this file changes.  Needs lr_scratch.h alone (lr_al, lr_ptr): nothing of the
+// correspondence-set front end.
 #pragma once
-#include "lr_corrset.h"
+#include "lr_scratch.h"
 
 #define NN_MAX_N 4194304             // points per cloud (2^22)
 #define NN_SHELL_CAP 3               // phase 1 walks shells 0..3 (up to 343 cells behind 119 ranges)
@@ -26,7 +27,7 @@ static_assert(sizeof(nn_ctl) <= 512, "nn_ctl outgrew its slot");
 struct nn_layout { size_t table, pts, pidx, blk, strag, idx, P0, zd, w, hist, part, end; };
 struct nn_args {
     char *base;
-    size_t stride;                           // (cs_ptr's form; always one arena)
+    size_t stride;                           // (lr_ptr's form; always one arena)
     nn_layout L;
     const double *xyz0, *xyz1, *T;
     int32_t n0, n1, ncell_max, refine;
@@ -44,26 +45,26 @@ static size_t nn_make_layout(nn_layout *L, size_t n0, size_t n1, int refine)
 {
     const size_t m0 = n0 > 0 ? n0 : 1, m1 = n1 > 0 ? n1 : 1;
     size_t o = 512;
-    L->table = o; o += cs_al(nn_cells_max(n1) * 4);
-    L->pts = o;   o += cs_al(m1 * 24);
-    L->pidx = o;  o += cs_al(m1 * 4);
-    L->blk = o;   o += cs_al((m0 / 256 + 2) * 4);
-    L->strag = o; o += cs_al(m0 * 4);
+    L->table = o; o += lr_al(nn_cells_max(n1) * 4);
+    L->pts = o;   o += lr_al(m1 * 24);
+    L->pidx = o;  o += lr_al(m1 * 4);
+    L->blk = o;   o += lr_al((m0 / 256 + 2) * 4);
+    L->strag = o; o += lr_al(m0 * 4);
     L->idx = L->P0 = L->zd = L->w = L->hist = L->part = o;
     if (refine) {
-        L->idx = o;  o += cs_al(m0 * 4);
-        L->P0 = o;   o += cs_al(m0 * 24);
-        L->zd = o;   o += cs_al(m0 * 8);
-        L->w = o;    o += cs_al(m0 * 8);
-        L->hist = o; o += cs_al(8 * 256 * 4);
-        L->part = o; o += cs_al((m0 / NN_RUN + 1) * 16);
+        L->idx = o;  o += lr_al(m0 * 4);
+        L->P0 = o;   o += lr_al(m0 * 24);
+        L->zd = o;   o += lr_al(m0 * 8);
+        L->w = o;    o += lr_al(m0 * 8);
+        L->hist = o; o += lr_al(8 * 256 * 4);
+        L->part = o; o += lr_al((m0 / NN_RUN + 1) * 16);
     }
     L->end = o;
     return o;
 }
 
 #ifdef __HIPCC__
-__device__ __forceinline__ nn_ctl *nn_c(const nn_args &g) { return cs_ptr<nn_ctl>(g, 0, 0); }
+__device__ __forceinline__ nn_ctl *nn_c(const nn_args &g) { return lr_ptr<nn_ctl>(g, 0, 0); }
 // a caller that runs these launches inside a device-side loop of its own (lr_bbrf) names the word that ends it; lr_nn3 / lr_refine_z pass none
 __device__ __forceinline__ bool nn_stopped(const nn_args &g) { return g.stop && *g.stop; }
 // clamped cell of a coordinate: 0 .. dim - 1, NaN and everything below the grid to 0

@@ -14,7 +14,6 @@
 // an exact radix select of the weights' median on their bit patterns (8 passes of 8 bits; every block re-derives the prefix from the
 // finished histograms, so no pass needs a host decision), the two-level sums in their contractual order, the step.  A finished call's
 // remaining launches return at their first instruction.  No floating-point atomic; every word read was written by a kernel of the call.
-#include "lr_corrset.h"
 #include "lr_prims.h"
 #include "lr_nn3.h"
 #include <math.h>
@@ -40,7 +39,7 @@ __device__ __forceinline__ void nn_take(double d2, int j, double &best, int &bj)
 __global__ void __launch_bounds__(256) nn_init_kernel(nn_args g)
 {
     if (nn_stopped(g)) return;
-    int32_t *table = cs_ptr<int32_t>(g, 0, g.L.table);
+    int32_t *table = lr_ptr<int32_t>(g, 0, g.L.table);
     for (size_t s = (size_t)blockIdx.x * 256 + threadIdx.x; s < (size_t)g.ncell_max; s += (size_t)gridDim.x * 256) table[s] = 0;
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         nn_ctl *c = nn_c(g);
@@ -147,13 +146,13 @@ __global__ void __launch_bounds__(256) nn_count_kernel(nn_args g)
     if (j >= g.n1) return;
     const double p[3] = { g.xyz1[3 * (size_t)j], g.xyz1[3 * (size_t)j + 1], g.xyz1[3 * (size_t)j + 2] };
     if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) return;
-    atomicAdd(&cs_ptr<int32_t>(g, 0, g.L.table)[nn_lin(c, p)], 1);
+    atomicAdd(&lr_ptr<int32_t>(g, 0, g.L.table)[nn_lin(c, p)], 1);
 }
 
 __global__ void __launch_bounds__(1024) nn_scan_kernel(nn_args g)
 {
     if (nn_stopped(g)) return;
-    lr_block_exscan(cs_ptr<int32_t>(g, 0, g.L.table), (size_t)nn_c(g)->ncell);
+    lr_block_exscan(lr_ptr<int32_t>(g, 0, g.L.table), (size_t)nn_c(g)->ncell);
 }
 
 // after this kernel table[c] = end of cell c; its start is table[c - 1] (0 for c = 0)
@@ -166,10 +165,10 @@ __global__ void __launch_bounds__(256) nn_scatter_kernel(nn_args g)
     const double p[3] = { g.xyz1[3 * (size_t)j], g.xyz1[3 * (size_t)j + 1], g.xyz1[3 * (size_t)j + 2] };
     if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) return;
     // starts + fills stay below n1_live <= n1 (the counts sum to it)
-    const int at = atomicAdd(&cs_ptr<int32_t>(g, 0, g.L.table)[nn_lin(c, p)], 1);
-    double *out = cs_ptr<double>(g, 0, g.L.pts) + 3 * (size_t)at;
+    const int at = atomicAdd(&lr_ptr<int32_t>(g, 0, g.L.table)[nn_lin(c, p)], 1);
+    double *out = lr_ptr<double>(g, 0, g.L.pts) + 3 * (size_t)at;
     out[0] = p[0]; out[1] = p[1]; out[2] = p[2];
-    cs_ptr<int32_t>(g, 0, g.L.pidx)[at] = j;
+    lr_ptr<int32_t>(g, 0, g.L.pidx)[at] = j;
 }
 
 // ---- phase 1 -------------------------------------------------------------------------------------------------------------------
@@ -198,12 +197,12 @@ __global__ void __launch_bounds__(256) nn_walk_kernel(nn_args g)
     nn_ctl *c = nn_c(g);
     if (g.refine && c->done) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    int32_t *idx_out = g.refine ? cs_ptr<int32_t>(g, 0, g.L.idx) : g.idx_out;
+    int32_t *idx_out = g.refine ? lr_ptr<int32_t>(g, 0, g.L.idx) : g.idx_out;
     bool open = false, bad = false;
     if (i < g.n0) {
         double q[3];
         if (g.refine) {
-            double *P0 = cs_ptr<double>(g, 0, g.L.P0) + 3 * (size_t)i;
+            double *P0 = lr_ptr<double>(g, 0, g.L.P0) + 3 * (size_t)i;
             q[0] = P0[0]; q[1] = P0[1];
             q[2] = P0[2] - c->pending;               // the previous repeat's step (Z7); 0 before the first
             P0[2] = q[2];
@@ -214,8 +213,8 @@ __global__ void __launch_bounds__(256) nn_walk_kernel(nn_args g)
         double best = INFINITY;
         int bj = -1;
         if (!bad && c->n1_live > 0) {
-            const int32_t *table = cs_ptr<int32_t>(g, 0, g.L.table), *pidx = cs_ptr<int32_t>(g, 0, g.L.pidx);
-            const double *pts = cs_ptr<double>(g, 0, g.L.pts);
+            const int32_t *table = lr_ptr<int32_t>(g, 0, g.L.table), *pidx = lr_ptr<int32_t>(g, 0, g.L.pidx);
+            const double *pts = lr_ptr<double>(g, 0, g.L.pts);
             const int dx = c->dim[0], dy = c->dim[1], dz = c->dim[2];
             const double cell = c->cell;
             const int cx = nn_cell(q[0], c->blo[0], cell, dx), cy = nn_cell(q[1], c->blo[1], cell, dy), cz = nn_cell(q[2], c->blo[2], cell, dz);
@@ -255,7 +254,7 @@ __global__ void __launch_bounds__(256) nn_walk_kernel(nn_args g)
     }
     const unsigned long long nbad = __ballot(bad);
     if ((threadIdx.x & 63) == 0 && nbad && c->repeats == 0) atomicAdd(&c->n0_dropped, __popcll(nbad));
-    lr_block_count(open, cs_ptr<int32_t>(g, 0, g.L.blk));
+    lr_block_count(open, lr_ptr<int32_t>(g, 0, g.L.blk));
 }
 
 // the open queries in index order; block 0 also clears the words the repeat's later kernels accumulate into
@@ -266,16 +265,16 @@ __global__ void __launch_bounds__(256) nn_strag_kernel(nn_args g)
     nn_ctl *c = nn_c(g);
     if (g.refine && c->done) return;
     if (g.refine && blockIdx.x == 0) {
-        int32_t *hist = cs_ptr<int32_t>(g, 0, g.L.hist);
+        int32_t *hist = lr_ptr<int32_t>(g, 0, g.L.hist);
         for (int k = threadIdx.x; k < 8 * 256; k += 256) hist[k] = 0;
         if (threadIdx.x == 0) { c->n_valid = 0; c->hi_key = ~0ull; }
     }
-    const int before = lr_blocks_before(cs_ptr<int32_t>(g, 0, g.L.blk)), i = blockIdx.x * 256 + threadIdx.x;
-    const int32_t *idx = g.refine ? cs_ptr<int32_t>(g, 0, g.L.idx) : g.idx_out;
+    const int before = lr_blocks_before(lr_ptr<int32_t>(g, 0, g.L.blk)), i = blockIdx.x * 256 + threadIdx.x;
+    const int32_t *idx = g.refine ? lr_ptr<int32_t>(g, 0, g.L.idx) : g.idx_out;
     const bool k = i < g.n0 && idx[i] == NN_OPEN;
     int prefix;
     const int slot = lr_ordered_slot(k, before, s_w, s_p, prefix);
-    if (k) cs_ptr<int32_t>(g, 0, g.L.strag)[slot] = i;      // slot < n0: the flags set number at most n0
+    if (k) lr_ptr<int32_t>(g, 0, g.L.strag)[slot] = i;      // slot < n0: the flags set number at most n0
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) c->n_strag = prefix + s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
 
@@ -286,13 +285,13 @@ __global__ void __launch_bounds__(256) nn_far_kernel(nn_args g)
     const nn_ctl *c = nn_c(g);
     if (g.refine && c->done) return;
     const int ns = c->n_strag, n1 = c->n1_live, lane = threadIdx.x & 63;
-    const int32_t *strag = cs_ptr<int32_t>(g, 0, g.L.strag), *pidx = cs_ptr<int32_t>(g, 0, g.L.pidx);
-    const double *pts = cs_ptr<double>(g, 0, g.L.pts);
-    int32_t *idx_out = g.refine ? cs_ptr<int32_t>(g, 0, g.L.idx) : g.idx_out;
+    const int32_t *strag = lr_ptr<int32_t>(g, 0, g.L.strag), *pidx = lr_ptr<int32_t>(g, 0, g.L.pidx);
+    const double *pts = lr_ptr<double>(g, 0, g.L.pts);
+    int32_t *idx_out = g.refine ? lr_ptr<int32_t>(g, 0, g.L.idx) : g.idx_out;
     for (int k = blockIdx.x * 4 + (threadIdx.x >> 6); k < ns; k += gridDim.x * 4) {
         const int i = strag[k];
         double q[3];
-        if (g.refine) { const double *P0 = cs_ptr<double>(g, 0, g.L.P0) + 3 * (size_t)i; q[0] = P0[0]; q[1] = P0[1]; q[2] = P0[2]; }
+        if (g.refine) { const double *P0 = lr_ptr<double>(g, 0, g.L.P0) + 3 * (size_t)i; q[0] = P0[0]; q[1] = P0[1]; q[2] = P0[2]; }
         else { q[0] = g.xyz0[3 * (size_t)i]; q[1] = g.xyz0[3 * (size_t)i + 1]; q[2] = g.xyz0[3 * (size_t)i + 2]; }
         double best = INFINITY;
         int bj = -1;
@@ -327,7 +326,7 @@ __global__ void __launch_bounds__(256) rz_xform_kernel(nn_args g)
 #pragma unroll
         for (int a = 0; a < 3; ++a) p[a] = ((g.T[4 * a] * x + g.T[4 * a + 1] * y) + g.T[4 * a + 2] * z) + g.T[4 * a + 3];
     }
-    double *P0 = cs_ptr<double>(g, 0, g.L.P0) + 3 * (size_t)i;
+    double *P0 = lr_ptr<double>(g, 0, g.L.P0) + 3 * (size_t)i;
     P0[0] = p[0]; P0[1] = p[1]; P0[2] = p[2];
 }
 
@@ -350,10 +349,10 @@ __global__ void __launch_bounds__(256) rz_pair_kernel(nn_args g)
     const int i = blockIdx.x * 256 + threadIdx.x;
     bool valid = false;
     if (i < g.n0) {
-        const int j = cs_ptr<int32_t>(g, 0, g.L.idx)[i];
+        const int j = lr_ptr<int32_t>(g, 0, g.L.idx)[i];
         double zd = 0.0, w = -1.0;
         if (j >= 0) {
-            const double *P0 = cs_ptr<double>(g, 0, g.L.P0) + 3 * (size_t)i, *b = g.xyz1 + 3 * (size_t)j;
+            const double *P0 = lr_ptr<double>(g, 0, g.L.P0) + 3 * (size_t)i, *b = g.xyz1 + 3 * (size_t)j;
             const double dx = P0[0] - b[0], dy = P0[1] - b[1];
             if (__dsqrt_rn(dx * dx + dy * dy) <= g.gate) {
                 valid = true;
@@ -362,12 +361,12 @@ __global__ void __launch_bounds__(256) rz_pair_kernel(nn_args g)
                 atomicAdd(&s_h[(int)((unsigned long long)__double_as_longlong(w) >> 56)], 1);
             }
         }
-        cs_ptr<double>(g, 0, g.L.zd)[i] = zd;
-        cs_ptr<double>(g, 0, g.L.w)[i] = w;          // negative: not a valid pair
+        lr_ptr<double>(g, 0, g.L.zd)[i] = zd;
+        lr_ptr<double>(g, 0, g.L.w)[i] = w;          // negative: not a valid pair
     }
     const unsigned long long bal = __ballot(valid);
     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&c->n_valid, __popcll(bal));
-    rz_flush(s_h, cs_ptr<int32_t>(g, 0, g.L.hist));
+    rz_flush(s_h, lr_ptr<int32_t>(g, 0, g.L.hist));
 }
 
 // block-wide (256 threads): the leading 8 npass bits of the key of rank `rank` (0-based, ascending) from the finished histograms of
@@ -401,14 +400,14 @@ __global__ void __launch_bounds__(256) rz_hist_kernel(nn_args g, int pass)
     if (c->done) return;
     const int nv = c->n_valid;
     if (nv == 0) return;
-    int32_t *hist = cs_ptr<int32_t>(g, 0, g.L.hist);
+    int32_t *hist = lr_ptr<int32_t>(g, 0, g.L.hist);
     int less, eq;
     const unsigned long long prefix = rz_select(hist, pass, (nv - 1) >> 1, less, eq);
     s_h[threadIdx.x] = 0;
     __syncthreads();
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i < g.n0) {
-        const unsigned long long key = (unsigned long long)__double_as_longlong(cs_ptr<double>(g, 0, g.L.w)[i]);
+        const unsigned long long key = (unsigned long long)__double_as_longlong(lr_ptr<double>(g, 0, g.L.w)[i]);
         if (!(key >> 63) && (key >> (64 - 8 * pass)) == prefix) atomicAdd(&s_h[(int)((key >> (56 - 8 * pass)) & 255)], 1);
     }
     rz_flush(s_h, hist + pass * 256);
@@ -424,12 +423,12 @@ __global__ void __launch_bounds__(256) rz_min_kernel(nn_args g)
     const int nv = c->n_valid;
     if (nv == 0) return;
     int less, eq;
-    const unsigned long long lo = rz_select(cs_ptr<int32_t>(g, 0, g.L.hist), 8, (nv - 1) >> 1, less, eq);
+    const unsigned long long lo = rz_select(lr_ptr<int32_t>(g, 0, g.L.hist), 8, (nv - 1) >> 1, less, eq);
     if (!rz_needs_hi(nv, less, eq)) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     unsigned long long m = ~0ull;
     if (i < g.n0) {
-        const unsigned long long key = (unsigned long long)__double_as_longlong(cs_ptr<double>(g, 0, g.L.w)[i]);
+        const unsigned long long key = (unsigned long long)__double_as_longlong(lr_ptr<double>(g, 0, g.L.w)[i]);
         if (!(key >> 63) && key > lo) m = key;
     }
 #pragma unroll
@@ -446,7 +445,7 @@ __global__ void __launch_bounds__(256) rz_runs_kernel(nn_args g)
     const int nv = c->n_valid;
     if (nv == 0) return;
     int less, eq;
-    const unsigned long long lo = rz_select(cs_ptr<int32_t>(g, 0, g.L.hist), 8, (nv - 1) >> 1, less, eq);
+    const unsigned long long lo = rz_select(lr_ptr<int32_t>(g, 0, g.L.hist), 8, (nv - 1) >> 1, less, eq);
     const double vlo = __longlong_as_double((long long)lo);
     double med = vlo;
     if (!(nv & 1)) {
@@ -456,7 +455,7 @@ __global__ void __launch_bounds__(256) rz_runs_kernel(nn_args g)
     if (blockIdx.x == 0 && threadIdx.x == 0) c->med = med;
     const int lane = threadIdx.x & 63, run = blockIdx.x * 4 + (threadIdx.x >> 6), nruns = (g.n0 + NN_RUN - 1) / NN_RUN;
     if (run >= nruns) return;
-    const double *zd = cs_ptr<double>(g, 0, g.L.zd), *w = cs_ptr<double>(g, 0, g.L.w);
+    const double *zd = lr_ptr<double>(g, 0, g.L.zd), *w = lr_ptr<double>(g, 0, g.L.w);
     const int begin = run * NN_RUN, end = begin + NN_RUN < g.n0 ? begin + NN_RUN : g.n0;
     double num = 0.0, den = 0.0;
     for (int base = begin; base < end; base += 64) {
@@ -468,7 +467,7 @@ __global__ void __launch_bounds__(256) rz_runs_kernel(nn_args g)
         }
         for (int j = 0; j < m; ++j) { num += __shfl(tn, j); den += __shfl(td, j); }
     }
-    if (lane == 0) { double *part = cs_ptr<double>(g, 0, g.L.part) + 2 * (size_t)run; part[0] = num; part[1] = den; }
+    if (lane == 0) { double *part = lr_ptr<double>(g, 0, g.L.part) + 2 * (size_t)run; part[0] = num; part[1] = den; }
 }
 
 // Z6 second level, Z7, Z8 and the result block
@@ -479,7 +478,7 @@ __global__ void __launch_bounds__(64) rz_step_kernel(nn_args g)
     const int lane = threadIdx.x, nv = c->n_valid, nruns = (g.n0 + NN_RUN - 1) / NN_RUN;
     double num = 0.0, den = 0.0;
     if (nv > 0) {
-        const double *part = cs_ptr<double>(g, 0, g.L.part);
+        const double *part = lr_ptr<double>(g, 0, g.L.part);
         for (int base = 0; base < nruns; base += 64) {
             const int m = nruns - base < 64 ? nruns - base : 64;
             double tn = 0.0, td = 0.0;
@@ -523,22 +522,15 @@ extern "C" size_t lr_refine_z_scratch_bytes(int n0, int n1)
     return nn_make_layout(&L, (size_t)n0, (size_t)n1, 1);
 }
 
-#define NN_REQUIRE(cond, msg) do { if (!(cond)) { lr_set_error("%s: " msg, who); return LR_EINVAL; } } while (0)
-
-static int nn_check_common(const char *who, const double *xyz0, int n0, const double *xyz1, int n1, double cell, void *scratch, size_t scratch_bytes,
-                           int refine, const char *fn, void *stream, nn_args *g)
+// the cloud checks of lr_nn3 / lr_refine_z; g = the call's arguments as far as the two share them, g->stride = the scratch it needs
+static int nn_check_common(const char *who, const double *xyz0, int n0, const double *xyz1, int n1, double cell, int refine, nn_args *g)
 {
-    NN_REQUIRE(cell == 0.0 || (cell > 0.0 && isfinite(cell)), "cell must be 0 (automatic) or positive and finite");
-    NN_REQUIRE(n0 >= 0 && n0 <= NN_MAX_N && n1 >= 0 && n1 <= NN_MAX_N, "n0 / n1 must lie in 0..4194304");
-    NN_REQUIRE(n0 == 0 || xyz0, "null xyz0");
-    NN_REQUIRE(n1 == 0 || xyz1, "null xyz1");
-    NN_REQUIRE(scratch, "null scratch");
+    LR_REFUSE_UNLESS(cell == 0.0 || (cell > 0.0 && isfinite(cell)), LR_EINVAL, "cell must be 0 (automatic) or positive and finite");
+    LR_REFUSE_UNLESS(n0 >= 0 && n0 <= NN_MAX_N && n1 >= 0 && n1 <= NN_MAX_N, LR_EINVAL, "n0 / n1 must lie in 0..4194304");
+    LR_REFUSE_UNLESS(n0 == 0 || xyz0, LR_EINVAL, "null xyz0");
+    LR_REFUSE_UNLESS(n1 == 0 || xyz1, LR_EINVAL, "null xyz1");
     memset(g, 0, sizeof *g);
-    const size_t need = nn_make_layout(&g->L, (size_t)n0, (size_t)n1, refine);
-    if (scratch_bytes < need) { lr_set_error("%s: scratch too small (%s)", who, fn); return LR_EINVAL; }
-    NN_REQUIRE(((uintptr_t)scratch & 255) == 0, "scratch must be 256-byte aligned");
-    LR_TRY_HIP(lr_check_memory_device(scratch, (hipStream_t)stream, who, nullptr));
-    g->base = reinterpret_cast<char *>(scratch); g->stride = need;
+    g->stride = nn_make_layout(&g->L, (size_t)n0, (size_t)n1, refine);
     g->xyz0 = xyz0; g->xyz1 = xyz1; g->n0 = n0; g->n1 = n1;
     g->ncell_max = (int32_t)nn_cells_max((size_t)n1);
     g->refine = refine; g->cell_user = cell;
@@ -582,10 +574,12 @@ extern "C" int lr_nn3(const double *xyz0, int n0, const double *xyz1, int n1, co
 {
     const char *who = "lr_nn3";
     LR_CHECK_STRUCT_SIZE(lr_nn3_params, p, who);
-    NN_REQUIRE(info, "null info");
-    NN_REQUIRE(n0 <= 0 || (idx && dist), "null idx / dist");
+    LR_REFUSE_UNLESS(info, LR_EINVAL, "null info");
+    LR_REFUSE_UNLESS(n0 <= 0 || (idx && dist), LR_EINVAL, "null idx / dist");
     nn_args g;
-    LR_TRY_HIP(nn_check_common(who, xyz0, n0, xyz1, n1, p->cell, scratch, scratch_bytes, 0, "lr_nn3_scratch_bytes(n0, n1)", stream, &g));
+    LR_TRY_HIP(nn_check_common(who, xyz0, n0, xyz1, n1, p->cell, 0, &g));
+    LR_TRY_HIP(lr_check_scratch(who, scratch, scratch_bytes, g.stride, "lr_nn3_scratch_bytes(n0, n1)", LR_EINVAL, stream, nullptr));
+    g.base = reinterpret_cast<char *>(scratch);
     g.idx_out = idx; g.dist_out = dist;
     hipStream_t st = (hipStream_t)stream;
     nn_launch_grid(g, st);
@@ -600,12 +594,14 @@ extern "C" int lr_refine_z(const double *xyz0, int n0, const double *xyz1, int n
 {
     const char *who = "lr_refine_z";
     LR_CHECK_STRUCT_SIZE(lr_refine_z_params, p, who);
-    NN_REQUIRE(p->max_repeats >= 1 && p->max_repeats <= 64, "max_repeats must lie in 1..64");
-    NN_REQUIRE(p->xy_gate > 0.0 && isfinite(p->xy_gate), "xy_gate must be positive and finite");
-    NN_REQUIRE(p->min_change >= 0.0 && isfinite(p->min_change), "min_change must be finite and not negative");
-    NN_REQUIRE(result, "null result");
+    LR_REFUSE_UNLESS(p->max_repeats >= 1 && p->max_repeats <= 64, LR_EINVAL, "max_repeats must lie in 1..64");
+    LR_REFUSE_UNLESS(p->xy_gate > 0.0 && isfinite(p->xy_gate), LR_EINVAL, "xy_gate must be positive and finite");
+    LR_REFUSE_UNLESS(p->min_change >= 0.0 && isfinite(p->min_change), LR_EINVAL, "min_change must be finite and not negative");
+    LR_REFUSE_UNLESS(result, LR_EINVAL, "null result");
     nn_args g;
-    LR_TRY_HIP(nn_check_common(who, xyz0, n0, xyz1, n1, p->cell, scratch, scratch_bytes, 1, "lr_refine_z_scratch_bytes(n0, n1)", stream, &g));
+    LR_TRY_HIP(nn_check_common(who, xyz0, n0, xyz1, n1, p->cell, 1, &g));
+    LR_TRY_HIP(lr_check_scratch(who, scratch, scratch_bytes, g.stride, "lr_refine_z_scratch_bytes(n0, n1)", LR_EINVAL, stream, nullptr));
+    g.base = reinterpret_cast<char *>(scratch);
     g.T = T; g.gate = p->xy_gate; g.min_change = p->min_change; g.max_repeats = p->max_repeats; g.res = result;
     hipStream_t st = (hipStream_t)stream;
     const int nb0 = lr_cdiv(n0 > 0 ? n0 : 1, 256), rb = lr_cdiv(lr_cdiv(n0 > 0 ? n0 : 1, NN_RUN), 4);

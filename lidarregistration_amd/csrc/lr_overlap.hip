@@ -20,8 +20,8 @@
 // only existence within r is asked), every source centroid tests the 27 surrounding buckets, counts through integer atomics.
 // No floating-point atomic anywhere; every word a kernel reads has been written by a kernel of the same call (scratch contents are irrelevant).
 // The table, the hash, the compaction steps and the block scan are the shared ones (lr_cells.h, lr_prims.h); this file owns the cell rule
-// -- the floor of (p - vmb) / voxel -- and its kernels over the pairs' arenas (cs_ptr).
-#include "lr_corrset.h"
+// -- the floor of (p - vmb) / voxel -- and its kernels over the pairs' arenas (lr_ptr).
+#include "lr_scratch.h"
 #include "lr_cells.h"
 #include <math.h>
 #include <string.h>
@@ -74,27 +74,27 @@ static ov_layout ov_make_layout(size_t o, size_t n)
 {
     const size_t nn = n > 0 ? n : 1, cap = lr_cells_capacity(n), nb = (nn + 255) / 256;
     ov_layout L;
-    L.P = o;        o += cs_al(nn * 24);
-    L.slot_of = o;  o += cs_al(nn * 4);
-    L.ordA = o;     o += cs_al(nn * 4);
-    L.ordB = o;     o += cs_al(nn * 4);
-    L.hist = o;     o += cs_al(nb * 256 * 4);
-    L.keys = o;     o += cs_al(cap * 8);
-    L.first = o;    o += cs_al(cap * 4);
-    L.cnt = o;      o += cs_al(cap * 4);
-    L.rowof = o;    o += cs_al(cap * 4);
-    L.blk = o;      o += cs_al((nb + 2) * 4);
-    L.seg = o;      o += cs_al(nn * 4);
-    L.cent = o;     o += cs_al(nn * 24);
-    L.counts = o;   o += cs_al(nn * 4);
-    L.firstrow = o; o += cs_al(nn * 4);
+    L.P = o;        o += lr_al(nn * 24);
+    L.slot_of = o;  o += lr_al(nn * 4);
+    L.ordA = o;     o += lr_al(nn * 4);
+    L.ordB = o;     o += lr_al(nn * 4);
+    L.hist = o;     o += lr_al(nb * 256 * 4);
+    L.keys = o;     o += lr_al(cap * 8);
+    L.first = o;    o += lr_al(cap * 4);
+    L.cnt = o;      o += lr_al(cap * 4);
+    L.rowof = o;    o += lr_al(cap * 4);
+    L.blk = o;      o += lr_al((nb + 2) * 4);
+    L.seg = o;      o += lr_al(nn * 4);
+    L.cent = o;     o += lr_al(nn * 24);
+    L.counts = o;   o += lr_al(nn * 4);
+    L.firstrow = o; o += lr_al(nn * 4);
     L.end = o;
     return L;
 }
 // arena of one pair: control blocks | cloud 0 | cloud 1 | hashed grid (clouds == 2)
 static size_t ov_make_args(ov_args *g, size_t n0, size_t n1, int clouds)
 {
-    size_t o = cs_al(sizeof(ov_pair));
+    size_t o = lr_al(sizeof(ov_pair));
     g->L[0] = ov_make_layout(o, n0); o = g->L[0].end;
     g->L[1] = g->L[0];
     g->bk_cnt = g->bk_fill = g->bk_pts = 0; g->bk_mask = 0;
@@ -102,15 +102,15 @@ static size_t ov_make_args(ov_args *g, size_t n0, size_t n1, int clouds)
         g->L[1] = ov_make_layout(o, n1); o = g->L[1].end;
         const size_t nb = ov_buckets(n1);
         g->bk_mask = (uint32_t)(nb - 1);
-        g->bk_cnt = o;  o += cs_al(nb * 4);
-        g->bk_fill = o; o += cs_al(nb * 4);
-        g->bk_pts = o;  o += cs_al((n1 > 0 ? n1 : 1) * 24);
+        g->bk_cnt = o;  o += lr_al(nb * 4);
+        g->bk_fill = o; o += lr_al(nb * 4);
+        g->bk_pts = o;  o += lr_al((n1 > 0 ? n1 : 1) * 24);
     }
     g->clouds = clouds;
     return o;
 }
 
-__device__ __forceinline__ ov_cloud *ov_ctl(const ov_args &g, int pair, int cl) { return &cs_ptr<ov_pair>(g, pair, 0)->c[cl]; }
+__device__ __forceinline__ ov_cloud *ov_ctl(const ov_args &g, int pair, int cl) { return &lr_ptr<ov_pair>(g, pair, 0)->c[cl]; }
 // total order of the doubles as unsigned integers
 __device__ __forceinline__ unsigned long long ov_enc(double v)
 {
@@ -128,7 +128,7 @@ __global__ void ov_setup_kernel(ov_desc_table t, ov_args g, int npairs)
     const int k = threadIdx.x >> 1, cl = threadIdx.x & 1;
     if (k >= npairs || cl >= g.clouds) return;
     const ov_desc d = t.d[k];
-    ov_pair *pp = cs_ptr<ov_pair>(g, k, 0);
+    ov_pair *pp = lr_ptr<ov_pair>(g, k, 0);
     ov_cloud *c = &pp->c[cl];
     if (cl == 0) pp->res = d.res;
     c->xyz = cl ? d.xyz1 : d.xyz0;
@@ -147,11 +147,11 @@ __global__ void __launch_bounds__(256) ov_init_kernel(ov_args g)
     const int pair = blockIdx.z, cl = blockIdx.y;
     const ov_cloud *c = ov_ctl(g, pair, cl);
     const size_t cap = c->n > 0 ? (size_t)c->cap_mask + 1 : 0;
-    unsigned long long *keys = cs_ptr<unsigned long long>(g, pair, g.L[cl].keys);
-    int32_t *first = cs_ptr<int32_t>(g, pair, g.L[cl].first), *cnt = cs_ptr<int32_t>(g, pair, g.L[cl].cnt);
+    unsigned long long *keys = lr_ptr<unsigned long long>(g, pair, g.L[cl].keys);
+    int32_t *first = lr_ptr<int32_t>(g, pair, g.L[cl].first), *cnt = lr_ptr<int32_t>(g, pair, g.L[cl].cnt);
     for (size_t s = (size_t)blockIdx.x * 256 + threadIdx.x; s < cap; s += (size_t)gridDim.x * 256) { keys[s] = LR_CELL_EMPTY; first[s] = 0x7fffffff; cnt[s] = 0; }
     if (cl == 1) {
-        int32_t *bc = cs_ptr<int32_t>(g, pair, g.bk_cnt), *bf = cs_ptr<int32_t>(g, pair, g.bk_fill);
+        int32_t *bc = lr_ptr<int32_t>(g, pair, g.bk_cnt), *bf = lr_ptr<int32_t>(g, pair, g.bk_fill);
         for (size_t s = (size_t)blockIdx.x * 256 + threadIdx.x; s <= g.bk_mask; s += (size_t)gridDim.x * 256) { bc[s] = 0; bf[s] = 0; }
     }
 }
@@ -164,8 +164,8 @@ __global__ void __launch_bounds__(256) ov_xform_kernel(ov_args g)
     const int n = c->n;
     if ((int)blockIdx.x * 256 >= n) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    double *P = cs_ptr<double>(g, pair, g.L[cl].P);
-    int32_t *slot_of = cs_ptr<int32_t>(g, pair, g.L[cl].slot_of);
+    double *P = lr_ptr<double>(g, pair, g.L[cl].P);
+    int32_t *slot_of = lr_ptr<int32_t>(g, pair, g.L[cl].slot_of);
     double lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
     bool bad = false;
     if (i < n) {
@@ -220,16 +220,16 @@ __global__ void __launch_bounds__(256) ov_insert_kernel(ov_args g)
     const int n = c->n_live;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    int32_t *slot_of = cs_ptr<int32_t>(g, pair, g.L[cl].slot_of);
+    int32_t *slot_of = lr_ptr<int32_t>(g, pair, g.L[cl].slot_of);
     if (slot_of[i] < 0) return;                      // dropped
-    const double *P = cs_ptr<double>(g, pair, g.L[cl].P);
+    const double *P = lr_ptr<double>(g, pair, g.L[cl].P);
     unsigned long long ca[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a)                      // 0 <= cell < 2^21 (ov_bounds_kernel)
         ca[a] = (unsigned long long)((int)floor((P[3 * (size_t)i + a] - c->vmb[a]) / g.voxel) & 0x1fffff);
-    const unsigned s = lr_cells_claim(cs_ptr<unsigned long long>(g, pair, g.L[cl].keys), c->cap_mask, lr_cells_pack(ca[0], ca[1], ca[2]));
-    atomicMin(&cs_ptr<int32_t>(g, pair, g.L[cl].first)[s], i);
-    atomicAdd(&cs_ptr<int32_t>(g, pair, g.L[cl].cnt)[s], 1);
+    const unsigned s = lr_cells_claim(lr_ptr<unsigned long long>(g, pair, g.L[cl].keys), c->cap_mask, lr_cells_pack(ca[0], ca[1], ca[2]));
+    atomicMin(&lr_ptr<int32_t>(g, pair, g.L[cl].first)[s], i);
+    atomicAdd(&lr_ptr<int32_t>(g, pair, g.L[cl].cnt)[s], 1);
     slot_of[i] = (int32_t)s;
 }
 
@@ -237,7 +237,7 @@ __global__ void __launch_bounds__(256) ov_insert_kernel(ov_args g)
 __device__ __forceinline__ bool ov_is_first(const ov_args &g, int pair, int cl, int i, int n, int &slot)
 {
     slot = -1;
-    return i < n && lr_cells_is_first(cs_ptr<int32_t>(g, pair, g.L[cl].first), cs_ptr<int32_t>(g, pair, g.L[cl].slot_of), i, slot);
+    return i < n && lr_cells_is_first(lr_ptr<int32_t>(g, pair, g.L[cl].first), lr_ptr<int32_t>(g, pair, g.L[cl].slot_of), i, slot);
 }
 
 __global__ void __launch_bounds__(256) ov_flag_kernel(ov_args g)
@@ -246,7 +246,7 @@ __global__ void __launch_bounds__(256) ov_flag_kernel(ov_args g)
     const int n = ov_ctl(g, pair, cl)->n_live;
     if ((int)blockIdx.x * 256 >= n) return;
     int slot;
-    lr_block_count(ov_is_first(g, pair, cl, blockIdx.x * 256 + threadIdx.x, n, slot), cs_ptr<int32_t>(g, pair, g.L[cl].blk));
+    lr_block_count(ov_is_first(g, pair, cl, blockIdx.x * 256 + threadIdx.x, n, slot), lr_ptr<int32_t>(g, pair, g.L[cl].blk));
 }
 
 __global__ void __launch_bounds__(256) ov_compact_kernel(ov_args g)
@@ -256,14 +256,14 @@ __global__ void __launch_bounds__(256) ov_compact_kernel(ov_args g)
     ov_cloud *c = ov_ctl(g, pair, cl);
     const int n = c->n_live;
     if ((int)blockIdx.x * 256 >= n) return;
-    const int before = lr_blocks_before(cs_ptr<int32_t>(g, pair, g.L[cl].blk)), i = blockIdx.x * 256 + threadIdx.x;
+    const int before = lr_blocks_before(lr_ptr<int32_t>(g, pair, g.L[cl].blk)), i = blockIdx.x * 256 + threadIdx.x;
     int slot, prefix;
     const bool k = ov_is_first(g, pair, cl, i, n, slot);
     const int row = lr_ordered_slot(k, before, s_w, s_p, prefix);
     if (k) {
-        cs_ptr<int32_t>(g, pair, g.L[cl].rowof)[slot] = row;
-        cs_ptr<int32_t>(g, pair, g.L[cl].firstrow)[row] = i;
-        cs_ptr<int32_t>(g, pair, g.L[cl].counts)[row] = cs_ptr<int32_t>(g, pair, g.L[cl].cnt)[slot];
+        lr_ptr<int32_t>(g, pair, g.L[cl].rowof)[slot] = row;
+        lr_ptr<int32_t>(g, pair, g.L[cl].firstrow)[row] = i;
+        lr_ptr<int32_t>(g, pair, g.L[cl].counts)[row] = lr_ptr<int32_t>(g, pair, g.L[cl].cnt)[slot];
     }
     if ((int)blockIdx.x == (n - 1) / 256 && threadIdx.x == 0) c->rows = prefix + s_w[0] + s_w[1] + s_w[2] + s_w[3];
 }
@@ -271,8 +271,8 @@ __global__ void __launch_bounds__(256) ov_compact_kernel(ov_args g)
 // ---- 4. stable LSD radix sort of the point indices on their row ----------------------------------------------------------------
 __device__ __forceinline__ int ov_key(const ov_args &g, int pair, int cl, int i)
 {
-    const int s = cs_ptr<int32_t>(g, pair, g.L[cl].slot_of)[i];
-    return s < 0 ? OV_NOKEY : cs_ptr<int32_t>(g, pair, g.L[cl].rowof)[s];
+    const int s = lr_ptr<int32_t>(g, pair, g.L[cl].slot_of)[i];
+    return s < 0 ? OV_NOKEY : lr_ptr<int32_t>(g, pair, g.L[cl].rowof)[s];
 }
 // rank of this thread's element among the block's elements of the same digit, in thread order; s_cnt[w * 256 + d] = elements of
 // digit d in wave w
@@ -301,7 +301,7 @@ __device__ __forceinline__ bool ov_sort_item(const ov_args &g, int pair, int cl,
     const int t = blockIdx.x * 256 + threadIdx.x;
     idx = 0; digit = 0;
     if (t >= n) return false;
-    idx = pass == 0 ? t : cs_ptr<int32_t>(g, pair, (pass & 1) ? g.L[cl].ordA : g.L[cl].ordB)[t];
+    idx = pass == 0 ? t : lr_ptr<int32_t>(g, pair, (pass & 1) ? g.L[cl].ordA : g.L[cl].ordB)[t];
     digit = (ov_key(g, pair, cl, idx) >> (8 * pass)) & 255;
     return true;
 }
@@ -316,14 +316,14 @@ __global__ void __launch_bounds__(256) ov_sort_hist_kernel(ov_args g, int pass)
     const bool valid = ov_sort_item(g, pair, cl, n, pass, idx, digit);
     ov_block_rank(digit, valid, s_cnt);
     const int nb = (n + 255) / 256, d = threadIdx.x;
-    cs_ptr<int32_t>(g, pair, g.L[cl].hist)[(size_t)d * nb + blockIdx.x] = (s_cnt[d] + s_cnt[256 + d]) + (s_cnt[512 + d] + s_cnt[768 + d]);
+    lr_ptr<int32_t>(g, pair, g.L[cl].hist)[(size_t)d * nb + blockIdx.x] = (s_cnt[d] + s_cnt[256 + d]) + (s_cnt[512 + d] + s_cnt[768 + d]);
 }
 
 __global__ void __launch_bounds__(1024) ov_sort_scan_kernel(ov_args g)
 {
     const int pair = blockIdx.z, cl = blockIdx.y;
     const int n = ov_ctl(g, pair, cl)->n_live;
-    lr_block_exscan(cs_ptr<int32_t>(g, pair, g.L[cl].hist), (size_t)256 * ((n + 255) / 256));
+    lr_block_exscan(lr_ptr<int32_t>(g, pair, g.L[cl].hist), (size_t)256 * ((n + 255) / 256));
 }
 
 __global__ void __launch_bounds__(256) ov_sort_scatter_kernel(ov_args g, int pass)
@@ -337,7 +337,7 @@ __global__ void __launch_bounds__(256) ov_sort_scatter_kernel(ov_args g, int pas
     const int rank = ov_block_rank(digit, valid, s_cnt);
     const int nb = (n + 255) / 256;
     // digit-major offsets: every position is below n (the histogram sums to n)
-    if (valid) cs_ptr<int32_t>(g, pair, (pass & 1) ? g.L[cl].ordB : g.L[cl].ordA)[cs_ptr<int32_t>(g, pair, g.L[cl].hist)[(size_t)digit * nb + blockIdx.x] + rank] = idx;
+    if (valid) lr_ptr<int32_t>(g, pair, (pass & 1) ? g.L[cl].ordB : g.L[cl].ordA)[lr_ptr<int32_t>(g, pair, g.L[cl].hist)[(size_t)digit * nb + blockIdx.x] + rank] = idx;
 }
 
 // segment start of every row in the sorted sequence
@@ -348,9 +348,9 @@ __global__ void __launch_bounds__(256) ov_heads_kernel(ov_args g, int passes)
     const int kept = c->n_live - c->dropped;
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= kept) return;
-    const int32_t *ord = cs_ptr<int32_t>(g, pair, (passes & 1) ? g.L[cl].ordA : g.L[cl].ordB);
+    const int32_t *ord = lr_ptr<int32_t>(g, pair, (passes & 1) ? g.L[cl].ordA : g.L[cl].ordB);
     const int key = ov_key(g, pair, cl, ord[t]);
-    if (t == 0 || ov_key(g, pair, cl, ord[t - 1]) != key) cs_ptr<int32_t>(g, pair, g.L[cl].seg)[key] = t;
+    if (t == 0 || ov_key(g, pair, cl, ord[t - 1]) != key) lr_ptr<int32_t>(g, pair, g.L[cl].seg)[key] = t;
 }
 
 // ---- 5. centroids ----------------------------------------------------------------------------------------------------------------
@@ -362,10 +362,10 @@ __global__ void __launch_bounds__(256) ov_centroid_kernel(ov_args g, int passes,
     if ((int)blockIdx.x * 256 >= rows) return;
     const int row = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
     const bool active = row < rows;
-    const int32_t *ord = cs_ptr<int32_t>(g, pair, (passes & 1) ? g.L[cl].ordA : g.L[cl].ordB);
-    const double *P = cs_ptr<double>(g, pair, g.L[cl].P);
-    const int32_t *counts = cs_ptr<int32_t>(g, pair, g.L[cl].counts);
-    const int start = active ? cs_ptr<int32_t>(g, pair, g.L[cl].seg)[row] : 0, cnt = active ? counts[row] : 0;
+    const int32_t *ord = lr_ptr<int32_t>(g, pair, (passes & 1) ? g.L[cl].ordA : g.L[cl].ordB);
+    const double *P = lr_ptr<double>(g, pair, g.L[cl].P);
+    const int32_t *counts = lr_ptr<int32_t>(g, pair, g.L[cl].counts);
+    const int start = active ? lr_ptr<int32_t>(g, pair, g.L[cl].seg)[row] : 0, cnt = active ? counts[row] : 0;
     double s[3] = { 0.0, 0.0, 0.0 };
     const bool heavy = cnt > OV_LIGHT;
     if (!heavy)
@@ -392,8 +392,8 @@ __global__ void __launch_bounds__(256) ov_centroid_kernel(ov_args g, int passes,
         if (lane == l) { s[0] = a[0]; s[1] = a[1]; s[2] = a[2]; }
     }
     if (!active) return;
-    double *cent = cs_ptr<double>(g, pair, g.L[cl].cent);
-    const int first = cs_ptr<int32_t>(g, pair, g.L[cl].firstrow)[row];
+    double *cent = lr_ptr<double>(g, pair, g.L[cl].cent);
+    const int first = lr_ptr<int32_t>(g, pair, g.L[cl].firstrow)[row];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const double v = s[a] / (double)cnt;
@@ -436,14 +436,14 @@ __global__ void __launch_bounds__(256) ov_bhist_kernel(ov_args g)
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= c1->rows) return;
     long long q[3];
-    ov_qcell(cs_ptr<double>(g, pair, g.L[1].cent) + 3 * (size_t)t, c1->vmb, g.g, q);
-    atomicAdd(&cs_ptr<int32_t>(g, pair, g.bk_cnt)[ov_bucket(q[0], q[1], q[2], g.bk_mask)], 1);
+    ov_qcell(lr_ptr<double>(g, pair, g.L[1].cent) + 3 * (size_t)t, c1->vmb, g.g, q);
+    atomicAdd(&lr_ptr<int32_t>(g, pair, g.bk_cnt)[ov_bucket(q[0], q[1], q[2], g.bk_mask)], 1);
 }
 
 __global__ void __launch_bounds__(1024) ov_bscan_kernel(ov_args g)
 {
     if (ov_ctl(g, blockIdx.z, 1)->rows == 0) return;
-    lr_block_exscan(cs_ptr<int32_t>(g, blockIdx.z, g.bk_cnt), (size_t)g.bk_mask + 1);
+    lr_block_exscan(lr_ptr<int32_t>(g, blockIdx.z, g.bk_cnt), (size_t)g.bk_mask + 1);
 }
 
 __global__ void __launch_bounds__(256) ov_bscatter_kernel(ov_args g)
@@ -452,13 +452,13 @@ __global__ void __launch_bounds__(256) ov_bscatter_kernel(ov_args g)
     const ov_cloud *c1 = ov_ctl(g, pair, 1);
     const int t = blockIdx.x * 256 + threadIdx.x;
     if (t >= c1->rows) return;
-    const double *p = cs_ptr<double>(g, pair, g.L[1].cent) + 3 * (size_t)t;
+    const double *p = lr_ptr<double>(g, pair, g.L[1].cent) + 3 * (size_t)t;
     long long q[3];
     ov_qcell(p, c1->vmb, g.g, q);
     const uint32_t b = ov_bucket(q[0], q[1], q[2], g.bk_mask);
     // bucket starts + fills stay below rows (the counts sum to it)
-    const int at = cs_ptr<int32_t>(g, pair, g.bk_cnt)[b] + atomicAdd(&cs_ptr<int32_t>(g, pair, g.bk_fill)[b], 1);
-    double *out = cs_ptr<double>(g, pair, g.bk_pts) + 3 * (size_t)at;
+    const int at = lr_ptr<int32_t>(g, pair, g.bk_cnt)[b] + atomicAdd(&lr_ptr<int32_t>(g, pair, g.bk_fill)[b], 1);
+    double *out = lr_ptr<double>(g, pair, g.bk_pts) + 3 * (size_t)at;
     out[0] = p[0]; out[1] = p[1]; out[2] = p[2];
 }
 
@@ -472,12 +472,12 @@ __global__ void __launch_bounds__(256) ov_search_kernel(ov_args g)
     const int t = blockIdx.x * 256 + threadIdx.x;
     bool hit = false;
     if (t < rows0) {
-        const double *a = cs_ptr<double>(g, pair, g.L[0].cent) + 3 * (size_t)t;
+        const double *a = lr_ptr<double>(g, pair, g.L[0].cent) + 3 * (size_t)t;
         const double ax = a[0], ay = a[1], az = a[2];
         long long q[3];
         ov_qcell(a, c1->vmb, g.g, q);
-        const int32_t *bs = cs_ptr<int32_t>(g, pair, g.bk_cnt), *bf = cs_ptr<int32_t>(g, pair, g.bk_fill);
-        const double *pts = cs_ptr<double>(g, pair, g.bk_pts);
+        const int32_t *bs = lr_ptr<int32_t>(g, pair, g.bk_cnt), *bf = lr_ptr<int32_t>(g, pair, g.bk_fill);
+        const double *pts = lr_ptr<double>(g, pair, g.bk_pts);
         for (int cc = 0; cc < 27 && !hit; ++cc) {
             const uint32_t b = ov_bucket(q[0] + (cc % 3) - 1, q[1] + ((cc / 3) % 3) - 1, q[2] + (cc / 9) - 1, g.bk_mask);
             const int s = bs[b], e = s + bf[b];
@@ -496,7 +496,7 @@ __global__ void ov_result_kernel(ov_args g, int npairs)
 {
     const int k = threadIdx.x;
     if (k >= npairs) return;
-    const ov_pair *pp = cs_ptr<ov_pair>(g, k, 0);
+    const ov_pair *pp = lr_ptr<ov_pair>(g, k, 0);
     const ov_cloud &a = pp->c[0], &b = pp->c[1];
     lr_overlap_result r;
     r.status = (a.status == 2 || b.status == 2) ? 2 : ((a.status || b.status) ? 1 : 0);
@@ -528,8 +528,6 @@ extern "C" size_t lr_overlap_scratch_bytes(int max_n0, int max_n1)
     return ov_make_args(&g, (size_t)max_n0, (size_t)max_n1, 2);
 }
 
-#define OV_REQUIRE(cond, msg) do { if (!(cond)) { lr_set_error("%s: " msg, who); return LR_EINVAL; } } while (0)
-
 // every cloud of the call through stages 1..5
 static void ov_launch_clouds(const ov_desc_table &t, const ov_outs &outs, const ov_args &g, int npairs, int mx, hipStream_t st)
 {
@@ -552,25 +550,17 @@ static void ov_launch_clouds(const ov_desc_table &t, const ov_outs &outs, const 
     hipLaunchKernelGGL(ov_centroid_kernel, grid, dim3(256), 0, st, g, passes, outs);
 }
 
-static int ov_check_scratch(const char *who, void *scratch, size_t scratch_bytes, size_t need, const char *fn, void *stream)
-{
-    OV_REQUIRE(scratch, "null scratch");
-    if (scratch_bytes < need) { lr_set_error("%s: scratch too small (%s)", who, fn); return LR_EINVAL; }
-    OV_REQUIRE(((uintptr_t)scratch & 255) == 0, "scratch must be 256-byte aligned");
-    return lr_check_memory_device(scratch, (hipStream_t)stream, who, nullptr);
-}
-
 extern "C" int lr_voxel_mean(const double *xyz, int n, const double *T, double voxel_size, double *cent, float *cent_f32, int32_t *counts,
                              int32_t *first, int32_t *info, void *scratch, size_t scratch_bytes, void *stream)
 {
     const char *who = "lr_voxel_mean";
-    OV_REQUIRE(voxel_size > 0.0 && isfinite(voxel_size), "voxel_size must be positive and finite");
-    OV_REQUIRE(n >= 0 && n <= OV_MAX_N, "n must lie in 0..4194304");
-    OV_REQUIRE(info, "null info");
-    OV_REQUIRE(n == 0 || xyz, "null xyz");
+    LR_REFUSE_UNLESS(voxel_size > 0.0 && isfinite(voxel_size), LR_EINVAL, "voxel_size must be positive and finite");
+    LR_REFUSE_UNLESS(n >= 0 && n <= OV_MAX_N, LR_EINVAL, "n must lie in 0..4194304");
+    LR_REFUSE_UNLESS(info, LR_EINVAL, "null info");
+    LR_REFUSE_UNLESS(n == 0 || xyz, LR_EINVAL, "null xyz");
     ov_args g;
     const size_t need = ov_make_args(&g, (size_t)n, 0, 1);
-    LR_TRY_HIP(ov_check_scratch(who, scratch, scratch_bytes, need, "lr_voxel_mean_scratch_bytes(n)", stream));
+    LR_TRY_HIP(lr_check_scratch(who, scratch, scratch_bytes, need, "lr_voxel_mean_scratch_bytes(n)", LR_EINVAL, stream, nullptr));
     g.base = reinterpret_cast<char *>(scratch); g.stride = need;
     g.voxel = voxel_size; g.r = 0.0; g.g = 1.0;
     ov_desc_table t;
@@ -588,24 +578,24 @@ static int ov_run(const char *who, int npairs, const double *const *xyz0, const 
                   const double *const *T, const lr_overlap_params *p, lr_overlap_result *results, void *scratch, size_t scratch_bytes, void *stream)
 {
     LR_CHECK_STRUCT_SIZE(lr_overlap_params, p, who);
-    OV_REQUIRE(p->voxel_size > 0.0 && isfinite(p->voxel_size), "voxel_size must be positive and finite");
-    OV_REQUIRE(p->radius >= 0.0 && isfinite(p->radius), "radius must be finite and not negative");
+    LR_REFUSE_UNLESS(p->voxel_size > 0.0 && isfinite(p->voxel_size), LR_EINVAL, "voxel_size must be positive and finite");
+    LR_REFUSE_UNLESS(p->radius >= 0.0 && isfinite(p->radius), LR_EINVAL, "radius must be finite and not negative");
     // one centroid per voxel bounds what a search cell of edge r can hold; a radius far from the voxel size would unbound the search
-    OV_REQUIRE(p->radius == 0.0 || (p->radius >= p->voxel_size * 0.0625 && p->radius <= p->voxel_size * 4.0), "radius must be 0 or lie in voxel_size / 16 .. 4 voxel_size");
-    OV_REQUIRE(npairs >= 1 && npairs <= LR_MAX_BATCH, "npairs must lie in 1..64");
-    OV_REQUIRE(xyz0 && n0 && xyz1 && n1 && results, "null pointer");
+    LR_REFUSE_UNLESS(p->radius == 0.0 || (p->radius >= p->voxel_size * 0.0625 && p->radius <= p->voxel_size * 4.0), LR_EINVAL, "radius must be 0 or lie in voxel_size / 16 .. 4 voxel_size");
+    LR_REFUSE_UNLESS(npairs >= 1 && npairs <= LR_MAX_BATCH, LR_EINVAL, "npairs must lie in 1..64");
+    LR_REFUSE_UNLESS(xyz0 && n0 && xyz1 && n1 && results, LR_EINVAL, "null pointer");
     ov_desc_table t;
     memset(&t, 0, sizeof t);
     int mx0 = 0, mx1 = 0;
     for (int k = 0; k < npairs; ++k) {
-        OV_REQUIRE(n0[k] >= 0 && n0[k] <= OV_MAX_N && n1[k] >= 0 && n1[k] <= OV_MAX_N, "n0 / n1 must lie in 0..4194304");
-        OV_REQUIRE((n0[k] == 0 || xyz0[k]) && (n1[k] == 0 || xyz1[k]), "null xyz0 / xyz1");
+        LR_REFUSE_UNLESS(n0[k] >= 0 && n0[k] <= OV_MAX_N && n1[k] >= 0 && n1[k] <= OV_MAX_N, LR_EINVAL, "n0 / n1 must lie in 0..4194304");
+        LR_REFUSE_UNLESS((n0[k] == 0 || xyz0[k]) && (n1[k] == 0 || xyz1[k]), LR_EINVAL, "null xyz0 / xyz1");
         t.d[k] = ov_desc{ xyz0[k], xyz1[k], T ? T[k] : nullptr, n0[k], n1[k], results + k };
         mx0 = n0[k] > mx0 ? n0[k] : mx0; mx1 = n1[k] > mx1 ? n1[k] : mx1;
     }
     ov_args g;
     const size_t per = ov_make_args(&g, (size_t)mx0, (size_t)mx1, 2);
-    LR_TRY_HIP(ov_check_scratch(who, scratch, scratch_bytes, per * (size_t)npairs, "npairs * lr_overlap_scratch_bytes(max n0, max n1)", stream));
+    LR_TRY_HIP(lr_check_scratch(who, scratch, scratch_bytes, per * (size_t)npairs, "npairs * lr_overlap_scratch_bytes(max n0, max n1)", LR_EINVAL, stream, nullptr));
     g.base = reinterpret_cast<char *>(scratch); g.stride = per;
     g.voxel = p->voxel_size;
     g.r = p->radius == 0.0 ? sqrt(2.0) * p->voxel_size : p->radius;

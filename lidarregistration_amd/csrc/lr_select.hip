@@ -11,7 +11,7 @@
 // are computed again and the round ends there, the next one evaluating from the attempt after it.  A call enqueues a fixed number of
 // rounds; the control block's first word ends the loop: every later launch returns at its first instruction.
 // No host synchronisation, no floating-point atomic, no block waits on another one; every loop is bounded by n, SEL_T or the round count.
-#include "lr_internal.h"
+#include "lr_scratch.h"
 #include <float.h>
 #include <math.h>
 #include <string.h>
@@ -344,7 +344,7 @@ static size_t sel_make_layout(sel_layout *L, size_t n)
     L->ctl = 0;
     L->part = 1024;
     L->pts = L->part + (size_t)SEL_PART_BLOCKS * 16 * sizeof(double);
-    L->total = (L->pts + 6 * L->n_pad * sizeof(double) + 255) & ~(size_t)255;
+    L->total = lr_al(L->pts + 6 * L->n_pad * sizeof(double));
     return L->total;
 }
 
@@ -363,38 +363,33 @@ static long long sel_rounds_needed(long long n_draws, int n_request)
     return full < n_draws ? full : n_draws;
 }
 
-#define SEL_REQUIRE(cond, msg) do { if (!(cond)) { lr_set_error("%s: " msg, who); return LR_EINVAL; } } while (0)
-
 extern "C" int lr_balanced_select(const double *fields, const int32_t *session, const int32_t *n_cands, int n, int n_sessions,
                                   const double *draws, long long n_draws, const lr_select_params *p, uint8_t *alive, int32_t *n_sel,
                                   int32_t *out, lr_select_result *result, void *scratch, size_t scratch_bytes, void *stream)
 {
     const char *who = "lr_balanced_select";
     LR_CHECK_STRUCT_SIZE(lr_select_params, p, who);
-    SEL_REQUIRE(n >= 0 && n <= SEL_MAX_N, "n must lie in 0..4194304");
-    SEL_REQUIRE(n_sessions >= 1 && n_sessions <= SEL_MAX_SESSIONS, "n_sessions must lie in 1..65536");
-    SEL_REQUIRE(p->thresh > 0.0 && isfinite(p->thresh), "thresh must be positive and finite");
-    SEL_REQUIRE(p->n_request >= 0 && p->n_request <= n, "n_request must lie in 0..n");
-    SEL_REQUIRE(n_draws >= 0 && n_draws <= (1ll << 40), "n_draws must lie in 0..2^40");
-    SEL_REQUIRE(p->max_rounds >= 0 && p->max_rounds <= LR_SELECT_MAX_ROUNDS, "max_rounds must lie in 0..65536 (0: as many as the draws can need)");
-    SEL_REQUIRE(p->resume == 0 || p->resume == 1, "resume must be 0 or 1");
-    SEL_REQUIRE(n == 0 || fields, "null fields");
-    SEL_REQUIRE(n == 0 || session, "null session");
-    SEL_REQUIRE(n_cands, "null n_cands");
-    SEL_REQUIRE(n_draws == 0 || draws, "null draws");
-    SEL_REQUIRE(n == 0 || alive, "null alive");
-    SEL_REQUIRE(n_sel, "null n_sel");
-    SEL_REQUIRE(p->n_request == 0 || out, "null out");
-    SEL_REQUIRE(result, "null result");
-    SEL_REQUIRE(scratch, "null scratch");
-    sel_layout L;
-    const size_t need = sel_make_layout(&L, (size_t)n);
-    if (scratch_bytes < need) { lr_set_error("%s: scratch too small (lr_balanced_select_scratch_bytes(n))", who); return LR_EINVAL; }
-    SEL_REQUIRE(((uintptr_t)scratch & 255) == 0, "scratch must be 256-byte aligned");
+    LR_REFUSE_UNLESS(n >= 0 && n <= SEL_MAX_N, LR_EINVAL, "n must lie in 0..4194304");
+    LR_REFUSE_UNLESS(n_sessions >= 1 && n_sessions <= SEL_MAX_SESSIONS, LR_EINVAL, "n_sessions must lie in 1..65536");
+    LR_REFUSE_UNLESS(p->thresh > 0.0 && isfinite(p->thresh), LR_EINVAL, "thresh must be positive and finite");
+    LR_REFUSE_UNLESS(p->n_request >= 0 && p->n_request <= n, LR_EINVAL, "n_request must lie in 0..n");
+    LR_REFUSE_UNLESS(n_draws >= 0 && n_draws <= (1ll << 40), LR_EINVAL, "n_draws must lie in 0..2^40");
+    LR_REFUSE_UNLESS(p->max_rounds >= 0 && p->max_rounds <= LR_SELECT_MAX_ROUNDS, LR_EINVAL, "max_rounds must lie in 0..65536 (0: as many as the draws can need)");
+    LR_REFUSE_UNLESS(p->resume == 0 || p->resume == 1, LR_EINVAL, "resume must be 0 or 1");
+    LR_REFUSE_UNLESS(n == 0 || fields, LR_EINVAL, "null fields");
+    LR_REFUSE_UNLESS(n == 0 || session, LR_EINVAL, "null session");
+    LR_REFUSE_UNLESS(n_cands, LR_EINVAL, "null n_cands");
+    LR_REFUSE_UNLESS(n_draws == 0 || draws, LR_EINVAL, "null draws");
+    LR_REFUSE_UNLESS(n == 0 || alive, LR_EINVAL, "null alive");
+    LR_REFUSE_UNLESS(n_sel, LR_EINVAL, "null n_sel");
+    LR_REFUSE_UNLESS(p->n_request == 0 || out, LR_EINVAL, "null out");
+    LR_REFUSE_UNLESS(result, LR_EINVAL, "null result");
     long long rounds = sel_rounds_needed(n_draws, p->n_request);
     if (p->max_rounds > 0 && rounds > p->max_rounds) rounds = p->max_rounds;
-    SEL_REQUIRE(rounds <= LR_SELECT_MAX_ROUNDS, "these draws can need more than 65536 rounds: pass fewer draws per call, or set max_rounds");
-    LR_TRY_HIP(lr_check_memory_device(scratch, (hipStream_t)stream, who, nullptr));
+    LR_REFUSE_UNLESS(rounds <= LR_SELECT_MAX_ROUNDS, LR_EINVAL, "these draws can need more than 65536 rounds: pass fewer draws per call, or set max_rounds");
+    sel_layout L;
+    const size_t need = sel_make_layout(&L, (size_t)n);
+    LR_TRY_HIP(lr_check_scratch(who, scratch, scratch_bytes, need, "lr_balanced_select_scratch_bytes(n)", LR_EINVAL, stream, nullptr));
     sel_args g;
     memset(&g, 0, sizeof g);
     char *base = reinterpret_cast<char *>(scratch);

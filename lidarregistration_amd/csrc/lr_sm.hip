@@ -74,11 +74,11 @@ static sm_layout sm_make_layout(int max_m)
     if (items < rb) items = rb;
     sm_layout L;
     size_t o = 0;
-    L.ctl = o;    o += cs_al(sizeof(sm_ctl));
-    L.rec = o;    o += cs_al(Mp * 32);
-    L.part = o;   o += cs_al(items * 64 * 4);
-    L.rowsum = o; o += cs_al(Mp * 8);
-    L.sel = o;    o += cs_al(Mp * 4);
+    L.ctl = o;    o += lr_al(sizeof(sm_ctl));
+    L.rec = o;    o += lr_al(Mp * 32);
+    L.part = o;   o += lr_al(items * 64 * 4);
+    L.rowsum = o; o += lr_al(Mp * 8);
+    L.sel = o;    o += lr_al(Mp * 4);
     L.total = o;
     return L;
 }
@@ -96,7 +96,7 @@ __global__ void sm_setup_kernel(cs_desc_table t, sm_args g, int npairs, double t
     const int k = threadIdx.x;
     if (k >= npairs) return;
     const cs_desc d = t.d[k];
-    sm_ctl *c = cs_ptr<sm_ctl>(g, k, g.L.ctl);
+    sm_ctl *c = lr_ptr<sm_ctl>(g, k, g.L.ctl);
     const int m = cs_live_m(d);
     const sm_plan p = sm_make_plan(m, g.target);
     c->a = d.a; c->b = d.b; c->eig_out = (float *)d.out0; c->labels_out = (uint8_t *)d.out1;
@@ -110,10 +110,10 @@ __global__ void sm_setup_kernel(cs_desc_table t, sm_args g, int npairs, double t
 __global__ void __launch_bounds__(256) sm_pack_kernel(sm_args g)
 {
     const int pair = blockIdx.z;
-    const sm_ctl *c = cs_ptr<sm_ctl>(g, pair, g.L.ctl);
+    const sm_ctl *c = lr_ptr<sm_ctl>(g, pair, g.L.ctl);
     const int m = c->m, m4 = (m + 3) & ~3, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= m4) return;
-    float *rec = cs_ptr<float>(g, pair, g.L.rec) + (size_t)i * 8;
+    float *rec = lr_ptr<float>(g, pair, g.L.rec) + (size_t)i * 8;
     float r[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
     bool ok = i < m;
     if (ok) {
@@ -226,12 +226,12 @@ __global__ void __launch_bounds__(SM_NB) sm_norm_kernel(sm_args g, int last)
 {
     __shared__ double s_red[SM_NB];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const sm_ctl *c = cs_ptr<sm_ctl>(g, pair, g.L.ctl);
+    const sm_ctl *c = lr_ptr<sm_ctl>(g, pair, g.L.ctl);
     const int m = c->m, chunks = c->chunks, Mp = c->rb * 64;
     if (m <= 0) return;
-    const float *part = cs_ptr<float>(g, pair, g.L.part);
-    double *rowsum = cs_ptr<double>(g, pair, g.L.rowsum);
-    float *rec = cs_ptr<float>(g, pair, g.L.rec);
+    const float *part = lr_ptr<float>(g, pair, g.L.part);
+    double *rowsum = lr_ptr<double>(g, pair, g.L.rowsum);
+    float *rec = lr_ptr<float>(g, pair, g.L.rec);
     double q = 0.0;
     for (int i = tid; i < m; i += SM_NB) {
         double s = 0.0;
@@ -255,10 +255,10 @@ __global__ void __launch_bounds__(SM_NB) sm_select_kernel(sm_args g)
     __shared__ int s_cnt[SM_NB / 64];
     __shared__ unsigned s_pick[2];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    sm_ctl *c = cs_ptr<sm_ctl>(g, pair, g.L.ctl);
+    sm_ctl *c = lr_ptr<sm_ctl>(g, pair, g.L.ctl);
     const int m = c->m, mh = c->m_host, K = c->K;
-    const uint32_t *rec = cs_ptr<uint32_t>(g, pair, g.L.rec);
-    int32_t *sel = cs_ptr<int32_t>(g, pair, g.L.sel);
+    const uint32_t *rec = lr_ptr<uint32_t>(g, pair, g.L.rec);
+    int32_t *sel = lr_ptr<int32_t>(g, pair, g.L.sel);
     uint8_t *labels = c->labels_out;
     float *eig = c->eig_out;
     // the K-th largest value: its bits (v >= 0), most significant byte first
@@ -311,10 +311,10 @@ __global__ void __launch_bounds__(SM_FB) sm_fit_kernel(sm_args g, lr_sm_result *
 {
     __shared__ double s_red[SM_FB];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    const sm_ctl *c = cs_ptr<sm_ctl>(g, pair, g.L.ctl);
+    const sm_ctl *c = lr_ptr<sm_ctl>(g, pair, g.L.ctl);
     const int K = c->K, n = c->nsel;
-    const float *rec = cs_ptr<float>(g, pair, g.L.rec);
-    const int32_t *sel = cs_ptr<int32_t>(g, pair, g.L.sel);
+    const float *rec = lr_ptr<float>(g, pair, g.L.rec);
+    const int32_t *sel = lr_ptr<int32_t>(g, pair, g.L.sel);
     const float *a = c->a, *b = c->b;
     lr_sm_result *res = results + pair;
     // weights w = v of the selected entries; an entry of weight 0 adds nothing and is not read (its coordinates may be non-finite)
@@ -382,7 +382,7 @@ static int sm_run(const char *who, int npairs, const float *const *src, const fl
                   const lr_sm_params *p, lr_sm_result *results, float *const *eig_out, uint8_t *const *labels_out,
                   void *scratch, size_t scratch_bytes, void *stream)
 {
-    static const cs_backend be = { "lr_sm_batch", "lr_sm_scratch_bytes", lr_sm_scratch_bytes, LR_EINVAL };
+    static const cs_backend be = { "lr_sm_batch", "npairs * lr_sm_scratch_bytes(max m)", lr_sm_scratch_bytes, LR_EINVAL };
     LR_TRY_HIP(check_sm_params(p, who));
     cs_front f;
     LR_TRY_HIP(cs_check_batch(be, npairs, src, tgt, m, m_dev, (void *const *)eig_out, (void *const *)labels_out, results, scratch, scratch_bytes, stream, &f));

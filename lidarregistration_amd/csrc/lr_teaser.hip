@@ -50,21 +50,21 @@ static tz_layout tz_make_layout(int max_m)
     const size_t W = (size_t)tz_words(max_m < 1 ? 1 : max_m), Mp = W * 64;
     tz_layout L;
     size_t o = 0;
-    L.ctl = o;    o += cs_al(sizeof(tz_ctl));
-    L.adj = o;    o += cs_al(Mp * W * 8);
-    L.cadj = o;   o += cs_al(Mp * W * 8);
-    L.stack = o;  o += cs_al((Mp + 1) * W * 8);
-    L.core = o;   o += cs_al(Mp * 4);
-    L.rlist = o;  o += cs_al(Mp * 4);
-    L.cstack = o; o += cs_al(Mp * 4);
-    L.bestc = o;  o += cs_al(Mp * 4);
-    L.clique = o; o += cs_al(Mp * 4);
-    L.pidx = o;   o += cs_al(Mp * 4);
-    L.bits = o;   o += cs_al(3 * W * 8);       // [0] incumbent clique, [1] universal vertices, [2] final clique
-    L.tim = o;    o += cs_al(6 * Mp * 8);
-    L.wgt = o;    o += cs_al(Mp * 8);
-    L.xv = o;     o += cs_al(3 * Mp * 8);
-    L.ecost = o;  o += cs_al(3 * 2 * Mp * 8);
+    L.ctl = o;    o += lr_al(sizeof(tz_ctl));
+    L.adj = o;    o += lr_al(Mp * W * 8);
+    L.cadj = o;   o += lr_al(Mp * W * 8);
+    L.stack = o;  o += lr_al((Mp + 1) * W * 8);
+    L.core = o;   o += lr_al(Mp * 4);
+    L.rlist = o;  o += lr_al(Mp * 4);
+    L.cstack = o; o += lr_al(Mp * 4);
+    L.bestc = o;  o += lr_al(Mp * 4);
+    L.clique = o; o += lr_al(Mp * 4);
+    L.pidx = o;   o += lr_al(Mp * 4);
+    L.bits = o;   o += lr_al(3 * W * 8);       // [0] incumbent clique, [1] universal vertices, [2] final clique
+    L.tim = o;    o += lr_al(6 * Mp * 8);
+    L.wgt = o;    o += lr_al(Mp * 8);
+    L.xv = o;     o += lr_al(3 * Mp * 8);
+    L.ecost = o;  o += lr_al(3 * 2 * Mp * 8);
     L.total = o;
     return L;
 }
@@ -89,7 +89,7 @@ __global__ void tz_setup_kernel(cs_desc_table t, tz_args g, int npairs)
     const int k = threadIdx.x;
     if (k >= npairs) return;
     const cs_desc d = t.d[k];
-    tz_ctl *c = cs_ptr<tz_ctl>(g, k, g.L.ctl);
+    tz_ctl *c = lr_ptr<tz_ctl>(g, k, g.L.ctl);
     const int m = cs_live_m(d);
     c->a = d.a; c->b = d.b; c->clique_out = (int32_t *)d.out0;
     c->m = m; c->W = tz_words(m);
@@ -125,11 +125,11 @@ __device__ __forceinline__ bool tz_edge(float aix, float aiy, float aiz, float b
 __global__ void __launch_bounds__(256) tz_graph_kernel(tz_args g, double thr)
 {
     const int pair = blockIdx.z;
-    const tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
+    const tz_ctl *c = lr_ptr<tz_ctl>(g, pair, g.L.ctl);
     const int m = c->m, i0 = blockIdx.x * 64, chunk = blockIdx.y * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i0 >= m || chunk * 64 >= m) return;
     const float *__restrict__ a = c->a, *__restrict__ b = c->b;
-    unsigned long long *adj = cs_ptr<unsigned long long>(g, pair, g.L.adj);
+    unsigned long long *adj = lr_ptr<unsigned long long>(g, pair, g.L.adj);
     const float thr32 = (float)thr;
     const int j = chunk * 64 + lane;
     const bool jv = j < m;
@@ -176,12 +176,12 @@ __global__ void __launch_bounds__(1024) tz_peel_kernel(tz_args g, double kcore_t
     __shared__ int s_red[16], s_gsize[TZ_GREEDY_WAVES];
     __shared__ int s_seed[TZ_GREEDY_WAVES];
     const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
+    tz_ctl *c = lr_ptr<tz_ctl>(g, pair, g.L.ctl);
     const int m = c->m, W = c->W, Ws = g.Wmax;
     if (m == 0) { if (tid == 0) c->done = 1; return; }
-    const unsigned long long *adj = cs_ptr<unsigned long long>(g, pair, g.L.adj);
-    int32_t *core = cs_ptr<int32_t>(g, pair, g.L.core);
-    unsigned long long *bits = cs_ptr<unsigned long long>(g, pair, g.L.bits);
+    const unsigned long long *adj = lr_ptr<unsigned long long>(g, pair, g.L.adj);
+    int32_t *core = lr_ptr<int32_t>(g, pair, g.L.core);
+    unsigned long long *bits = lr_ptr<unsigned long long>(g, pair, g.L.bits);
     unsigned long long *inc = bits, *ubits = bits + Ws, *fin = bits + 2 * Ws;
 
     // degrees (popcount of the rows) and the alive set
@@ -341,7 +341,7 @@ __global__ void __launch_bounds__(1024) tz_peel_kernel(tz_args g, double kcore_t
         return;
     }
     // compact list of the remaining vertices, ascending
-    int32_t *rlist = cs_ptr<int32_t>(g, pair, g.L.rlist);
+    int32_t *rlist = lr_ptr<int32_t>(g, pair, g.L.rlist);
     if (tid == 0) {
         int off = 0;
         for (int w = 0; w < W; ++w) { const int pc = __popcll(s_alive[w]); s_deg[w] = off; off += pc; }    // (s_deg is free again)
@@ -359,12 +359,12 @@ __global__ void __launch_bounds__(1024) tz_peel_kernel(tz_args g, double kcore_t
 __global__ void __launch_bounds__(256) tz_compact_kernel(tz_args g)
 {
     const int pair = blockIdx.y;
-    const tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
+    const tz_ctl *c = lr_ptr<tz_ctl>(g, pair, g.L.ctl);
     if (c->done) return;
     const int n = c->nR, Wn = tz_words(n), Ws = g.Wmax;
-    const unsigned long long *adj = cs_ptr<unsigned long long>(g, pair, g.L.adj);
-    unsigned long long *cadj = cs_ptr<unsigned long long>(g, pair, g.L.cadj);
-    const int32_t *rlist = cs_ptr<int32_t>(g, pair, g.L.rlist);
+    const unsigned long long *adj = lr_ptr<unsigned long long>(g, pair, g.L.adj);
+    unsigned long long *cadj = lr_ptr<unsigned long long>(g, pair, g.L.cadj);
+    const int32_t *rlist = lr_ptr<int32_t>(g, pair, g.L.rlist);
     for (int r = blockIdx.x; r < n; r += gridDim.x) {
         const unsigned long long *row = adj + (size_t)rlist[r] * Ws;
         for (int w = threadIdx.x; w < Wn; w += 256) {
@@ -394,20 +394,20 @@ __device__ __forceinline__ int tz_lowest(const unsigned long long (&x)[TZ_NWL], 
 __global__ void __launch_bounds__(64) tz_search_kernel(tz_args g, long long node_budget, unsigned long long tick_budget)
 {
     const int pair = blockIdx.x, lane = threadIdx.x;
-    tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
+    tz_ctl *c = lr_ptr<tz_ctl>(g, pair, g.L.ctl);
     const int m = c->m, W = c->W, Ws = g.Wmax;
-    unsigned long long *bits = cs_ptr<unsigned long long>(g, pair, g.L.bits);
+    unsigned long long *bits = lr_ptr<unsigned long long>(g, pair, g.L.bits);
     unsigned long long *inc = bits, *ubits = bits + Ws, *fin = bits + 2 * Ws;
-    int32_t *clique = cs_ptr<int32_t>(g, pair, g.L.clique);
+    int32_t *clique = lr_ptr<int32_t>(g, pair, g.L.clique);
     if (m == 0) { if (lane == 0) { c->K = 0; c->exact = 1; c->nodes = 0; } return; }
     long long nodes = 0;
     int aborted = 0;
     if (!c->done) {
         const int n = c->nR, Wn = tz_words(n);
-        const unsigned long long *cadj = cs_ptr<unsigned long long>(g, pair, g.L.cadj);
-        unsigned long long *stack = cs_ptr<unsigned long long>(g, pair, g.L.stack);
-        int32_t *cstack = cs_ptr<int32_t>(g, pair, g.L.cstack), *bestc = cs_ptr<int32_t>(g, pair, g.L.bestc);
-        const int32_t *rlist = cs_ptr<int32_t>(g, pair, g.L.rlist);
+        const unsigned long long *cadj = lr_ptr<unsigned long long>(g, pair, g.L.cadj);
+        unsigned long long *stack = lr_ptr<unsigned long long>(g, pair, g.L.stack);
+        int32_t *cstack = lr_ptr<int32_t>(g, pair, g.L.cstack), *bestc = lr_ptr<int32_t>(g, pair, g.L.bestc);
+        const int32_t *rlist = lr_ptr<int32_t>(g, pair, g.L.rlist);
         int best = c->target, found = 0;
         for (int w = lane; w < Wn; w += 64) { const int lo = w * 64; stack[w] = (n - lo >= 64) ? ~0ull : ((1ull << (n - lo)) - 1ull); }
         tz_wsync();
@@ -589,12 +589,12 @@ __global__ void __launch_bounds__(TZ_RB) tz_rot_kernel(tz_args g, double nb2, do
     __shared__ double s_red[10][TZ_RB];
     __shared__ double s_R[9];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
+    tz_ctl *c = lr_ptr<tz_ctl>(g, pair, g.L.ctl);
     const int K = c->K;
     if (K < 3) { if (tid == 0) c->status = 1; return; }
     const size_t Mp = (size_t)g.Wmax * 64;
-    const int32_t *clique = cs_ptr<int32_t>(g, pair, g.L.clique);
-    double *tim = cs_ptr<double>(g, pair, g.L.tim), *wgt = cs_ptr<double>(g, pair, g.L.wgt);
+    const int32_t *clique = lr_ptr<int32_t>(g, pair, g.L.clique);
+    double *tim = lr_ptr<double>(g, pair, g.L.tim), *wgt = lr_ptr<double>(g, pair, g.L.wgt);
     const float *a = c->a, *b = c->b;
     double v[10];
     for (int i = 0; i < 10; ++i) v[i] = 0.0;
@@ -643,8 +643,8 @@ __global__ void __launch_bounds__(TZ_RB) tz_rot_kernel(tz_args g, double nb2, do
     }
     // rotation inliers (w >= 0.5; all when GNC did not start) -> participating clique points, ascending, and their x = b - R a
     __shared__ int s_cnt[TZ_RB / 64 + 1];
-    int32_t *pidx = cs_ptr<int32_t>(g, pair, g.L.pidx);
-    double *xv = cs_ptr<double>(g, pair, g.L.xv);
+    int32_t *pidx = lr_ptr<int32_t>(g, pair, g.L.pidx);
+    double *xv = lr_ptr<double>(g, pair, g.L.xv);
     int base = 0;
     for (int k0 = 0; k0 < K; k0 += TZ_RB) {
         const int k = k0 + tid;
@@ -687,13 +687,13 @@ __global__ void __launch_bounds__(256) tz_vote_kernel(tz_args g, double beta)
 {
     __shared__ double s_x[256];
     const int pair = blockIdx.z, axis = blockIdx.y, tid = threadIdx.x;
-    const tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
+    const tz_ctl *c = lr_ptr<tz_ctl>(g, pair, g.L.ctl);
     if (c->status) return;
     const int n = c->n_part;
     if ((int)blockIdx.x * 256 >= 2 * n) return;
     const size_t Mp = (size_t)g.Wmax * 64;
-    const double *x = cs_ptr<double>(g, pair, g.L.xv) + axis * Mp;
-    double *ecost = cs_ptr<double>(g, pair, g.L.ecost) + axis * 2 * Mp;
+    const double *x = lr_ptr<double>(g, pair, g.L.xv) + axis * Mp;
+    double *ecost = lr_ptr<double>(g, pair, g.L.ecost) + axis * 2 * Mp;
     const int e = blockIdx.x * 256 + tid;
     const bool ev = e < 2 * n;
     const int ie = e >> 1, te = e & 1;
@@ -724,16 +724,16 @@ __global__ void __launch_bounds__(256) tz_final_kernel(tz_args g, double beta, l
     __shared__ double s_red[10][TZ_RB];
     __shared__ double s_t[3];
     const int pair = blockIdx.x, tid = threadIdx.x;
-    tz_ctl *c = cs_ptr<tz_ctl>(g, pair, g.L.ctl);
+    tz_ctl *c = lr_ptr<tz_ctl>(g, pair, g.L.ctl);
     lr_teaser_result *res = results + pair;
     const int status = c->status, n = c->n_part;
     const size_t Mp = (size_t)g.Wmax * 64;
-    const double *xv = cs_ptr<double>(g, pair, g.L.xv);
+    const double *xv = lr_ptr<double>(g, pair, g.L.xv);
     int ntrans = 0;
     if (!status) {
         for (int axis = 0; axis < 3; ++axis) {
             const double *x = xv + axis * Mp;
-            const double *ec = cs_ptr<double>(g, pair, g.L.ecost) + axis * 2 * Mp;
+            const double *ec = lr_ptr<double>(g, pair, g.L.ecost) + axis * 2 * Mp;
             // first minimum: smallest (cost, key)
             double bc = INFINITY, bv = 0; int be = -1;
             for (int e = tid; e < 2 * n; e += 256) {
@@ -844,7 +844,7 @@ static int tz_run(const char *who, int npairs, const float *const *src, const fl
                   const int32_t *const *m_dev, const lr_teaser_params *p, lr_teaser_result *results,
                   int32_t *const *clique_out, void *scratch, size_t scratch_bytes, void *stream)
 {
-    static const cs_backend be = { "lr_teaser_batch", "lr_teaser_scratch_bytes", lr_teaser_scratch_bytes, LR_ESIZE };
+    static const cs_backend be = { "lr_teaser_batch", "npairs * lr_teaser_scratch_bytes(max m)", lr_teaser_scratch_bytes, LR_ESIZE };
     LR_TRY_HIP(check_teaser_params(p, who));
     cs_front f;
     LR_TRY_HIP(cs_check_batch(be, npairs, src, tgt, m, m_dev, (void *const *)clique_out, nullptr, results, scratch, scratch_bytes, stream, &f));

@@ -13,26 +13,12 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _ext
+from . import _ext, devmem
+from .devmem import T_dev, as_dict, f64, ptr, read_struct
 from .matching import _device, _stream
 
 OVERLAP_VOXEL = 1.0         # GenerateBalancedSet.py:171
 MAX_PAIRS = 64              # pairs per lr_overlap_batch call
-
-
-def _f64(X, dev):
-    return torch.as_tensor(X).to(device=dev, dtype=torch.float64).contiguous().reshape(-1, 3)
-
-
-def _T_dev(T, dev):
-    return None if T is None else torch.as_tensor(np.ascontiguousarray(T, np.float64).reshape(16)).to(dev)
-
-
-def _scratch(nbytes, dev, poison):
-    s = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-    if poison is not None:
-        s.fill_(int(poison))
-    return s
 
 
 def voxel_mean_dev(X, voxel_size, T=None, poison=None):
@@ -40,17 +26,17 @@ def voxel_mean_dev(X, voxel_size, T=None, poison=None):
     the rows -- cent [rows,3] float64, cent_f32 [rows,3] float32, counts, first (int32) -- and rows, dropped, status (ints).
     poison: fill the scratch with this byte first (test hook)."""
     dev = _device()
-    x = _f64(X, dev)
+    x = f64(X, dev)
     n = int(x.shape[0])
     L = _ext.lib()
-    Td = _T_dev(T, dev)
+    Td = T_dev(T, dev)
     m = max(n, 1)
     cent = torch.empty((m, 3), dtype=torch.float64, device=dev); cent32 = torch.empty((m, 3), dtype=torch.float32, device=dev)
     counts = torch.empty(m, dtype=torch.int32, device=dev); first = torch.empty(m, dtype=torch.int32, device=dev)
     info = torch.empty(4, dtype=torch.int32, device=dev)
-    scratch = _scratch(L.lr_voxel_mean_scratch_bytes(n), dev, poison)
-    _ext.check(L.lr_voxel_mean(x.data_ptr() if n else None, n, None if Td is None else Td.data_ptr(), float(voxel_size), cent.data_ptr(),
-                               cent32.data_ptr(), counts.data_ptr(), first.data_ptr(), info.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
+    scratch = devmem.scratch(L.lr_voxel_mean_scratch_bytes(n), dev, poison)
+    _ext.check(L.lr_voxel_mean(ptr(x, n), n, ptr(Td), float(voxel_size), cent.data_ptr(), cent32.data_ptr(), counts.data_ptr(), first.data_ptr(),
+                               info.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
     rows, dropped, status, _ = (int(v) for v in info.cpu())
     return dict(cent=cent[:rows], cent_f32=cent32[:rows], counts=counts[:rows], first=first[:rows], rows=rows, dropped=dropped, status=status)
 
@@ -66,24 +52,18 @@ def voxel_down_sample(X, voxel_size, T=None, return_counts=False):
     return (r["cent"], r["counts"]) if return_counts else r["cent"]
 
 
-def _result(buf, k=0):
-    r = _ext.OverlapResult.from_buffer_copy(buf[k].cpu().numpy().tobytes())
-    return {name: getattr(r, name) for name, _ in _ext.OverlapResult._fields_}
-
-
 def overlap_dev(A, B, T=None, voxel_size=OVERLAP_VOXEL, radius=0.0, poison=None):
     """lr_overlap on one pair: A [n0,3] (moved by T, 4x4, if given) against B [n1,3].  Returns the lr_overlap_result as a dict."""
     dev = _device()
-    a, b = _f64(A, dev), _f64(B, dev)
+    a, b = f64(A, dev), f64(B, dev)
     n0, n1 = int(a.shape[0]), int(b.shape[0])
     L = _ext.lib()
-    Td = _T_dev(T, dev)
+    Td = T_dev(T, dev)
     p = _ext.OverlapParams(voxel_size=float(voxel_size), radius=float(radius))
     res = torch.zeros((1, ctypes.sizeof(_ext.OverlapResult)), dtype=torch.uint8, device=dev)
-    scratch = _scratch(L.lr_overlap_scratch_bytes(n0, n1), dev, poison)
-    _ext.check(L.lr_overlap(a.data_ptr() if n0 else None, n0, b.data_ptr() if n1 else None, n1, None if Td is None else Td.data_ptr(),
-                            ctypes.byref(p), res.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
-    return _result(res)
+    scratch = devmem.scratch(L.lr_overlap_scratch_bytes(n0, n1), dev, poison)
+    _ext.check(L.lr_overlap(ptr(a, n0), n0, ptr(b, n1), n1, ptr(Td), ctypes.byref(p), res.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
+    return as_dict(read_struct(res, _ext.OverlapResult))
 
 
 def overlap_batch_dev(pairs, voxel_size=OVERLAP_VOXEL, radius=0.0, poison=None):
@@ -92,18 +72,18 @@ def overlap_batch_dev(pairs, voxel_size=OVERLAP_VOXEL, radius=0.0, poison=None):
     dev = _device()
     npairs = len(pairs)
     L = _ext.lib()
-    As = [_f64(pr[0], dev) for pr in pairs]; Bs = [_f64(pr[1], dev) for pr in pairs]
-    Ts = [_T_dev(pr[2] if len(pr) > 2 else None, dev) for pr in pairs]
+    As = [f64(pr[0], dev) for pr in pairs]; Bs = [f64(pr[1], dev) for pr in pairs]
+    Ts = [T_dev(pr[2] if len(pr) > 2 else None, dev) for pr in pairs]
     n0 = [int(a.shape[0]) for a in As]; n1 = [int(b.shape[0]) for b in Bs]
-    ptrs = lambda ts, ns: (ctypes.c_void_p * npairs)(*[t.data_ptr() if n else None for t, n in zip(ts, ns)])
-    tp = (ctypes.c_void_p * npairs)(*[None if t is None else t.data_ptr() for t in Ts])
+    ptrs = lambda ts, ns: (ctypes.c_void_p * npairs)(*[ptr(t, n) for t, n in zip(ts, ns)])
+    tp = (ctypes.c_void_p * npairs)(*[ptr(t) for t in Ts])
     p = _ext.OverlapParams(voxel_size=float(voxel_size), radius=float(radius))
     res = torch.zeros((max(npairs, 1), ctypes.sizeof(_ext.OverlapResult)), dtype=torch.uint8, device=dev)
     per = L.lr_overlap_scratch_bytes(max(n0, default=0), max(n1, default=0))
-    scratch = _scratch(per * npairs, dev, poison)
+    scratch = devmem.scratch(per * npairs, dev, poison)
     _ext.check(L.lr_overlap_batch(npairs, ptrs(As, n0), (ctypes.c_int32 * npairs)(*n0), ptrs(Bs, n1), (ctypes.c_int32 * npairs)(*n1), tp,
                                   ctypes.byref(p), res.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
-    return [_result(res, k) for k in range(npairs)]
+    return [as_dict(read_struct(res, _ext.OverlapResult, k)) for k in range(npairs)]
 
 
 def _fractions(r, who):
@@ -133,8 +113,8 @@ def refine_inputs(GT_mot_orig, A, B, downsample=True, voxel_size=0.3):
     """What refine_motion hands to the ICP (GenerateBalancedSet.py:233-243): (a moved by GT_mot_orig, b) as float32 device clouds; the
     down-sampling and the transform are float64."""
     dev = _device()
-    a = voxel_down_sample(A, voxel_size) if downsample else _f64(A, dev)
-    b = voxel_down_sample(B, voxel_size) if downsample else _f64(B, dev)
+    a = voxel_down_sample(A, voxel_size) if downsample else f64(A, dev)
+    b = voxel_down_sample(B, voxel_size) if downsample else f64(B, dev)
     M = np.ascontiguousarray(GT_mot_orig, np.float64)
     x, y, z = a[:, 0], a[:, 1], a[:, 2]
     a_corr = torch.stack([((float(M[r, 0]) * x + float(M[r, 1]) * y) + float(M[r, 2]) * z) + float(M[r, 3]) for r in range(3)], dim=1)
@@ -160,15 +140,15 @@ def nearest_neighbour_dev(A, B, cell=0.0, poison=None):
     target), status (1: no finite target), n0_dropped, n1_dropped, n_far (queries resolved by the second phase).  cell: edge of the
     search grid, 0 = automatic; the result does not depend on it."""
     dev = _device()
-    a, b = _f64(A, dev), _f64(B, dev)
+    a, b = f64(A, dev), f64(B, dev)
     n0, n1 = int(a.shape[0]), int(b.shape[0])
     L = _ext.lib()
     idx = torch.empty(max(n0, 1), dtype=torch.int32, device=dev); dist = torch.empty(max(n0, 1), dtype=torch.float64, device=dev)
     info = torch.empty(4, dtype=torch.int32, device=dev)
     p = _ext.Nn3Params(cell=float(cell))
-    scratch = _scratch(L.lr_nn3_scratch_bytes(n0, n1), dev, poison)
-    _ext.check(L.lr_nn3(a.data_ptr() if n0 else None, n0, b.data_ptr() if n1 else None, n1, ctypes.byref(p), idx.data_ptr(), dist.data_ptr(),
-                        info.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
+    scratch = devmem.scratch(L.lr_nn3_scratch_bytes(n0, n1), dev, poison)
+    _ext.check(L.lr_nn3(ptr(a, n0), n0, ptr(b, n1), n1, ctypes.byref(p), idx.data_ptr(), dist.data_ptr(), info.data_ptr(), scratch.data_ptr(),
+                        scratch.numel(), _stream()))
     status, d0, d1, far = (int(v) for v in info.cpu())
     return dict(dist=dist[:n0], idx=idx[:n0], status=status, n0_dropped=d0, n1_dropped=d1, n_far=far)
 
@@ -183,17 +163,15 @@ def nearest_neighbour(A, B):
 def refine_z_dev(A, B, T=None, xy_gate=0.3, max_repeats=10, min_change=1e-6, cell=0.0, poison=None):
     """lr_refine_z: A [n0,3] (moved by T, 4x4, if given) against B [n1,3], the clouds as given.  Returns the lr_refine_z_result as a dict."""
     dev = _device()
-    a, b = _f64(A, dev), _f64(B, dev)
+    a, b = f64(A, dev), f64(B, dev)
     n0, n1 = int(a.shape[0]), int(b.shape[0])
     L = _ext.lib()
-    Td = _T_dev(T, dev)
+    Td = T_dev(T, dev)
     p = _ext.RefineZParams(xy_gate=float(xy_gate), max_repeats=int(max_repeats), min_change=float(min_change), cell=float(cell))
     res = torch.zeros((1, ctypes.sizeof(_ext.RefineZResult)), dtype=torch.uint8, device=dev)
-    scratch = _scratch(L.lr_refine_z_scratch_bytes(n0, n1), dev, poison)
-    _ext.check(L.lr_refine_z(a.data_ptr() if n0 else None, n0, b.data_ptr() if n1 else None, n1, None if Td is None else Td.data_ptr(),
-                             ctypes.byref(p), res.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
-    r = _ext.RefineZResult.from_buffer_copy(res[0].cpu().numpy().tobytes())
-    return {name: getattr(r, name) for name, _ in _ext.RefineZResult._fields_}
+    scratch = devmem.scratch(L.lr_refine_z_scratch_bytes(n0, n1), dev, poison)
+    _ext.check(L.lr_refine_z(ptr(a, n0), n0, ptr(b, n1), n1, ptr(Td), ctypes.byref(p), res.data_ptr(), scratch.data_ptr(), scratch.numel(), _stream()))
+    return as_dict(read_struct(res, _ext.RefineZResult))
 
 
 def refine_motion_Z_only(raw_mot, A, B, voxel_size, return_info=False):
@@ -214,8 +192,8 @@ def refine_GT(GT_mot_orig, A, B, downsample=True, voxel_size=0.3, z_only=False):
     if not z_only:
         return refine_motion(GT_mot_orig, A, B, downsample, voxel_size)
     dev = _device()
-    a = voxel_down_sample(A, voxel_size) if downsample else _f64(A, dev)
-    b = voxel_down_sample(B, voxel_size) if downsample else _f64(B, dev)
+    a = voxel_down_sample(A, voxel_size) if downsample else f64(A, dev)
+    b = voxel_down_sample(B, voxel_size) if downsample else f64(B, dev)
     return refine_motion_Z_only(GT_mot_orig, a, b, voxel_size)
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _ext
+from .devmem import as_dict, read_struct
 from .matching import _device, _f32, _i32, _stream, workspace
 
 DEFAULT_SEED = 51          # Experiments/test.py:357
@@ -48,7 +49,7 @@ def ransac_dev(src, tgt, iters, sample_size=3, use_elc=True, thr=0.6, seed=DEFAU
         nin = torch.zeros(1, dtype=torch.int32, device=src.device)
         _ext.check(_ext.lib().lr_inlier_mask(ws.handle, src.data_ptr(), tgt.data_ptr(), m, T.data_ptr(), ctypes.c_float(p.effective_thr2()),
                                               mask.data_ptr(), nin.data_ptr(), _stream()))
-    r = _ext.RansacResult.from_buffer_copy(res.cpu().numpy().tobytes())          # (the one synchronisation of the call)
+    r = read_struct(res, _ext.RansacResult)          # (the one synchronisation of the call)
     info = dict(best_h=r.best_h, best_count=r.best_count, best_ssq=r.best_ssq, n_valid=r.n_valid, n_ids=r.n_ids)
     if want_mask:
         if r.best_h < 0:          # no model (pygcransac returns pose None there): the mask of nothing
@@ -87,8 +88,7 @@ def icp_dev(xyz0, xyz1, T_init, max_dist=0.6, max_iter=30, rel_fitness=1e-6, rel
     xyz0, xyz1 = _f32(xyz0), _f32(xyz1)
     Tin = torch.as_tensor(np.ascontiguousarray(T_init, np.float64).reshape(16)).to(xyz0.device)
     Tout, res = icp_launch(workspace(xyz0.shape[0], xyz1.shape[0]), xyz0, xyz1, Tin.data_ptr(), _stream(), max_dist, max_iter, rel_fitness, rel_rmse)
-    r = _ext.IcpResult.from_buffer_copy(res.cpu().numpy().tobytes())
-    return Tout.cpu().numpy().reshape(4, 4), dict(fitness=r.fitness, inlier_rmse=r.inlier_rmse, n_corr=r.n_corr, iterations=r.iterations)
+    return Tout.cpu().numpy().reshape(4, 4), as_dict(read_struct(res, _ext.IcpResult))
 
 
 def kabsch_dev(P, Q, w=None):

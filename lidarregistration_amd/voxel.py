@@ -6,7 +6,7 @@ is computed by a hash-grid HIP kernel (csrc/lr_voxel.hip).  No CPU fallback.
 """
 import torch
 
-from . import _ext
+from . import _ext, devmem
 from .matching import _device, _stream
 
 VOXEL_SIZE = 0.3            # Experiments/dataloader/generic_balanced_loader.py voxel_size of the balanced loaders (config.voxel_size)
@@ -19,7 +19,7 @@ def sparse_quantize(coordinates, return_index=True):
     c = torch.as_tensor(coordinates).to(device=dev, dtype=torch.float64).contiguous()
     n = int(c.shape[0])
     L = _ext.lib()
-    scratch = torch.empty(int(L.lr_voxel_dedup_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    scratch = devmem.scratch(L.lr_voxel_dedup_scratch_bytes(n), dev)
     sel = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
     cells = torch.empty((max(n, 1), 3), dtype=torch.int32, device=dev)
     cnt = torch.zeros(1, dtype=torch.int32, device=dev)

@@ -194,3 +194,23 @@ def test_cell_table_scratch_sizes_unchanged(libpath, fn):
     assert tuple(call(n) for n in CELLS_N) == CELLS_BYTES[fn]
     if fn != "lr_voxel_dedup_scratch_bytes":
         assert call(4194305) == 0                       # one point more than a cloud may have: refused
+
+
+# lr_nn3_scratch_bytes(n, n), lr_refine_z_scratch_bytes(n, n), lr_bbrf_scratch_bytes(n, n, 100), lr_normals_scratch_bytes(n) and
+# lr_balanced_select_scratch_bytes(n) around the block size, the run length, past 65 536 points and at the largest cloud, as the library
+# returned them BEFORE the cloud-level entry points got one scratch front end (csrc/lr_scratch.h): constants read from that build, so
+# that the one align helper cannot shift an arena
+CLOUD_N = (0, 1, 255, 256, 257, 4097, 30000, 65537, 4194304)
+CLOUD_BYTES = {"lr_nn3_scratch_bytes": (17920, 17920, 25344, 25344, 26112, 198400, 1441280, 3148544, 201392896),
+               "lr_refine_z_scratch_bytes": (27392, 27392, 45056, 45056, 46848, 388096, 2770432, 6042624, 386016256),
+               "lr_bbrf_scratch_bytes": (38144, 38144, 66304, 66304, 68864, 628736, 4566016, 9973504, 637930240),
+               "lr_normals_scratch_bytes": (17920, 17920, 25344, 25344, 26112, 198400, 1441280, 3148544, 201392896),
+               "lr_balanced_select_scratch_bytes": (33792, 35328, 46080, 46080, 47616, 231936, 1474560, 3181056, 201360384)}
+CLOUD_ARGS = {"lr_nn3_scratch_bytes": lambda n: (n, n), "lr_refine_z_scratch_bytes": lambda n: (n, n), "lr_bbrf_scratch_bytes": lambda n: (n, n, 100)}
+
+
+@pytest.mark.parametrize("fn", sorted(CLOUD_BYTES))
+def test_cloud_level_scratch_sizes_unchanged(libpath, fn):
+    f, args = getattr(_ext.lib(), fn), CLOUD_ARGS.get(fn, lambda n: (n,))
+    assert tuple(f(*args(n)) for n in CLOUD_N) == CLOUD_BYTES[fn]
+    assert f(*args(4194305)) == 0                       # one point more than a cloud may have: refused

@@ -26,7 +26,7 @@ import torch
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
-from lidarregistration_amd import _ext, balanced  # noqa: E402
+from lidarregistration_amd import _ext, balanced, devmem  # noqa: E402
 from tests import balanced_cases, balanced_cpu  # noqa: E402
 
 SEED = 51
@@ -71,7 +71,7 @@ def timed_call(fields, session, n_cands, n_request, attempts, reps, dev, per_rou
         e1.record(); e1.synchronize()
         if k:
             times.append(e0.elapsed_time(e1))
-    st.update(balanced._result(st))
+    st.update(devmem.as_dict(devmem.read_struct(st["res"], _ext.SelectResult)))
     rounds_enqueued = max_rounds or min(attempts, n_request + (attempts + per_round - 1) // per_round)
     return float(np.median(times)), float(min(times)), st, 3 + 2 * rounds_enqueued
 

@@ -28,7 +28,7 @@ import torch
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
-from lidarregistration_amd import _ext, overlap, synth  # noqa: E402
+from lidarregistration_amd import _ext, devmem, overlap, synth  # noqa: E402
 
 VOXEL, OFF_DEG, OFF_M = 0.3, 0.8, 0.05
 GROUPS = (("search", ("nn_",)), ("transform", ("bb_xform", "bb_init")), ("pair", ("bb_pair",)), ("step", ("bb_step",)))
@@ -60,7 +60,7 @@ def make_call(a, na, b, nb, dev):
     p = _ext.BbrfParams()
     res = torch.zeros(ctypes.sizeof(_ext.BbrfResult), dtype=torch.uint8, device=dev)
     log = torch.zeros((p.n_iter, 8), dtype=torch.float64, device=dev)
-    sc = torch.empty(L.lr_bbrf_scratch_bytes(n0, n1, p.n_iter), dtype=torch.uint8, device=dev)
+    sc = devmem.scratch(L.lr_bbrf_scratch_bytes(n0, n1, p.n_iter), dev)
     st = torch.cuda.current_stream().cuda_stream
 
     def call():
@@ -127,7 +127,7 @@ def run(n, reps, dev, threads, trace):
     a, na, b, nb = clouds(n, dev)
     call, res, log = make_call(a, na, b, nb, dev)
     med, mn = timed(call, reps)
-    r = _ext.BbrfResult.from_buffer_copy(res.cpu().numpy().tobytes())
+    r = devmem.read_struct(res, _ext.BbrfResult)
     host_s = host_iteration(a.cpu().numpy(), na.cpu().numpy(), b.cpu().numpy(), nb.cpu().numpy(), threads)
     row = dict(n=n, n0=int(a.shape[0]), n1=int(b.shape[0]), bbrf_ms=med, bbrf_ms_min=mn, iters_run=r.iters_run, status=r.status, best_iter=r.best_iter,
                best_loss=r.best_loss, n_pairs_best=r.n_pairs_best, launches=7 + 15 * r.iters_run, host_iteration_ms=host_s * 1e3)

@@ -20,7 +20,7 @@ import torch
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
-from lidarregistration_amd import _ext, synth  # noqa: E402
+from lidarregistration_amd import _ext, devmem, synth  # noqa: E402
 
 
 def host_downsample(X, voxel):
@@ -62,15 +62,15 @@ def run(n, voxel, batch, reps, dev):
     ns = (ctypes.c_int32 * batch)(*[n] * batch)
     p = _ext.OverlapParams(voxel_size=voxel)
     res = torch.zeros((batch, ctypes.sizeof(_ext.OverlapResult)), dtype=torch.uint8, device=dev)
-    scratch = torch.empty(L.lr_overlap_scratch_bytes(n, n) * batch, dtype=torch.uint8, device=dev)
+    scratch = devmem.scratch(L.lr_overlap_scratch_bytes(n, n) * batch, dev)
     st = torch.cuda.current_stream().cuda_stream
 
     def call():
         _ext.check(L.lr_overlap_batch(batch, xyz0, ns, xyz1, ns, Ts, ctypes.byref(p), res.data_ptr(), scratch.data_ptr(), scratch.numel(), st))
     med, mn = timed(call, reps)
-    out = [_ext.OverlapResult.from_buffer_copy(res[k].cpu().numpy().tobytes()) for k in range(batch)]
+    out = [devmem.read_struct(res, _ext.OverlapResult, k) for k in range(batch)]
     cent = torch.empty((n, 3), dtype=torch.float64, device=dev); info = torch.zeros(4, dtype=torch.int32, device=dev)
-    vs = torch.empty(L.lr_voxel_mean_scratch_bytes(n), dtype=torch.uint8, device=dev)
+    vs = devmem.scratch(L.lr_voxel_mean_scratch_bytes(n), dev)
 
     def down():
         _ext.check(L.lr_voxel_mean(Ad.data_ptr(), n, None, voxel, cent.data_ptr(), None, None, None, info.data_ptr(), vs.data_ptr(), vs.numel(), st))

@@ -21,7 +21,7 @@ import torch
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, ROOT)
-from lidarregistration_amd import _ext, overlap, synth  # noqa: E402
+from lidarregistration_amd import _ext, devmem, overlap, synth  # noqa: E402
 
 VOXEL, Z_OFF = 0.3, 0.37
 
@@ -71,7 +71,7 @@ def run(n, reps, dev, threads):
     st = torch.cuda.current_stream().cuda_stream
     idx = torch.empty(n0, dtype=torch.int32, device=dev); dist = torch.empty(n0, dtype=torch.float64, device=dev)
     info = torch.zeros(4, dtype=torch.int32, device=dev)
-    ns = torch.empty(L.lr_nn3_scratch_bytes(n0, n1), dtype=torch.uint8, device=dev)
+    ns = devmem.scratch(L.lr_nn3_scratch_bytes(n0, n1), dev)
     pn = _ext.Nn3Params()
 
     def nn():
@@ -79,13 +79,13 @@ def run(n, reps, dev, threads):
     nn_med, nn_min = timed(nn, reps)
     far = int(info.cpu()[3])
     res = torch.zeros(ctypes.sizeof(_ext.RefineZResult), dtype=torch.uint8, device=dev)
-    zs = torch.empty(L.lr_refine_z_scratch_bytes(n0, n1), dtype=torch.uint8, device=dev)
+    zs = devmem.scratch(L.lr_refine_z_scratch_bytes(n0, n1), dev)
     pz = _ext.RefineZParams(xy_gate=VOXEL)
 
     def rz():
         _ext.check(L.lr_refine_z(a.data_ptr(), n0, b.data_ptr(), n1, Td.data_ptr(), ctypes.byref(pz), res.data_ptr(), zs.data_ptr(), zs.numel(), st))
     rz_med, rz_min = timed(rz, reps)
-    r = _ext.RefineZResult.from_buffer_copy(res.cpu().numpy().tobytes())
+    r = devmem.read_struct(res, _ext.RefineZResult)
     t0 = time.perf_counter()
     host_dz, host_nn = host_refine(a.cpu().numpy(), b.cpu().numpy(), raw, VOXEL, threads)
     host_ms = (time.perf_counter() - t0) * 1e3

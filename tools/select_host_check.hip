@@ -108,6 +108,8 @@ int main()
     { call_args a; a.bytes = lr_balanced_select_scratch_bytes(a.n) - 1; REFUSED(a, "scratch too small"); }
     { call_args a; a.scratch = (void *)(uintptr_t)264; REFUSED(a, "aligned"); }
     { call_args a; a.n_draws = 1ll << 30; REFUSED(a, "rounds"); }
+    // the rounds are checked before the scratch: too many rounds and a short scratch report the rounds
+    { call_args a; a.n_draws = 1ll << 30; a.bytes = lr_balanced_select_scratch_bytes(a.n) - 1; REFUSED(a, "rounds"); }
     // what passes every check reaches the device check, once, and launches nothing: real host buffers, exactly sized
     {
         call_args a;
