@@ -9,6 +9,9 @@ A case is a dict: name, a / b ([M,3] float32: src / tgt of the M correspondences
     planted  hand-made structure (see each builder)
 unique_fit: the selected points determine the rotation.  golden: the reference's SM() is recorded for it (finite input, M <= 3000,
 unique_fit: the hand-made collinear sets leave ties and the rotation to torch's argsort and SVD).
+
+large_cases() (tests/test_sm_large_cpu.py, tests/test_gpu_sm_large.py, tests/golden/make_golden_sm_large.py) continues the list above
+one selection pass and up to M = 32 768; cases() itself and g16_sm.npz stay as they were.
 """
 import functools
 import hashlib
@@ -100,8 +103,53 @@ def cases():
     return tuple(out)
 
 
+def plant_pair(b, p, q):
+    """Makes (p, q), p < q, of line() compatible with d = 0 exactly by moving b_q: b_q - b_p = a_q - a_p."""
+    b[q, 0] = b[p, 0] + 10.0 * (q - p)
+
+
+def _planted(name, M, pairs, ratio):
+    """line(M) with the disjoint partner pairs planted: 2 len(pairs) equal non-zero v (sm_cpu.planted_v), everything else exactly 0;
+    expect_sel: the first K planted indices (K <= their number), else the lowest K indices."""
+    a, b = line(M)
+    for p, q in pairs:
+        plant_pair(b, p, q)
+    idx = sorted(i for pq in pairs for i in pq)
+    assert len(set(idx)) == len(idx), "the planted pairs must be disjoint"
+    K = int(M * ratio)
+    sel = tuple(idx[:K]) if pairs else tuple(range(K))
+    assert len(sel) == K
+    return _case(name, "planted", a, b, ratio, golden=False, unique_fit=False, pairs=tuple(pairs), expect_sel=sel, K=K)
+
+
+# the seed of each golden-backed case: the first from 6000 + M on that met the conditions tests/golden/make_golden_sm_large.py asserts
+LARGE_SEEDS = {"gap_8193_409": 14193, "full_20001": 26001, "full_32768": 38768}
+
+
+@functools.lru_cache(maxsize=None)
+def large_cases():
+    """Above one 1 024-entry selection pass and up to the accepted maximum (M = 32 768).  The planted ones have an analytic reference
+    (sm_cpu.planted_v); the random ones (`large`: True) are too large to restate in a test: tests/golden/g23_sm_large.npz holds their
+    fp64 eigenvector (tests/golden/make_golden_sm_large.py)."""
+    out = []
+    # 620 equal values; K = 310 falls inside the second selection pass, K = 465 (odd: it separates a pair) inside the third
+    ties = [(p, p + 1) for p in range(0, 3100, 10)]
+    out.append(_planted("planted_ties_3100_k310", 3100, ties, 0.1))
+    out.append(_planted("planted_ties_3100_k465", 3100, ties, 0.15))
+    # nothing compatible over three passes: the lowest 1 500 indices
+    out.append(_planted("planted_zeros_2500", 2500, [], 0.6))
+    # M = 3 mod 4 at the limit: the only partner of row 0 is the last row, that of row 32 765 is row 1; K = half of the planted entries
+    far = [(0, 32766), (1, 32765)] + [(p, p + 1) for p in range(1000, 32767, 1000)]
+    out.append(_planted("planted_limit_32767", 32767, far, (len(far) + 0.5) / 32767))
+    for name, M, n_inl in (("gap_8193_409", 8193, 409), ("full_20001", 20001, 6000), ("full_32768", 32768, 9830)):
+        a, b, _, _ = synth(M, n_inl, LARGE_SEEDS[name])
+        out.append(_case(name, "gap" if name.startswith("gap") else "cluster", a, b, 0.05, golden=False, large=True))
+    return tuple(out)
+
+
 def by_name(name):
-    return next(c for c in cases() if c["name"] == name)
+    hit = [c for c in cases() if c["name"] == name]
+    return hit[0] if hit else next(c for c in large_cases() if c["name"] == name)
 
 
 def checksum(c):

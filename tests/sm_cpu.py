@@ -84,6 +84,55 @@ def sm(a, b, thr=0.6, ratio=0.05, iterations=10, dtype=np.float64, m=None):
     return dict(v=v, K=K, sel=sel, labels=labels, w_sum=float(w.sum()), status=status, T=T)
 
 
+def planted_v(M, pairs, iterations=10):
+    """The eigenvector of sm_cases.line(M) with disjoint planted partner pairs, in closed form: every planted entry has exactly one
+    partner with c = 4.5 and every other c is 0, so the 2 len(pairs) non-zero entries stay equal to one scalar s: s0 = 1, u = 4.5 s,
+    s <- u / (u sqrt(n) + 1e-6), `iterations` times.  fp64 [M]."""
+    idx = np.array([i for pq in pairs for i in pq], np.int64)
+    v = np.zeros(M, np.float64)
+    if len(idx):
+        s = 1.0
+        for _ in range(iterations):
+            u = 4.5 * s
+            s = u / (u * np.sqrt(float(len(idx))) + 1e-6)
+        v[idx] = s
+    return v
+
+
+def planted_distances(a, b, q):
+    """d(q, j) = |a_q - a_j| - |b_q - b_j| for every j of an integer-valued set on the x axis, in exact integer arithmetic: int64 [M]."""
+    assert not a[:, 1:].any() and not b[:, 1:].any()
+    ax, bx = a[:, 0].astype(np.int64), b[:, 0].astype(np.int64)
+    assert np.array_equal(ax, a[:, 0]) and np.array_equal(bx, b[:, 0])
+    return np.abs(ax[q] - ax) - np.abs(bx[q] - bx)
+
+
+def plan(m, cus=256):
+    """The matvec's work plan restated from sm_make_plan (csrc/lr_sm.hip): (row blocks of 64, column chunks, columns per chunk) for a
+    live count m on a device of `cus` compute units."""
+    target = min(max(8 * cus, 64), 4096)
+    rb = (m + 63) >> 6 if m > 0 else 1
+    ch = max(1, min(target // rb, rb, 64))
+    m4 = (m + 3) & ~3 if m > 0 else 4
+    per = (((m4 + ch - 1) // ch) + 3) & ~3
+    return rb, (m4 + per - 1) // per, per
+
+
+def power_chunked32(C, per, iterations=10, slab=2048):
+    """The power iteration on an fp32 C with the contract's order of summation: a row's sum runs in fp32 IN SEQUENCE over each chunk
+    of `per` columns (np.cumsum: one running fp32 sum), the chunks of a row, the norm and the division in fp64, v rounded to fp32 once
+    per iteration.  What the device's order of summation alone costs against numpy's blocked fp32 matvec."""
+    M = len(C)
+    v = np.ones(M, np.float32)
+    for _ in range(iterations):
+        s = np.zeros(M, np.float64)
+        for i0 in range(0, M, slab):
+            for j0 in range(0, M, per):
+                s[i0:i0 + slab] += np.cumsum(C[i0:i0 + slab, j0:j0 + per] * v[j0:j0 + per], axis=1, dtype=np.float32)[:, -1].astype(np.float64)
+        v = (s / (np.sqrt((s * s).sum()) + 1e-6)).astype(np.float32)
+    return v
+
+
 @functools.lru_cache(maxsize=None)
 def reference(name, dtype_name="float64"):
     """sm() of a case of tests/sm_cases.py, computed once per process and shared (read-only)."""
