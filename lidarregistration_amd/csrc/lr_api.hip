@@ -680,7 +680,7 @@ static int register_stages(const lr_call &c, const float *xyz0, const float *xyz
 {
     lr_workspace *ws = c.ws;
     int32_t *m_dev = ws->counters + LR_CNT_NCORR;
-    int32_t *n_refit = ws->counters + LR_CNT_COUNT - 2;
+    int32_t *n_refit = ws->counters + LR_CNT_NREFIT;
     pad_if_narrow(c, F0, n0, F1, n1, dim);
     // 1. coarse correspondences (FR.py:38): first + second NN of every cloud-0 descriptor
     LR_TRY(lr_nn16_prep(c, F0, n0, F1, n1, true));         // (the prep kernel clears the counter block itself)

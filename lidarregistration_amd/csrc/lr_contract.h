@@ -22,7 +22,7 @@
  *   - the fp64 residual of refit_moments_kernel / ICP (no fma, fp64 threshold): a different contract from the fp32 scoring below.
  *   - the pruning radii eps of ransac_order_kernel (fp32) and of the LO near list (fp64): bounds on where inliers can lie, not
  *     results; the oracle scores everything and has neither.
- *   - the packed two-correspondence form of the scoring residual (lr_ransac.hip, lr_d2x2): ext_vector arithmetic has no C99
+ *   - the packed two-correspondence form of the scoring residual (lr_ransac_dev.h, lr_d2x2): ext_vector arithmetic has no C99
  *     spelling; it applies lr_score_d2's fma order to each half.
  */
 #ifndef LR_CONTRACT_H

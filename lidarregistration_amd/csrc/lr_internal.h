@@ -191,7 +191,7 @@ struct lr_workspace {
     double *refit_part;          // [blocks][16] moment partials
     int32_t *lo_list;            // [max_n0] inlier list of the model under local optimisation
     void *lo_ctl;                // lr_lo_ctl (LR_LO_CTL_BYTES): jobs the master block of a local optimisation publishes for its helper blocks
-    // pilot-ordered scoring (lr_ransac.hip, "score"): head / order passes -> main pass
+    // pilot-ordered scoring (lr_score.hip): head / order passes -> main pass
     void *sc_info;               // lr_score_info (LR_SC_INFO_BYTES)
     float *corr8s;               // the records behind the head, sorted by their residual under the pilot model (layout of corr8)
     int32_t *sc_perm;            // [max_iters] model slots by descending reach
@@ -235,6 +235,7 @@ enum {
     LR_CNT_NVALID2,      // SPRT pre-verification: models that survived it (dense second list, scored in full)
     LR_CNT_FORM_MISS_F,  // single-pair calls launch only the form of the filter pass the last call's norms asked for: set when THIS call's norms
     LR_CNT_FORM_MISS_R,  //   ask for the other one (forward / reverse launch) -- the exact kernel then re-does every row by the full scan
+    LR_CNT_NREFIT = 14,  // inliers of the pair pipeline's refit (lr_pair_result.n_refit)
     LR_CNT_COUNT = 16,
     LR_CNT_TOTAL = 64        // counters[16..63] hold lr_ransac_state
 };
@@ -301,9 +302,20 @@ int lr_icp_run(const lr_call &c, const float *xyz0, int n0, const float *xyz1, i
                const lr_ransac_result *gate, double max_dist, int max_iter, double rel_fit, double rel_rmse,
                double *T_out, lr_icp_result *res);
 
-// lr_ransac.hip
+// lr_ransac.hip: a whole RANSAC call (hypotheses, scoring, merge, local optimisation) -> T_out / res
 int lr_ransac_run(const lr_call &c, const float *corr8, int m_max, const int32_t *m_dev, const lr_ransac_params *p,
                   double *T_out, lr_ransac_result *res);
+// The stage launchers below are called from lr_ransac_run with resolved parameters: they refuse nothing, and the call checks for a launch
+// error once, at its end.
+// lr_score.hip: scores the model list `models` (live length counters[vslot]) of a batch of h_count hypothesis ids
+void lr_score_run(const lr_call &c, const float *corr8, int m_max, const int32_t *m_dev, float thr2, const float *models, int h_count, int vslot);
+// lr_lo.hip: local optimisation behind the batch that ended with id h_end (mode 0), final iterated least squares (mode 1); blocks per pair
+// of a mode-0 launch (more than 1: helper blocks run, and ransac_final_kernel has to zero their job slots)
+void lr_lo_run(const lr_call &c, const float *corr8, int m_max, const int32_t *m_dev, const lr_ransac_params &p, int h_end, int mode,
+               double *T_out, lr_ransac_result *res);
+int lr_lo_groups(const lr_call &c, const lr_ransac_params &p, int m_max);
+
+// lr_refit.hip
 int lr_inlier_mask_run(const float *src, const float *tgt, const int32_t *i0, const int32_t *i1, int m_max, const int32_t *m_dev,
                        const double *T, float thr2, uint8_t *mask, int32_t *n_inliers, hipStream_t st);
 int lr_refit_run(const lr_call &c, const float *xyz0, int n0, const float *xyz1, const int32_t *idx1,

@@ -12,7 +12,7 @@
 //                      (fmaxf(0, NaN) = 0: compatibility 0 with everything); the list is padded to a multiple of 4 with such records
 //   sm_matvec_kernel   the hot path: work item = 64 rows (one per lane, the row's six coordinates in registers) x one chunk of columns;
 //                      the column records are wave-uniform and arrive by scalar loads, four per wait, ping-pong as in the scoring loop
-//                      of lr_ransac.hip; partial sums go to part[chunk][row] by plain stores
+//                      of lr_score.hip; partial sums go to part[chunk][row] by plain stores
 //   sm_norm_kernel     one block per pair: row sums over the chunks (ascending, fp64), the norm by a fixed-order tree, v back into the
 //                      records
 //   sm_select_kernel   one block per pair: the K-th largest v by four radix passes over the float bits (v >= 0: integer order is float

@@ -2,7 +2,7 @@
 
 ``GC_RANSAC`` keeps the reference's call shape (Experiments/algorithms/GC_RANSAC.py:8-55);
 ``RANSAC_registration`` keeps FR.py:122-139's.  Both run the same HIP kernels (hypothesis
-generation, lane-per-hypothesis scoring, Kabsch) -- see csrc/lr_ransac.hip.
+generation, lane-per-hypothesis scoring, Kabsch) -- see csrc/lr_ransac.hip, lr_score.hip, lr_lo.hip and lr_refit.hip.
 """
 import ctypes
 from time import time

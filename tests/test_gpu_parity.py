@@ -324,7 +324,7 @@ def test_ransac_odd_counts_with_few_hypotheses(lr, oracle, n, iters):
 @pytest.mark.parametrize("case", ["far_from_origin", "few_good_models", "nonfinite", "msac_4pt", "noise_free_ties", "just_above_limits",
                                   "odd_tail", "huge_noise", "two_motions"])
 def test_ransac_pilot_ordered_scoring_is_exact(lr, oracle, case):
-    """The scoring passes skip records a model cannot reach (csrc/lr_ransac.hip, "score": pilot model, residual buckets, reach of
+    """The scoring passes skip records a model cannot reach (csrc/lr_score.hip: pilot model, residual buckets, reach of
     every model); the oracle scores every model over every correspondence.  Winner id, inlier count, error sum and model must agree
     where the pruning bound is under stress: coordinates of 1e4 m (fp32 rounding against the slack), a pilot that is a bad model,
     non-finite coordinates, MSAC, ties decided by the error sum, sizes at the switch-on limits, an odd sorted list, inlier noise of

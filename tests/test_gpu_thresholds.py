@@ -1,5 +1,5 @@
 """lr_ransac across its whole threshold range: bit-exact against the oracle, and within the fp32 band of independent fp64 scoring
-(tests/ransac_hp.py).  Several kernel branches are chosen by the threshold (csrc/lr_ransac.hip); every row restates the predicate
+(tests/ransac_hp.py).  Several kernel branches are chosen by the threshold (csrc/lr_ransac.hip, lr_score.hip, lr_lo.hip); every row restates the predicate
 that picks its branch and asserts it, so the row is known to reach that branch.  Needs an MI355X."""
 import numpy as np
 import pytest
@@ -25,18 +25,18 @@ def lr():
     return ns
 
 
-# ----------------------------------------------------------------------------- the threshold predicates of lr_ransac.hip
+# ----------------------------------------------------------------------------- the threshold predicates of lr_ransac.hip, lr_score.hip and lr_lo.hip
 
 def f32_thr2(thr):
     return float(np.float32(float(thr) * float(thr)))           # what ransac_params / oracle._params store
 
 
 def eff_thr2(thr2, scoring):
-    return float(np.float32(np.float32(thr2) * np.float32(2.25))) if scoring == 2 else thr2       # eff_params / lr_ransac_run
+    return float(np.float32(np.float32(thr2) * np.float32(2.25))) if scoring == 2 else thr2       # eff_params / ransac_resolve
 
 
 def sub_len(thr2):
-    """lr_ransac_run: sub-block length of the 32-bit error sums of lr_score_stream."""
+    """lr_score_run: sub-block length of the 32-bit error sums of lr_score_stream."""
     sub = int(4095.0 / (thr2 * 1.0000001 + 1e-6))
     sub = min(sub, 4096) & ~1
     return max(sub, 2)

@@ -1,5 +1,5 @@
-"""One call of every entry point of liblidarreg.so that launches kernels, at dim 32 and dim 3: the workload behind
-profiles/host_context_trace.txt and profiles/prims_trace.txt.  Run it under `rocprofv3 --kernel-trace -- python tools/entry_point_trace.py`, once per library
+"""One call of every entry point of liblidarreg.so that launches kernels, at dim 32 and dim 3, and every branch of the RANSAC launch plan: the
+workload behind profiles/host_context_trace.txt, profiles/prims_trace.txt and profiles/ransac_split_trace.txt.  Run it under `rocprofv3 --kernel-trace -- python tools/entry_point_trace.py`, once per library
 (LIDARREG_LIB names an alternate build), and compare the two kernel traces with tools/trace_compare.py."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -45,5 +45,15 @@ src, tgt = A[o0.long()].contiguous(), B[o1.long()].contiguous()
 sets = [len(src), 300, 65]
 sm.sm_batch_dev([src[:m] for m in sets], [tgt[:m] for m in sets])
 teaser.teaser_batch_dev([src[:m] for m in sets], [tgt[:m] for m in sets])
+torch.cuda.synchronize()
+# the branches of the RANSAC launch plan (lr_ransac_run) the calls above do not reach
+gc = dict(mode="MNN", codebase="GC", prosac=True, iters=4096)      # GC defaults: exit rule (batches of 1 024, then 3 072 ids), PROSAC, ELC, LO + polish
+ws5 = _ext.Workspace(3000, 2500, 32, 4096, max_pairs=5)
+FR.register_batch_dev(dev + dev[:2], FR.pair_params(Args(**gc)), ws=ws5)      # more than four pairs, a batch of >= 2 048 ids: the pilot-ordered passes
+FR.register_batch_dev(dev, FR.pair_params(Args(**gc)), ws=ws5)                # three pairs: eight helper groups per pair in the local optimisation
+for kw in (dict(fast_rejection="SPRT"), dict(fast_rejection="NONE"), dict(GC_LO=False)):      # second model list; no pre-check; polish only
+    FR.read_result(FR.register_pair_dev(A, B, FA, FB, FR.pair_params(Args(**gc, **kw))))
+FR.read_result(FR.register_pair_dev(A, B, FA, FB, FR.pair_params(Args(mode="MNN", codebase="open3D", iters=2048, ransac_n=4, o3d_conf=1.0))))
+ransac.ransac_dev(A[o0.long()], B[o1.long()], 2048, confidence=0.99, batch=512)      # the caller's batch length
 torch.cuda.synchronize()
 print("entry_point_trace: done")

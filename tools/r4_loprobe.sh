@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; C=$R/lidarregistration_amd/csrc
 if [ "$1" != "run" ]; then
   mkdir -p $R/tools/bin; make -C $C -s -j4 liblidarreg.so
-  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form=1 --offload-arch=gfx950 -fvisibility=hidden -DLR_LO_PROBE -c $C/lr_ransac.hip -o /tmp/lr_ransac_probe.o &&
+  /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize -mllvm -amdgpu-mfma-vgpr-form=1 --offload-arch=gfx950 -fvisibility=hidden -DLR_LO_PROBE -c $C/lr_lo.hip -o /tmp/lr_ransac_probe.o &&
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/tools/bin/liblidarreg_probe.so $C/lr_api.o $C/lr_nn16.o $C/lr_filter.o /tmp/lr_ransac_probe.o $C/lr_icp.o $C/lr_voxel.o && echo built
   exit
 fi
