@@ -266,7 +266,7 @@ extern "C" int lr_workspace_option(lr_workspace *ws, int option, int value)
     case LR_OPT_NN_BLOCKS: ws->nn_blocks_target = value > 0 ? value : 3 * ws->n_cus; break;
     case LR_OPT_NN_BLOCKS_BATCH: ws->nn_blocks_batch = value > 0 ? value : 12 * ws->n_cus; break;
     case LR_OPT_NN_SAMPLE_STRIDE: ws->nn_sample_stride = value > 4096 ? 4096 : value; break;      // (lr_nn16_run clamps it to the strip length)
-    case LR_OPT_REV_STRIPS: ws->rev_strips = value > 64 ? 64 : value; break;
+    case LR_OPT_REV_STRIPS: ws->rev_strips = value > LR_REV_MAX_STRIPS ? LR_REV_MAX_STRIPS : value; break;
     case LR_OPT_NN_SECOND_AUTO: ws->nn_second_auto = value ? 1 : 0; break;
     case LR_OPT_CLOCK_PROBE: ws->clock_probe = value ? 1 : 0; break;
     default: lr_set_error("lr_workspace_option: unknown option %d", option); return LR_EINVAL;

@@ -24,14 +24,16 @@ void lr_set_error(const char *fmt, ...);
     } while (0)
 
 // Candidate store of the f16 filter: every wave of a pass-B block (64 query rows x one column strip) owns a private segment
-// of { column | lane group, row mask | filter value } entries (lr_nn16.hip, LR_PB_*); the segments of one wave's rows over all strips hold at most
+// of { column | lane group, row mask | filter value } entries (lr_nn16_dev.h, LR_PB_*); the segments of one wave's rows over all strips hold at most
 // LR_NN16_SEG entries (8 bytes each).  Columns must be < 2^22.
 #define LR_NN16_SEG 4096
+#define LR_REV_MAX_STRIPS 64     // most column strips a filter pass runs with: the reverse pass under LR_OPT_REV_STRIPS (forward: LR_NN_MAX_STRIPS)
 #define LR_NN16_SEG_INTS(n) ((size_t)((n) / 256 + 1) * 4 * LR_NN16_SEG * 2)      // int32 words of the store for n query rows
-#define LR_NN16_CNT_INTS(n) ((size_t)((n) / 256 + 1) * 4 * 65)                   // segment counters (up to 64 strips) + strips used
-static inline int lr_cdiv(int a, int b) { return (a + b - 1) / b; }
+#define LR_NN16_CNT_INTS(n) ((size_t)((n) / 256 + 1) * 4 * (LR_REV_MAX_STRIPS + 1))      // segment counters (up to LR_REV_MAX_STRIPS strips) + strips used
+static constexpr int lr_cdiv(int a, int b) { return (a + b - 1) / b; }
 // entries per (row block, wave, strip) segment when a pass runs with `strips` column strips
-__host__ __device__ static inline int lr_seg_cap(int strips) { const int c = (LR_NN16_SEG / strips) & ~63; return c < 64 ? 64 : c; }
+__host__ __device__ static constexpr int lr_seg_cap(int strips) { const int c = (LR_NN16_SEG / strips) & ~63; return c < 64 ? 64 : c; }
+static_assert(lr_seg_cap(LR_REV_MAX_STRIPS) * LR_REV_MAX_STRIPS <= LR_NN16_SEG, "the segments of a wave's rows over all strips fit its share of the candidate store");
 
 #define LR_TRY_HIP(x) do { int rc__ = (x); if (rc__ != LR_OK) return rc__; } while (0)
 
@@ -275,7 +277,8 @@ int lr_check_memory_device(const void *mem, hipStream_t st, const char *who, int
 int lr_timer_mark(const lr_call &c, lr_event e);
 
 // lr_nn16.hip: norms + f16 operand copies of both clouds; forward (rows of cloud 0 against cloud 1: first NN, and the second when idx2
-// is given); reverse (rows of cloud 1 against cloud 0, first NN only; `seeded`: by the forward pass of the same call)
+// is given); lr_nn16_rev.hip: reverse (rows of cloud 1 against cloud 0, first NN only; `seeded`: by the forward pass of the same call).
+// Both directions go through lr_nn16_pass.hip (the filter pass) and lr_nn16_exact.hip (exact verification), see lr_nn16_dev.h
 int lr_nn16_prep(const lr_call &c, const float *F0, int n0, const float *F1, int n1, bool zero_counters = false);
 int lr_nn16_run(const lr_call &c, const float *F0, int n0, const float *F1, int n1,
                 int32_t *idx1, int32_t *idx2, float *s1, float *s2, bool seed_reverse = false);

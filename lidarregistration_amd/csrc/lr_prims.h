@@ -1,6 +1,6 @@
 // The integer building blocks the cloud-level kernels share (lr_filter.hip, lr_icp.hip, lr_voxel.hip, lr_overlap.hip, lr_sm.hip,
 // lr_teaser.hip; not part of the ABI): wave and block scans, flag counting and ordered compaction, the 64-bit mix hash.  Device only,
-// inlined, no state; a wave is 64 lanes.  lr_nn16.hip and the RANSAC files (lr_ransac.hip, lr_score.hip, lr_lo.hip) keep their own spellings: the helper re-schedules their kernels.
+// inlined, no state; a wave is 64 lanes.  The NN files (lr_nn16*.hip) and the RANSAC files (lr_ransac.hip, lr_score.hip, lr_lo.hip) keep their own spellings: the helper re-schedules their kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 

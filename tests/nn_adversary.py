@@ -1,4 +1,4 @@
-"""Adversarial inputs for the f16 filter pass of the NN kernel (csrc/lr_nn16.hip), and an fp64 model of what that pass sees.
+"""Adversarial inputs for the f16 filter pass of the NN kernel (csrc/lr_nn16_pass.hip; the error bound it is tested against: csrc/lr_nn16.hip), and an fp64 model of what that pass sees.
 
 The filter pass prunes columns on u' = n1_j - 2 dot16(i, j), a dot product of f16 copies accumulated in fp32, and keeps a column
 whenever it could still be within the row's need-th exact distance: the slack that makes this safe is E = 1.05e-3 (n0_i + max_j n1_j)

@@ -1,5 +1,5 @@
-"""One call of every entry point of liblidarreg.so that launches kernels, at dim 32 and dim 3, and every branch of the RANSAC launch plan: the
-workload behind profiles/host_context_trace.txt, profiles/prims_trace.txt and profiles/ransac_split_trace.txt.  Run it under `rocprofv3 --kernel-trace -- python tools/entry_point_trace.py`, once per library
+"""One call of every entry point of liblidarreg.so that launches kernels, at dim 32 and dim 3, and every branch of the RANSAC and NN launch plans: the
+workload behind profiles/host_context_trace.txt, profiles/prims_trace.txt, profiles/ransac_split_trace.txt and profiles/nn_split_trace.txt.  Run it under `rocprofv3 --kernel-trace -- python tools/entry_point_trace.py`, once per library
 (LIDARREG_LIB names an alternate build), and compare the two kernel traces with tools/trace_compare.py."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -56,4 +56,21 @@ for kw in (dict(fast_rejection="SPRT"), dict(fast_rejection="NONE"), dict(GC_LO=
 FR.read_result(FR.register_pair_dev(A, B, FA, FB, FR.pair_params(Args(mode="MNN", codebase="open3D", iters=2048, ransac_n=4, o3d_conf=1.0))))
 ransac.ransac_dev(A[o0.long()], B[o1.long()], 2048, confidence=0.99, batch=512)      # the caller's batch length
 torch.cuda.synchronize()
+# the branches of the NN launch plans (lr_nn16_plan_fwd / lr_nn16_plan_rev) and of the form hint the calls above do not reach
+big = synth.make_pair(N=3000, N1=8192, rho=0.5, s=0.9, seed=640)
+G0, G1 = t(big["feats0"]).cuda(), t(big["feats1"]).cuda()
+matching.nn_top2_dev(G0, G1, want_2nd=True)       # 256 column tiles: four forward strips on 256 CUs (the pairs above: one)
+matching.nn_top2_dev(G0, G1, want_2nd=False)
+for name, value in (("nn_sample_stride", 1), ("nn_sample_stride", 64), ("nn_blocks", 1), ("rev_strips", 1), ("rev_strips", 64)):
+    ws1 = matching.workspace(3000, 8192)
+    ws1.set_option(name, value)
+    j1, j2, _, _ = matching.nn_top2_dev(G0, G1)
+    matching.mutual_dev(G0, G1, j1, j2)            # a caller's list: the unseeded reverse pass
+    ws1.set_option(name, 0)
+# the form hint of single-pair calls: unknown and then one reading (both forms), two readings that agree (one form), a miss (the norms change)
+unit = [F / F.norm(dim=1, keepdim=True) for F in (FA, FB)]
+spread = [F * torch.linspace(0.5, 3.0, len(F), device=F.device)[:, None] for F in unit]
+for U0, U1 in [unit] * 3 + [spread] * 3:
+    matching.nn_top2_dev(U0, U1)
+    torch.cuda.synchronize()      # (the hint is what the previous call's range kernel left in host memory)
 print("entry_point_trace: done")

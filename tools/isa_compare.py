@@ -70,6 +70,9 @@ for f in fa:
         bad += not same
         nd = sum(x != y for x, y in zip(ta, tb)) + abs(len(ta) - len(tb))
         print(f"  {'identical' if same else 'differs  '}  {demangle(n)}  -> {g[:-2]}.hip  ({len(ta)} lines" + ("" if same else f", {nd} differ") + ")")
+        if not same and len(ta) == len(tb) and nd <= 8:      # a handful of lines: show them
+            for x, y in zip(ta, tb):
+                if x != y: print(f"      parent: {x.strip()}\n      branch: {y.strip()}")
         for side, r in (("parent", ra), ("branch", rb)):
             if not same or side == "branch":
                 print(f"      {side}: VGPRs {r.get('NumVgprs')} SGPRs {r.get('TotalNumSgprs')} LDS {r.get('LDSByteSize')} scratch {r.get('ScratchSize')} occupancy {r.get('Occupancy')}"

@@ -2,10 +2,18 @@
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form=1 [-DLR_PB_PROBE] tools/pb_micro.hip -o tools/bin/pb_micro
 //   (-DLR_PB_PROBE: hit statistics.  The round-5 ablation variants -- -DLR_PB_EXP=... -- are built from that round's source: tools/pb_variant.sh)
 //   usage: pb_micro [n=30000] [P=32] [strips=1]
-#ifndef PB_SRC
-#define PB_SRC "../lidarregistration_amd/csrc/lr_nn16.hip"
-#endif
+// It compiles what it launches: the prep and range kernels (lr_nn16.hip) and the filter pass (lr_nn16_pass.hip).  -DPB_SRC=... : one file
+// that holds all three, an old commit's lr_nn16.hip (tools/pb_variant.sh) or a patched copy.
+#include <stdlib.h>
+#ifdef PB_SRC
 #include PB_SRC
+#else
+#include "../lidarregistration_amd/csrc/lr_nn16.hip"
+#include "../lidarregistration_amd/csrc/lr_nn16_pass.hip"
+// (what the host functions of those two files call in the rest of the library; never called here)
+int lr_timer_mark(const lr_call &, lr_event) { return 0; }
+int lr_nn16_exact(const lr_call &, int, const float *, int, const float *, int, int, int, const float *, const int32_t *, const int32_t *, const lr_ex_out &) { return 0; }
+#endif
 #ifdef PB_OLD_ABI      // kernels of round 3: no pooled-threshold argument
 #define PB_YS
 #define PB_YS_ARG
