@@ -659,6 +659,67 @@ LR_API int lr_balanced_select(const double *fields, const int32_t *session, cons
                               const double *draws, long long n_draws, const lr_select_params *params, uint8_t *alive, int32_t *n_sel,
                               int32_t *out, lr_select_result *result, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- p1: PointDSC's SC-NonLocal correspondence encoder and confidence head over M correspondences src[i] <-> tgt[i] -------------
+ * Replaces NonLocalNet (Experiments/models/PointDSC.py:9-77), the spatial-consistency matrix it attends with (:150-153) and the
+ * classification head (:107-113, :171) in inference mode: a 128-d feature and an inlier logit per correspondence.  The M x M
+ * matrices (compatibility, logits, softmax weights) are never stored.  Seed picking, the neural spectral matching, the per-seed fits
+ * and post_refinement are not built.  Contract (restated in tests/pdsc_cpu.py):
+ *  E1 a correspondence with a non-finite coordinate is dead (deviation: the reference propagates NaN into every output): its key gets
+ *     weight 0 in every softmax, its feature is 0 and its confidence -inf, and it does not enter the mean of E2;
+ *  E2 corr_pos = [src, tgt] - column mean over the live rows (demo_registration.py:107-108): the sums in fp64 (thread t of 1024 adds
+ *     rows t, t + 1024, ... in ascending order, then the halving tree s[t] += s[t + h], h = 512 .. 1), mean = sum / count, the
+ *     subtraction in fp64, rounded to fp32 once;
+ *  E3 compat(i,j) = max(0, 1 - d^2 / sigma_d^2), d = |s_i - s_j| - |t_i - t_j|, in fp32 on the direct differences of the given
+ *     coordinates: (dx*dx + dy*dy) + dz*dz, correctly rounded sqrt, fmaxf(0, fmaf(d*d, (float)(-1 / sigma_d^2), 1));
+ *  E4 per layer, fp32: h = relu(bn(conv(feat))) (PointCN); q, k, v = conv(h); w = softmax_j(compat(i,j) * (q_i . k_j * (float)(1/sqrt(128))))
+ *     over the live j (all of them: a zero compatibility still weighs exp(0 - max)); message_i = sum_j w_ij v_j;
+ *     feat = h + fc_message(message) (128 -> 64 -> 64 -> 128, bn + relu after the first two).  BatchNorm is folded: every layer is
+ *     y = scale * (W x) + offset, the dot product an fmaf chain over ascending input channel;
+ *  E5 confidence = conv(relu(conv(relu(conv(feat))))), 128 -> 32 -> 32 -> 1;
+ *  E6 no floating-point atomics; a row's softmax runs over key tiles of 32 in ascending order inside each of up to 8 key chunks (their
+ *     number a function of the pair's live M alone), the chunks are merged in ascending order; the same input gives the same bits on every
+ *     run, whatever the scratch held, alone or as pair k of a batch.
+ * Parity with the reference is to a tolerance (torch's order of summation is unspecified): tests/test_gpu_pdsc.py.
+ *
+ * Weights: one flat fp32 device blob of lr_pdsc_weights_bytes(num_layers) bytes, 16-byte aligned, the caller's.  A block is { Wt[in][out] (the conv's
+ * weight transposed), scale[out], offset[out] }; the blob is: layer0 (in 8: the 6 inputs and two zero rows, out 128); then per layer
+ * PointCN (128, 128), q|k|v as one layer (128, 384; scale 1, offset = the biases), fc_message 0 (128, 64), 3 (64, 64), 6 (64, 128);
+ * then the head: (128, 32), (32, 32), (32, 1).  With a BatchNorm behind the conv, scale = gamma / sqrt(var + eps) and
+ * offset = (bias - mean) * scale + beta, folded in fp64 and rounded once; without, scale = 1 and offset = bias.                   */
+typedef struct lr_pdsc_params {
+    uint32_t struct_size;        /* = sizeof(lr_pdsc_params), checked like lr_ransac_params.struct_size                            */
+    int32_t  num_layers;         /* 12 (config.py:34); 1..16                                                                        */
+    double   sigma_d;            /* 1.2 for Lidar (the reference's sigma_spat); positive and finite                                 */
+} lr_pdsc_params;
+
+/* Written to device memory by lr_pdsc_encode / _batch (16 bytes). */
+typedef struct lr_pdsc_result {
+    int32_t  status;             /* 0 ok, 1 = no live correspondence                                                                */
+    int32_t  m;                  /* live correspondence count the call ran on (m_dev clamped to 0..m)                               */
+    int32_t  dead;               /* of those, correspondences with a non-finite coordinate                                          */
+    int32_t  reserved;           /* 0                                                                                               */
+} lr_pdsc_result;
+
+/* Bytes of the weight blob (0 when num_layers is outside 1..16). */
+LR_API size_t lr_pdsc_weights_bytes(int num_layers);
+/* Caller-owned device scratch per pair for up to max_m correspondences (0 when max_m is outside 0..32768); linear in max_m. */
+LR_API size_t lr_pdsc_scratch_bytes(int max_m);
+/* m_dev, if not NULL, is a device int32 holding the live M (clamped to 0..m).  feat_out (nullable, float32 [m,128]) receives the
+ * features, conf_out (nullable, float32 [m]) the logits; rows at and past the live count are written 0, dead rows 0 / -inf; with m = 0
+ * nothing is stored.  scratch: >= lr_pdsc_scratch_bytes(m) bytes, 256-byte aligned, memory of the current device (checked, like the
+ * stream: LR_EINVAL).  Every refusal (struct_size, num_layers / sigma_d out of range, a short or misaligned weight blob, short scratch, m > 32768) is
+ * LR_EINVAL, before any launch.  No host synchronisation, no allocation.                                                           */
+LR_API int lr_pdsc_encode(const float *src, const float *tgt, int m, const int32_t *m_dev, const float *weights, size_t weights_bytes,
+                          const lr_pdsc_params *p, lr_pdsc_result *result, float *feat_out, float *conf_out, void *scratch,
+                          size_t scratch_bytes, void *stream);
+/* npairs (1..64) independent pairs under one set of weights in one sequence of launches (the pair is a grid dimension);
+ * src/tgt/m/m_dev/feat_out/conf_out are HOST arrays of length npairs (m_dev, feat_out and conf_out, and their entries, may be NULL),
+ * carried by value into a setup kernel; results is a DEVICE array of npairs blocks; scratch >= npairs * lr_pdsc_scratch_bytes(max m).
+ * The result of pair k is bit-identical to lr_pdsc_encode on that pair.                                                            */
+LR_API int lr_pdsc_encode_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
+                                const float *weights, size_t weights_bytes, const lr_pdsc_params *p, lr_pdsc_result *results,
+                                float *const *feat_out, float *const *conf_out, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */
 LR_API int lr_workspace_timing(lr_workspace *ws, int enable);

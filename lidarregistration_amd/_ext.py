@@ -26,6 +26,7 @@ SYMBOLS = [
     "lr_nn3_scratch_bytes", "lr_nn3", "lr_refine_z_scratch_bytes", "lr_refine_z",
     "lr_bbrf_scratch_bytes", "lr_bbrf", "lr_normals_scratch_bytes", "lr_normals",
     "lr_balanced_select_scratch_bytes", "lr_balanced_select",
+    "lr_pdsc_weights_bytes", "lr_pdsc_scratch_bytes", "lr_pdsc_encode", "lr_pdsc_encode_batch",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -175,6 +176,17 @@ class SelectResult(ctypes.Structure):
                 ("hi", ctypes.c_double * 6)]
 
 
+class PdscParams(KeywordParams):
+    """lr_pdsc_params with the settings of the reference's CLI (config.py:34, sigma_spat for Lidar) as defaults; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_layers", ctypes.c_int32), ("sigma_d", ctypes.c_double)]
+    DEFAULTS = dict(num_layers=12, sigma_d=1.2)
+
+
+class PdscResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("m", ctypes.c_int32), ("dead", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(PdscParams) == 16 and ctypes.sizeof(PdscResult) == 16
 assert ctypes.sizeof(SelectParams) == 24 and ctypes.sizeof(SelectResult) == 136
 assert ctypes.sizeof(BbrfParams) == 56 and ctypes.sizeof(BbrfResult) == 280
 assert ctypes.sizeof(Nn3Params) == 16 and ctypes.sizeof(RefineZParams) == 32 and ctypes.sizeof(RefineZResult) == 40
@@ -271,6 +283,11 @@ def lib():
         L.lr_normals.argtypes = [vp, ci, dp, ci, vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_balanced_select_scratch_bytes.argtypes = [ci]
         L.lr_balanced_select.argtypes = [vp, vp, vp, ci, ci, vp, ctypes.c_longlong, ctypes.POINTER(SelectParams), vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.lr_pdsc_weights_bytes.restype = ctypes.c_size_t
+        L.lr_pdsc_weights_bytes.argtypes = [ci]
+        L.lr_pdsc_scratch_bytes.argtypes = [ci]
+        L.lr_pdsc_encode.argtypes = [vp, vp, ci, vp, vp, ctypes.c_size_t, ctypes.POINTER(PdscParams), vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.lr_pdsc_encode_batch.argtypes = [ci, pp, pp, ip, pp, vp, ctypes.c_size_t, ctypes.POINTER(PdscParams), vp, pp, pp, vp, ctypes.c_size_t, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

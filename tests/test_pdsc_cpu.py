@@ -1,0 +1,235 @@
+"""The yardsticks of the PointDSC encoder, without a GPU: the numpy restatement (tests/pdsc_cpu.py) against what the reference's own model
+returned (tests/golden/g24_pdsc.npz), rule E1 by hand, the state-dict packing, the refusals and the size functions of the C ABI."""
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+from lidarregistration_amd import _ext, pointdsc
+from tests import pdsc_cases, pdsc_cpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLD = np.load(os.path.join(ROOT, "tests", "golden", "g24_pdsc.npz"))
+IDS = [pdsc_cases.golden_name(m, L) for m, L in pdsc_cases.GOLDEN]
+
+
+def test_golden_covers_what_the_issue_names_and_stays_small():
+    assert {m for m, L in pdsc_cases.GOLDEN if L == 12} == {1, 2, 3, 31, 32, 33, 64, 65, 129, 257, 1000}
+    assert {(m, L) for m, L in pdsc_cases.GOLDEN if L != 12} == {(257, 1), (257, 2)}
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "g24_pdsc.npz")) < os.path.getsize(os.path.join(ROOT, "tests", "golden", "g12_full_30k.npz"))
+
+
+@pytest.mark.parametrize("m,num_layers", pdsc_cases.GOLDEN, ids=IDS)
+def test_golden_belongs_to_these_inputs(m, num_layers):
+    c = pdsc_cases.golden_case(m, num_layers)
+    assert str(GOLD[c["name"] + "/sha256"]) == pdsc_cases.checksum(c), "tests/pdsc_cases.py changed: regenerate with tests/golden/make_golden_pdsc.py"
+    assert GOLD[c["name"] + "/conf"].shape == (m,) and GOLD[c["name"] + "/feat"].shape == (len(pdsc_cases.feature_rows(m)), 128)
+
+
+@pytest.mark.parametrize("m,num_layers", pdsc_cases.GOLDEN, ids=IDS)
+def test_restatement_fp64_equals_the_reference_fp64(m, num_layers):
+    """Two fp64 evaluations of one formula in different order: 1e-9 abs (measured maximum: DESIGN.md §16.3)."""
+    name = pdsc_cases.golden_name(m, num_layers)
+    feat, conf = pdsc_cpu.golden_reference(m, num_layers)
+    df = np.abs(feat[pdsc_cases.feature_rows(m)] - GOLD[name + "/feat"]).max()
+    dc = np.abs(conf - GOLD[name + "/conf"]).max()
+    print(f"{name}: restatement fp64 vs reference fp64: features {df:.2e}, confidence {dc:.2e}")
+    assert df <= 1e-9 and dc <= 1e-9
+
+
+@pytest.mark.parametrize("m,num_layers", pdsc_cases.GOLDEN, ids=IDS)
+def test_restatement_fp32_is_a_valid_yardstick(m, num_layers):
+    """The restatement run in fp32 deviates from fp64 by at most 2 x what the reference's own fp32 run does: that makes it a valid
+    yardstick where no recording exists."""
+    name = pdsc_cases.golden_name(m, num_layers)
+    f64, c64 = pdsc_cpu.golden_reference(m, num_layers)
+    f32, c32 = pdsc_cpu.golden_reference(m, num_layers, "float32")
+    df, dc = np.abs(f32 - f64).max(), np.abs(c32 - c64).max()
+    rf, rc = float(GOLD[name + "/dev_feat"]), float(GOLD[name + "/dev_conf"])
+    print(f"{name}: fp32-vs-fp64 restatement / reference: features {df:.2e} / {rf:.2e}, confidence {dc:.2e} / {rc:.2e}")
+    assert df <= 2.0 * rf and dc <= 2.0 * rc
+
+
+def test_dead_rows_by_hand():
+    """E1 and E2 on three rows, one dead, one layer: the mean is the two live rows', each live row attends the two live keys with
+    softmax weights worked out here, the dead row gets feature 0 and confidence -inf."""
+    sd = pdsc_cases.shared_weights(1)
+    src = np.array([[0, 0, 0], [np.nan, 1, 1], [3, 4, 0]], np.float32)
+    tgt = np.array([[1, 1, 1], [5, 5, 5], [1, 1, 6.5]], np.float32)
+    feat, conf = pdsc_cpu.encode(src, tgt, sd, 1, 1.2)
+    assert not feat[1].any() and conf[1] == -np.inf and np.isfinite(conf[[0, 2]]).all()
+    B = pointdsc.fold(sd, 1, np.float64)
+    lay = lambda x, b, relu=False: (np.maximum(x @ b[0][:x.shape[1]] * b[1] + b[2], 0) if relu else x @ b[0][:x.shape[1]] * b[1] + b[2])
+    X = np.array([[0, 0, 0, 1, 1, 1], [3, 4, 0, 1, 1, 6.5]], np.float64)
+    X = (X - X.mean(0)).astype(np.float32).astype(np.float64)                # mean of the LIVE rows
+    h = lay(lay(X, B[0]), B[1], True)
+    qkv = lay(h, B[2])
+    q, k, v = qkv[:, :128], qkv[:, 128:256], qkv[:, 256:]
+    d = 5.0 - 5.5                                                            # |s0 - s2| = 5, |t0 - t2| = 5.5
+    cm = np.array([[1.0, 1 - d * d / 1.44], [1 - d * d / 1.44, 1.0]])
+    msg = np.empty((2, 128))
+    for i in range(2):
+        lg = np.array([cm[i, j] * (q[i] @ k[j]) / np.sqrt(128.0) for j in range(2)])
+        w = np.exp(lg - lg.max()); w /= w.sum()
+        msg[i] = w[0] * v[0] + w[1] * v[1]
+    x = h + lay(lay(lay(msg, B[3], True), B[4], True), B[5])
+    c = lay(lay(lay(x, B[6], True), B[7], True), B[8])[:, 0]
+    assert np.abs(feat[[0, 2]] - x).max() <= 1e-12 * np.abs(x).max() and np.abs(conf[[0, 2]] - c).max() <= 1e-12 * max(1.0, np.abs(c).max())
+    # all rows dead, and no rows
+    f, c = pdsc_cpu.encode(np.full((2, 3), np.inf, np.float32), tgt[:2], sd, 1, 1.2)
+    assert not f.any() and (c == -np.inf).all()
+    f, c = pdsc_cpu.encode(src[:0], tgt[:0], sd, 1, 1.2)
+    assert f.shape == (0, 128) and c.shape == (0,)
+
+
+def test_column_mean_is_the_contracts_tree():
+    rng = np.random.default_rng(5)
+    X = rng.standard_normal((2500, 6)) * 100
+    ok = rng.random(2500) > 0.1
+    s = [np.zeros(6) for _ in range(1024)]
+    for i in range(2500):
+        if ok[i]:
+            s[i % 1024] = s[i % 1024] + X[i]
+    h = 512
+    while h:
+        for t in range(h):
+            s[t] = s[t] + s[t + h]
+        h //= 2
+    assert np.array_equal(pdsc_cpu.column_mean(X, ok), s[0] / ok.sum())
+    assert np.abs(pdsc_cpu.column_mean(X, ok) - X[ok].mean(0)).max() < 1e-12
+
+
+@pytest.mark.parametrize("num_layers", (1, 2, 12, 16))
+def test_packing_round_trip_and_size(num_layers):
+    L = _ext.lib()
+    sd = pdsc_cases.weights(3, num_layers)
+    blob = pointdsc.pack(sd, num_layers)
+    assert blob.dtype == np.float32 and blob.nbytes == L.lr_pdsc_weights_bytes(num_layers) == 4 * pointdsc.packed_floats(num_layers)
+    blocks = pointdsc.unpack(blob, num_layers)
+    plan = pointdsc.layer_plan(num_layers)
+    assert len(blocks) == len(plan) == 1 + 5 * num_layers + 3
+    # the first block: the conv's weight transposed over two zero rows, no BatchNorm
+    Wt, scale, offset = blocks[0]
+    assert np.array_equal(Wt[:6], sd["encoder.layer0.weight"][:, :, 0].T) and not Wt[6:].any()
+    assert np.array_equal(scale, np.ones(128, np.float32)) and np.array_equal(offset, sd["encoder.layer0.bias"])
+    # a PointCN block: BatchNorm folded in fp64, rounded once
+    i = num_layers - 1
+    Wt, scale, offset = blocks[1 + 5 * i]
+    p = f"encoder.blocks.PointCN_layer_{i}"
+    g, b, mu, var = (sd[f"{p}.1.{k}"].astype(np.float64) for k in ("weight", "bias", "running_mean", "running_var"))
+    s64 = g / np.sqrt(var + 1e-5)
+    assert np.array_equal(Wt, sd[p + ".0.weight"][:, :, 0].T) and np.array_equal(scale, s64.astype(np.float32))
+    assert np.array_equal(offset, ((sd[p + ".0.bias"].astype(np.float64) - mu) * s64 + b).astype(np.float32))
+    # q | k | v stacked along the outputs
+    Wt, scale, offset = blocks[2 + 5 * i]
+    n = f"encoder.blocks.NonLocal_layer_{i}"
+    for j, x in enumerate("qkv"):
+        assert np.array_equal(Wt[:, 128 * j:128 * (j + 1)], sd[f"{n}.projection_{x}.weight"][:, :, 0].T)
+        assert np.array_equal(offset[128 * j:128 * (j + 1)], sd[f"{n}.projection_{x}.bias"])
+    assert np.array_equal(blocks[-1][0], sd["classification.4.weight"][:, :, 0].T) and blocks[-1][0].shape == (32, 1)
+    assert L.lr_pdsc_weights_bytes(0) == 0 and L.lr_pdsc_weights_bytes(17) == 0
+
+
+def test_state_dict_keys_are_checked_by_name():
+    sd = dict(pdsc_cases.weights(3, 2))
+    pointdsc.check_keys(sd, 2)                                               # sigma, sigma_spat, num_batches_tracked: ignored
+    lacking = {k: v for k, v in sd.items() if k != "encoder.blocks.NonLocal_layer_1.fc_message.4.running_var"}
+    with pytest.raises(KeyError, match=r"missing key 'encoder\.blocks\.NonLocal_layer_1\.fc_message\.4\.running_var'"):
+        pointdsc.pack(lacking, 2)
+    with pytest.raises(KeyError, match=r"unexpected key 'encoder\.blocks\.PointCN_layer_2\.0\.bias'"):
+        pointdsc.pack({**sd, "encoder.blocks.PointCN_layer_2.0.bias": np.zeros(128, np.float32)}, 2)
+    with pytest.raises(KeyError, match="missing key 'encoder.blocks.NonLocal_layer_2"):
+        pointdsc.pack(sd, 3)                                                 # a 2-layer checkpoint is not a 3-layer one
+    with pytest.raises(KeyError, match="unexpected key"):
+        pointdsc.pack(sd, 1)
+
+
+def test_struct_mirrors_match_the_header():
+    P, R = _ext.PdscParams, _ext.PdscResult
+    assert ctypes.sizeof(P) == 16 and P.struct_size.offset == 0 and P.num_layers.offset == 4 and P.sigma_d.offset == 8
+    assert ctypes.sizeof(R) == 16 and [f[0] for f in R._fields_] == ["status", "m", "dead", "reserved"]
+    p = P()
+    assert (p.struct_size, p.num_layers, p.sigma_d) == (16, 12, 1.2)
+    hdr = open(os.path.join(ROOT, "include", "lidarreg.h")).read()
+    for struct, mirror in (("lr_pdsc_params", P), ("lr_pdsc_result", R)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), hdr, re.S).group(1)
+        assert re.findall(r"^\s*(?:uint32_t|int32_t|double)\s+(\w+);", body, re.M) == [f[0] for f in mirror._fields_]
+
+
+def _single(L, **over):
+    one = ctypes.c_void_p(256)
+    a = dict(src=one, tgt=one, m=10, m_dev=None, weights=one, weights_bytes=L.lr_pdsc_weights_bytes(12), params=_ext.PdscParams(), result=one,
+             feat=None, conf=None, scratch=one, scratch_bytes=1 << 30)
+    a.update(over)
+    return L.lr_pdsc_encode(a["src"], a["tgt"], a["m"], a["m_dev"], a["weights"], a["weights_bytes"], ctypes.byref(a["params"]), a["result"],
+                            a["feat"], a["conf"], a["scratch"], a["scratch_bytes"], None)
+
+
+def _batch(L, **over):
+    one = ctypes.c_void_p(256)
+    ptrs = (ctypes.c_void_p * 2)(256, 256)
+    a = dict(npairs=2, src=ptrs, tgt=ptrs, m=(ctypes.c_int32 * 2)(10, 20), m_dev=None, weights=one, weights_bytes=L.lr_pdsc_weights_bytes(12),
+             params=_ext.PdscParams(), results=one, feat=None, conf=None, scratch=one, scratch_bytes=1 << 30)
+    a.update(over)
+    return L.lr_pdsc_encode_batch(a["npairs"], a["src"], a["tgt"], a["m"], a["m_dev"], a["weights"], a["weights_bytes"], ctypes.byref(a["params"]),
+                                  a["results"], a["feat"], a["conf"], a["scratch"], a["scratch_bytes"], None)
+
+
+def _bad_size():
+    p = _ext.PdscParams(); p.struct_size = 8
+    return p
+
+
+FAULTS = [
+    (dict(params=_bad_size()), b"lr_pdsc_params.struct_size is 8"),
+    (dict(params=_ext.PdscParams(num_layers=0)), b"num_layers"),
+    (dict(params=_ext.PdscParams(num_layers=17)), b"num_layers"),
+    (dict(params=_ext.PdscParams(sigma_d=0.0)), b"sigma_d"),
+    (dict(params=_ext.PdscParams(sigma_d=float("inf"))), b"sigma_d"),
+    (dict(params=_ext.PdscParams(sigma_d=float("nan"))), b"sigma_d"),
+    (dict(weights=None), b"null weights"),
+    (dict(weights=ctypes.c_void_p(260)), b"weights must be 16-byte aligned"),
+    (dict(weights_bytes=4 * pointdsc.packed_floats(12) - 4), b"weights_bytes"),
+    (dict(scratch=None), b"null"),
+    (dict(scratch_bytes=1024), b"scratch too small (npairs * lr_pdsc_scratch_bytes(max m))"),
+    (dict(scratch=ctypes.c_void_p(264)), b"256-byte aligned"),
+]
+
+
+@pytest.mark.parametrize("k", range(len(FAULTS)))
+def test_refusals_come_before_any_device_call(k):
+    """Every entry point with exactly one fault each: LR_EINVAL with the argument named, nothing touched (the pointers are not memory)."""
+    L = _ext.lib()
+    over, text = FAULTS[k]
+    for call, who in ((_single, b"lr_pdsc_encode"), (_batch, b"lr_pdsc_encode_batch")):
+        assert call(L, **over) == -1, (who, over)
+        err = L.lr_last_error()
+        assert text in err and who in err, err
+
+
+def test_refusals_of_the_counts():
+    L = _ext.lib()
+    assert _single(L, m=32769) == -1 and b"32768" in L.lr_last_error()
+    assert _single(L, m=-1) == -1 and b"negative" in L.lr_last_error()
+    assert _single(L, src=None) == -1 and b"null point array" in L.lr_last_error()
+    assert _single(L, result=None) == -1 and b"null pointer" in L.lr_last_error()
+    assert _batch(L, m=(ctypes.c_int32 * 2)(10, 32769)) == -1 and b"32768" in L.lr_last_error()
+    assert _batch(L, npairs=0) == -1 and _batch(L, npairs=65) == -1 and b"npairs" in L.lr_last_error()
+    assert _batch(L, src=None) == -1 and b"null pointer" in L.lr_last_error()
+    # a 16-layer blob is asked for when the params say 16 layers
+    assert _single(L, params=_ext.PdscParams(num_layers=16)) == -1 and b"weights_bytes" in L.lr_last_error()
+
+
+def test_scratch_bytes_is_linear_in_m():
+    L = _ext.lib()
+    f = L.lr_pdsc_scratch_bytes
+    assert f(-1) == 0 and f(32769) == 0 and f(0) > 0
+    ms = sorted({0, 1, 2, 31, 32, 33, 127, 128, 129, 1000, 2000, 4095, 4096, 4097, 8191, 8192, 8193, 12000, 16384, 20000, 32768} | set(range(0, 32769, 997)))
+    sizes = [f(m) for m in ms]
+    assert all(a <= b for a, b in zip(sizes, sizes[1:]))
+    for m in ms:
+        if 2 * m <= 32768:
+            assert f(2 * m) <= 2 * f(m) + f(0), m
+    assert f(32768) <= 32768 * 5500 + f(0)                                   # no M x M term: a few KB per correspondence
