@@ -122,11 +122,13 @@ class PointDSCEncoder:
         classification.{0,2,4}.*.  sigma, sigma_spat and num_batches_tracked are ignored; any other missing or extra key is refused."""
         return cls(pack(sd, num_layers), num_layers, sigma_d, device)
 
-    def encode_batch(self, srcs, tgts, ms=None, m_devs=None, poison=None, single=False, timed=False):
+    def encode_batch(self, srcs, tgts, ms=None, m_devs=None, poison=None, single=False, timed=False, want_feat=None, want_conf=None):
         """lr_pdsc_encode_batch over len(srcs) ragged pairs ([M_k,3] float32 each, any M_k incl. 0).  ms: the counts passed as m (default:
-        the rows); m_devs: optional device int32 tensors with a smaller live count; poison: fill the scratch with this byte first (test
-        hook); single: go through lr_pdsc_encode (one pair).  Returns [(features [m,128], confidence [m], info dict)] with device
-        tensors -- and, with timed, the device time of the call in ms."""
+        the rows); m_devs: optional device int32 tensors with a smaller live count (an entry may be None); poison: fill the scratch with
+        this byte first (test hook); single: go through lr_pdsc_encode (one pair).  want_feat / want_conf: which outputs the library is
+        asked for -- None: all; False: none, the call gets NULL for the whole feat_out / conf_out array; a list of bools: NULL for the
+        entries that are False.  The tensor of an output that was not asked for comes back with its -1 fill.  Returns [(features
+        [m,128], confidence [m], info dict)] with device tensors -- and, with timed, the device time of the call in ms."""
         L = _ext.lib()
         n = len(srcs)
         srcs = [_f32(s).reshape(-1, 3) for s in srcs]; tgts = [_f32(t).reshape(-1, 3) for t in tgts]
@@ -138,14 +140,17 @@ class PointDSCEncoder:
         feats = [torch.full((max(m, 1), C), -1.0, dtype=torch.float32, device=dev) for m in ms]
         confs = [torch.full((max(m, 1),), -1.0, dtype=torch.float32, device=dev) for m in ms]
         w = (self.weights.data_ptr(), self.weights.numel() * 4, ctypes.byref(self.params), res.data_ptr())
+        # the output tensors as the call sees them: None for the whole array, or None per entry
+        asked = lambda ts, want: ts if want is None else None if want is False else [t if ok else None for t, ok in zip(ts, want)]
+        fo, co = asked(feats, want_feat), asked(confs, want_conf)
         if single:
             assert n == 1
             fn = L.lr_pdsc_encode
-            args = (ptr(srcs[0]), ptr(tgts[0]), ms[0], ptr(m_devs and m_devs[0]), *w, ptr(feats[0]), ptr(confs[0]))
+            args = (ptr(srcs[0]), ptr(tgts[0]), ms[0], ptr(m_devs and m_devs[0]), *w, ptr(fo and fo[0]), ptr(co and co[0]))
         else:
             arr = lambda ts: None if ts is None else (ctypes.c_void_p * n)(*[ptr(t) for t in ts])
             fn = L.lr_pdsc_encode_batch
-            args = (n, arr(srcs), arr(tgts), (ctypes.c_int32 * n)(*ms), arr(m_devs), *w, arr(feats), arr(confs))
+            args = (n, arr(srcs), arr(tgts), (ctypes.c_int32 * n)(*ms), arr(m_devs), *w, arr(fo), arr(co))
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         ev0.record()
         _ext.check(fn(*args, scratch.data_ptr(), scratch.numel(), _stream()))
@@ -157,7 +162,9 @@ class PointDSCEncoder:
         self.last_raw = (feats, confs)
         return (out, ev0.elapsed_time(ev1)) if timed else out
 
-    def encode(self, src, tgt, m_dev=None, poison=None):
-        """lr_pdsc_encode on one correspondence set: (features [m,128], confidence [m]) as device tensors."""
-        f, c, self.last_info = self.encode_batch([src], [tgt], None, None if m_dev is None else [m_dev], poison, single=True)[0]
+    def encode(self, src, tgt, m_dev=None, poison=None, want_feat=None, want_conf=None):
+        """lr_pdsc_encode on one correspondence set: (features [m,128], confidence [m]) as device tensors; want_feat / want_conf = False
+        passes NULL for that output (its tensor keeps the -1 fill)."""
+        f, c, self.last_info = self.encode_batch([src], [tgt], None, None if m_dev is None else [m_dev], poison, single=True,
+                                                 want_feat=want_feat, want_conf=want_conf)[0]
         return f, c

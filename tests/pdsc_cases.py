@@ -115,6 +115,35 @@ def nonfinite(m, seed=0):
     return src, tgt, bad
 
 
+def dead_block(m, lo, hi, keep=()):
+    """The planted case with the rows lo .. hi-1 (but those in `keep`) dead as a block: NaN, +Inf, -Inf in turn, in src or tgt as
+    nonfinite() places them: (src, tgt, indices of the dead rows, ascending)."""
+    src, tgt = planted(m)
+    bad = np.array([i for i in range(lo, hi) if i not in keep], np.int64)
+    for n, i in enumerate(bad):
+        (src if n & 1 else tgt)[i, n % 3] = (np.nan, np.inf, -np.inf)[n % 3]
+    return src, tgt, bad
+
+
+# The attention plans above m = 8192 (pd_make_plan): the full 512-block grid, the first m of 7, 6, 4, 3 and 2 chunks and the contract's
+# largest m at one layer (one attention pass is what the plan changes); the first m of 5 chunks -- the plan of the CLI's 12 000 rows -- at
+# full depth.  Recorded by tests/golden/make_golden_pdsc_large.py.
+LARGE = tuple((m, 1) for m in (8192, 8193, 9345, 13057, 16385, 21761, 32768)) + ((10881, 12),)
+
+
+def large_case(m, num_layers):
+    src, tgt = planted(m)
+    return dict(name=golden_name(m, num_layers), m=m, num_layers=num_layers, src=src, tgt=tgt, sd=shared_weights(num_layers))
+
+
+def conf_rows(m):
+    """The rows of a large case whose fp64 confidence is recorded: 128 b + ((37 b + 32 w) mod 128) for every query block b and w = 0 .. 3
+    -- four rows of every block, one per wave, the lane moving from block to block -- as far as they lie below m, and row m - 1."""
+    b, w = np.meshgrid(np.arange((m + 127) // 128, dtype=np.int64), np.arange(4, dtype=np.int64), indexing="ij")
+    rows = (128 * b + (37 * b + 32 * w) % 128).reshape(-1)
+    return np.unique(np.concatenate([rows[rows < m], [m - 1]]))
+
+
 def golden_case(m, num_layers):
     src, tgt = planted(m, seed=m + num_layers)
     return dict(name=golden_name(m, num_layers), m=m, num_layers=num_layers, src=src, tgt=tgt, sd=shared_weights(num_layers))

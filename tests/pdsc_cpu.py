@@ -3,7 +3,9 @@ include/lidarreg.h).
 
 Independent of the device code: the compatibility matrix, the logits and the softmax weights are formed whole, the layers are matrix
 products.  dtype float64 is what the GPU is held to (and what tests/test_pdsc_cpu.py holds against the reference's own fp64 run);
-dtype float32 measures what fp32 arithmetic alone costs on a case (a tolerance is a multiple of THAT distance, never of the kernel's)."""
+dtype float32 measures what fp32 arithmetic alone costs on a case (a tolerance is a multiple of THAT distance, never of the kernel's).
+encode_slabbed is encode() without an m x m matrix (it reaches m = 32 768), encode_tiled32 an fp32 evaluation whose softmax runs in the
+contract's own order; plan, max_blocks and scratch_bytes restate the attention's work plan and the arena layout of the C code."""
 import functools
 
 import numpy as np
@@ -44,21 +46,26 @@ def corr_pos(src, tgt, ok):
     return out
 
 
+def compat_rows(A, B, i0, i1, sigma_d):
+    """E3 for the query rows i0 .. i1-1 against every key: [i1-i0, m] in the dtype of A and B (the coordinates, already converted)."""
+    dtype = A.dtype.type
+    da = A[i0:i1, None, :] - A[None, :, :]
+    db = B[i0:i1, None, :] - B[None, :, :]
+    la = np.sqrt((da[..., 0] * da[..., 0] + da[..., 1] * da[..., 1]) + da[..., 2] * da[..., 2])
+    lb = np.sqrt((db[..., 0] * db[..., 0] + db[..., 1] * db[..., 1]) + db[..., 2] * db[..., 2])
+    d = la - lb
+    if dtype == np.float32:
+        return np.maximum(np.float32(0), (d * d) * np.float32(-1.0 / (sigma_d * sigma_d)) + np.float32(1))
+    return np.maximum(0.0, 1.0 - d * d / (sigma_d * sigma_d))
+
+
 def compat(src, tgt, sigma_d, dtype=np.float64, slab=512):
     """E3: [m,m] max(0, 1 - d^2 / sigma_d^2), d = |s_i - s_j| - |t_i - t_j| on direct differences of the given fp32 coordinates."""
     m = len(src)
     A, B = src.astype(dtype), tgt.astype(dtype)
     out = np.empty((m, m), dtype)
     for i0 in range(0, m, slab):
-        da = A[i0:i0 + slab, None, :] - A[None, :, :]
-        db = B[i0:i0 + slab, None, :] - B[None, :, :]
-        la = np.sqrt((da[..., 0] * da[..., 0] + da[..., 1] * da[..., 1]) + da[..., 2] * da[..., 2])
-        lb = np.sqrt((db[..., 0] * db[..., 0] + db[..., 1] * db[..., 1]) + db[..., 2] * db[..., 2])
-        d = la - lb
-        if dtype == np.float32:
-            out[i0:i0 + slab] = np.maximum(np.float32(0), (d * d) * np.float32(-1.0 / (sigma_d * sigma_d)) + np.float32(1))
-        else:
-            out[i0:i0 + slab] = np.maximum(0.0, 1.0 - d * d / (sigma_d * sigma_d))
+        out[i0:i0 + slab] = compat_rows(A, B, i0, min(m, i0 + slab), sigma_d)
     return out
 
 
@@ -68,10 +75,87 @@ def layer(x, block, relu=False):
     return np.maximum(y, 0) if relu else y
 
 
-def encode(src, tgt, sd, num_layers=12, sigma_d=1.2, dtype=np.float64, m=None):
-    """The whole contract on the first m (default: all) correspondences: (features [m,128], confidence [m]) as `dtype`; dead rows get
-    feature 0 and confidence -inf.  The live rows are evaluated as a set of their own: a dead row is attended by nobody and enters no
-    mean, so it changes nothing for the others."""
+def _attend_whole(src, tgt, sigma_d, dtype):
+    """The attention of encode(): compatibility, logits and softmax weights as whole [n,n] matrices; the compatibility formed once."""
+    Cm = compat(src, tgt, sigma_d, dtype)
+    qscale = dtype(1.0 / np.sqrt(float(C)))
+
+    def attend(q, k, v):
+        logits = Cm * ((q @ k.T) * qscale)
+        w = np.exp(logits - logits.max(axis=1, keepdims=True))
+        w = w / w.sum(axis=1, keepdims=True)
+        return w @ v
+    return attend
+
+
+def _attend_slabbed(src, tgt, sigma_d, dtype, slab):
+    """The same formulas per slab of query rows, the compatibility recomputed per layer: never more than slab x n at a time."""
+    A, B = src.astype(dtype), tgt.astype(dtype)
+    qscale = dtype(1.0 / np.sqrt(float(C)))
+
+    def attend(q, k, v):
+        msg = np.empty_like(v)
+        for i0 in range(0, len(q), slab):
+            i1 = min(len(q), i0 + slab)
+            logits = compat_rows(A, B, i0, i1, sigma_d) * ((q[i0:i1] @ k.T) * qscale)
+            w = np.exp(logits - logits.max(axis=1, keepdims=True))
+            w = w / w.sum(axis=1, keepdims=True)
+            msg[i0:i1] = w @ v
+        return msg
+    return attend
+
+
+FLT_MAX = np.float32(np.finfo(np.float32).max)
+
+
+def _attend_tiled32(src, tgt, sigma_d):
+    """E6's order in fp32: under plan(n) every chunk walks its key tiles of 32 in ascending order behind a running maximum and sum per
+    row, rescaling on a new maximum (pd_attn_kernel); the chunks are merged in ascending order (pd_combine_kernel).  Vectorised over the
+    queries, one step per tile.  Not the device's bits: the order inside a tile (the MFMA's, the two lane halves') is numpy's here."""
+    f32 = np.float32
+    A, B = src.astype(f32), tgt.astype(f32)
+    n = len(A)
+    _, chunks, per = plan(n)
+    qscale, nk = f32(1.0 / np.sqrt(float(C))), f32(-1.0 / (sigma_d * sigma_d))
+
+    def tile_compat(j0, j1):
+        da, db = A[:, None, :] - A[None, j0:j1, :], B[:, None, :] - B[None, j0:j1, :]
+        la = np.sqrt((da[..., 0] * da[..., 0] + da[..., 1] * da[..., 1]) + da[..., 2] * da[..., 2])
+        lb = np.sqrt((db[..., 0] * db[..., 0] + db[..., 1] * db[..., 1]) + db[..., 2] * db[..., 2])
+        d = la - lb
+        return np.maximum(f32(0), (d * d) * nk + f32(1))
+
+    def attend(q, k, v):
+        part = []
+        with np.errstate(over="ignore", under="ignore"):
+            for c in range(chunks):
+                k0, k1 = c * per, min(n, (c + 1) * per)
+                assert k0 < k1
+                m_run, l_run, o = np.full(n, -FLT_MAX, f32), np.zeros(n, f32), np.zeros((n, C), f32)
+                for j0 in range(k0, k1, TILE):
+                    j1 = min(k1, j0 + TILE)
+                    x = tile_compat(j0, j1) * ((q @ k[j0:j1].T) * qscale)
+                    m_new = np.maximum(m_run, x.max(axis=1))
+                    alpha = np.exp(m_run - m_new)
+                    p = np.exp(x - m_new[:, None])
+                    l_run = l_run * alpha + p.sum(axis=1, dtype=f32)
+                    o = o * alpha[:, None] + p @ v[j0:j1]
+                    m_run = m_new
+                part.append((m_run, l_run, o))
+            mx = np.full(n, -FLT_MAX, f32)
+            for m_c, _, _ in part:
+                mx = np.maximum(mx, m_c)
+            l, acc = np.zeros(n, f32), np.zeros((n, C), f32)
+            for m_c, l_c, o_c in part:
+                w = np.exp(m_c - mx)
+                l = l_c * w + l
+                acc = o_c * w[:, None] + acc
+        assert (l > 0).all()
+        return acc / l[:, None]
+    return attend
+
+
+def _encode(src, tgt, sd, num_layers, dtype, m, make_attend):
     m = len(src) if m is None else int(m)
     src, tgt = np.asarray(src, np.float32)[:m], np.asarray(tgt, np.float32)[:m]
     feat, conf = np.zeros((m, C), dtype), np.full(m, -np.inf, dtype)
@@ -80,21 +164,68 @@ def encode(src, tgt, sd, num_layers=12, sigma_d=1.2, dtype=np.float64, m=None):
         return feat, conf
     blocks = iter(pointdsc.fold(sd, num_layers, dtype))
     x = layer(corr_pos(src, tgt, ok)[ok].astype(dtype), next(blocks))
-    Cm = compat(src[ok], tgt[ok], sigma_d, dtype)
-    qscale = dtype(1.0 / np.sqrt(float(C)))
+    attend = make_attend(src[ok], tgt[ok])
     for _ in range(num_layers):
         h = layer(x, next(blocks), relu=True)
         qkv = layer(h, next(blocks))
-        q, k, v = qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:]
-        logits = Cm * ((q @ k.T) * qscale)
-        w = np.exp(logits - logits.max(axis=1, keepdims=True))
-        w = w / w.sum(axis=1, keepdims=True)
-        msg = w @ v
+        msg = attend(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:])
         msg = layer(layer(layer(msg, next(blocks), relu=True), next(blocks), relu=True), next(blocks))
         x = h + msg
     c = layer(layer(layer(x, next(blocks), relu=True), next(blocks), relu=True), next(blocks))
     feat[ok], conf[ok] = x, c[:, 0]
     return feat, conf
+
+
+def encode(src, tgt, sd, num_layers=12, sigma_d=1.2, dtype=np.float64, m=None):
+    """The whole contract on the first m (default: all) correspondences: (features [m,128], confidence [m]) as `dtype`; dead rows get
+    feature 0 and confidence -inf.  The live rows are evaluated as a set of their own: a dead row is attended by nobody and enters no
+    mean, so it changes nothing for the others."""
+    return _encode(src, tgt, sd, num_layers, dtype, m, lambda s, t: _attend_whole(s, t, sigma_d, dtype))
+
+
+def encode_slabbed(src, tgt, sd, num_layers=12, sigma_d=1.2, dtype=np.float64, m=None, slab=512):
+    """encode() without an n x n matrix: the compatibility, the logits and the softmax weights are formed per slab of `slab` query rows
+    and recomputed per layer -- never more than slab x n at a time, which is what reaches m = 32 768 (the three fp64 matrices of
+    encode() would take 26 GB there).  The same formulas: fp64 equals encode() to 1e-12 (tests/test_pdsc_cpu.py); in float32 it is one
+    valid fp32 evaluation like any other."""
+    return _encode(src, tgt, sd, num_layers, dtype, m, lambda s, t: _attend_slabbed(s, t, sigma_d, dtype, slab))
+
+
+def encode_tiled32(src, tgt, sd, num_layers=12, sigma_d=1.2, m=None):
+    """An fp32 evaluation whose softmax runs in the order E6 fixes (_attend_tiled32) under plan(number of live rows): what summing 512
+    tiles in sequence behind one running maximum costs in fp32, which numpy's blocked sums do not show.  Returns float32."""
+    return _encode(src, tgt, sd, num_layers, np.float32, m, lambda s, t: _attend_tiled32(s, t, sigma_d))
+
+
+# ---- pd_make_plan, pd_max_blocks and pd_make_layout of csrc/lr_pdsc.hip, restated ------------------------------------------------------
+QB, TILE, MAX_CHUNKS, TARGET_BLOCKS, MAX_M = 128, 32, 8, 512, 32768
+
+
+def plan(m):
+    """pd_make_plan: (query blocks of 128, key chunks, keys per chunk) of a pair with live count m."""
+    nb = (m + QB - 1) // QB if m > 0 else 1
+    ch = max(1, min(TARGET_BLOCKS // nb, MAX_CHUNKS))
+    tiles = (m + TILE - 1) // TILE if m > 0 else 1
+    ch = min(ch, tiles)
+    tpc = (tiles + ch - 1) // ch
+    return nb, (tiles + tpc - 1) // tpc, tpc * TILE
+
+
+def max_blocks(mx):
+    """pd_max_blocks: the attention launch's blocks per pair for a call whose largest m is mx."""
+    nb = (mx + QB - 1) // QB if mx > 0 else 1
+    return min(MAX_CHUNKS * nb, max(nb, TARGET_BLOCKS))
+
+
+def scratch_bytes(mx):
+    """pd_make_layout: the control block, then per padded row the 32-byte record, the input [8], A, B, q|k|v, the
+    message [128 + 128 + 384 + 128 floats], f1 and f2 [64 each] and the confidence, then max_blocks x 128 partial rows of 128 floats
+    and of (maximum, sum); every array rounded up to 256 bytes (lr_al of csrc/lr_scratch.h)."""
+    al = lambda x: (x + 255) & ~255
+    Mp = (max(mx, 1) + QB - 1) // QB * QB
+    prow = max_blocks(mx) * QB
+    rows = (32, 8 * 4, C * 4, C * 4, 3 * C * 4, C * 4, 64 * 4, 64 * 4, 4)
+    return al(64) + sum(al(Mp * b) for b in rows) + al(prow * C * 4) + al(prow * 8)
 
 
 @functools.lru_cache(maxsize=None)

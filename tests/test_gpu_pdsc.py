@@ -1,43 +1,54 @@
 """The PointDSC encoder on the GPU (csrc/lr_pdsc.hip through lidarregistration_amd.pointdsc) against the reference's recorded fp64 outputs
-(tests/golden/g24_pdsc.npz) and the numpy restatement (tests/pdsc_cpu.py).
+(tests/golden/g24_pdsc.npz), the numpy restatement (tests/pdsc_cpu.py) and, above m = 8 192, the restatement's recorded fp64 outputs
+(tests/golden/g25_pdsc_large.npz).
 
 The tolerance rule, everywhere: |device - fp64 reference| <= max(4 x yardstick, 16 x 2^-23 x max |reference|), for features and confidence
 separately, where the yardstick is what fp32 arithmetic costs the REFERENCE on that case: its own recorded fp32-vs-fp64 deviation for
 the golden cases, the fp32-vs-fp64 deviation of the restatement elsewhere (tests/test_pdsc_cpu.py holds the latter within 2 x the
-former).  The factor 4 is the room for another, fixed order of summation and the folded BatchNorm; nothing here is derived from what
+former); for the recorded large cases the larger of two such deviations, numpy's blocked sums and the contract's own tile order.  The factor 4 is the room for another, fixed order of summation and the folded BatchNorm; nothing here is derived from what
 the kernel returns."""
+import ctypes
 import functools
 import os
+import time
 
 import numpy as np
 import pytest
 import torch
 
-from lidarregistration_amd import pointdsc
+from lidarregistration_amd import _ext, pointdsc
 from tests import pdsc_cases, pdsc_cpu
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = np.load(os.path.join(ROOT, "tests", "golden", "g24_pdsc.npz"))
+LARGE_GOLD = np.load(os.path.join(ROOT, "tests", "golden", "g25_pdsc_large.npz"))
 IDS = [pdsc_cases.golden_name(m, L) for m, L in pdsc_cases.GOLDEN]
+LARGE_IDS = [pdsc_cases.golden_name(m, L) for m, L in pdsc_cases.LARGE]
 SIGMA = pdsc_cases.SIGMA_D
 
 
 @functools.lru_cache(maxsize=None)
-def encoder(num_layers=12, scale=1.0):
-    return pointdsc.PointDSCEncoder.from_state_dict(pdsc_cases.shared_weights(num_layers, scale), num_layers, SIGMA)
+def encoder(num_layers=12, scale=1.0, sigma_d=SIGMA):
+    return pointdsc.PointDSCEncoder.from_state_dict(pdsc_cases.shared_weights(num_layers, scale), num_layers, sigma_d)
+
+
+def live_bound(src, tgt, sd, num_layers, sigma_d, f64, c64, fn=pdsc_cpu.encode):
+    """The bounds of the tolerance rule with a live yardstick: the fp32 restatement's distance to the fp64 one, f64 / c64."""
+    f32, c32 = fn(src, tgt, sd, num_layers, sigma_d, np.float32)
+    fin = np.isfinite(c64)
+    return pdsc_cpu.bound(float(np.abs(f32 - f64).max(initial=0.0)), float(np.abs(c32[fin] - c64[fin]).max(initial=0.0)), f64, c64)
 
 
 @functools.lru_cache(maxsize=None)
-def yardstick(kind, m, scale=1.0):
-    """(case inputs, fp64 restatement, bounds of the tolerance rule) of a 12-layer case, computed once and shared (read-only)."""
-    case = getattr(pdsc_cases, kind)(m)
+def yardstick(kind, m, scale=1.0, num_layers=12, sigma_d=SIGMA, extra=()):
+    """(case inputs, fp64 restatement, bounds of the tolerance rule) of the case pdsc_cases.<kind>(m, *extra), computed once and shared
+    (read-only)."""
+    case = getattr(pdsc_cases, kind)(m, *extra)
     src, tgt = case[0], case[1]
-    sd = pdsc_cases.shared_weights(12, scale)
-    f64, c64 = pdsc_cpu.encode(src, tgt, sd, 12, SIGMA, np.float64)
-    f32, c32 = pdsc_cpu.encode(src, tgt, sd, 12, SIGMA, np.float32)
-    fin = np.isfinite(c64)
-    bounds = pdsc_cpu.bound(float(np.abs(f32 - f64).max(initial=0.0)), float(np.abs(c32[fin] - c64[fin]).max(initial=0.0)), f64, c64)
+    sd = pdsc_cases.shared_weights(num_layers, scale)
+    f64, c64 = pdsc_cpu.encode(src, tgt, sd, num_layers, sigma_d, np.float64)
+    bounds = live_bound(src, tgt, sd, num_layers, sigma_d, f64, c64)
     for x in (f64, c64):
         x.setflags(write=False)
     return case, f64, c64, bounds
@@ -169,3 +180,249 @@ def test_empty_pair_stores_nothing():
     assert out[0][2] == dict(status=1, m=0, dead=0) and (enc.last_raw[0][0] == -1.0).all() and (enc.last_raw[1][0] == -1.0).all()
     f, c = enc.encode(src, tgt)
     assert torch.equal(out[1][0], f) and torch.equal(out[1][1], c)
+
+
+# ---- the attention plans above m = 8 192 (tests/golden/g25_pdsc_large.npz) ---------------------------------------------------------------
+@pytest.mark.parametrize("m,num_layers", pdsc_cases.LARGE, ids=LARGE_IDS)
+def test_large_plans(m, num_layers):
+    """Every chunk count of pd_make_plan from 8 down to 2, the saturated grid and the contract's largest m, against the recorded fp64
+    rows.  The yardstick is the larger of the two recorded fp32 evaluations of the reference's formula: numpy's blocked sums (d32) and
+    the contract's own order (d32t), both from the CPU generator."""
+    c = pdsc_cases.large_case(m, num_layers)
+    n = c["name"]
+    enc = encoder(num_layers)
+    feat, conf = enc.encode(c["src"], c["tgt"])
+    assert enc.last_info == dict(status=0, m=m, dead=0)
+    feat, conf = host(feat), host(conf)
+    gf, gc = LARGE_GOLD[n + "/feat"], LARGE_GOLD[n + "/conf"]
+    yf = max(float(LARGE_GOLD[n + "/d32_feat"]), float(LARGE_GOLD[n + "/d32t_feat"]))
+    yc = max(float(LARGE_GOLD[n + "/d32_conf"]), float(LARGE_GOLD[n + "/d32t_conf"]))
+    bounds = pdsc_cpu.bound(yf, yc, gf, gc)
+    df = float(np.abs(feat[pdsc_cases.feature_rows(m)] - gf).max()); dc = float(np.abs(conf[pdsc_cases.conf_rows(m)] - gc).max())
+    print(f"{n}, plan {pdsc_cpu.plan(m)}: |device - fp64 recording| / yardstick: features {df:.2e} / {yf:.2e} = {df / yf:.2f}, "
+          f"confidence {dc:.2e} / {yc:.2e} = {dc / yc:.2f}; bounds {bounds[0]:.2e}, {bounds[1]:.2e}")
+    assert np.isfinite(feat).all() and np.isfinite(conf).all()
+    assert df <= bounds[0] and dc <= bounds[1]
+
+
+def test_bits_at_the_grid_edge_in_a_batch():
+    """m = 8 193 needs 455 of the 512 launched blocks (57 leave early): as pair 0 of [8 193, 129] over a scratch of 0xFF it gives the
+    bits of its single call."""
+    enc = encoder(1)
+    s, t = pdsc_cases.planted(8193)
+    s2, t2 = pdsc_cases.planted(129)
+    f1, c1 = enc.encode(s, t, poison=0x00)
+    out = enc.encode_batch([s, s2], [t, t2], poison=0xFF)
+    assert out[0][2] == dict(status=0, m=8193, dead=0) and out[1][2] == dict(status=0, m=129, dead=0)
+    assert torch.equal(out[0][0], f1) and torch.equal(out[0][1], c1)
+    f2, c2 = enc.encode(s2, t2)
+    assert torch.equal(out[1][0], f2) and torch.equal(out[1][1], c2)
+
+
+def test_live_count_fills_the_grid_under_a_larger_m():
+    """m = 8 320 on the host, 8 192 on the device: the live plan (64 query blocks x 8 chunks) fills the 512-block grid exactly.  The
+    bits of the single call on the first 8 192 rows, zeros behind them -- and that single call by the tolerance rule against the slabbed
+    restatement run here (1 layer; the one large case with a live yardstick)."""
+    enc = encoder(1)
+    src, tgt = pdsc_cases.planted(8320)
+    live = 8192
+    feat, conf = enc.encode(src, tgt, m_dev=torch.tensor([live], dtype=torch.int32, device="cuda"), poison=0xFF)
+    assert enc.last_info == dict(status=0, m=live, dead=0) and feat.shape == (8320, 128)
+    f1, c1 = enc.encode(src[:live], tgt[:live])
+    assert torch.equal(feat[:live], f1) and torch.equal(conf[:live], c1)
+    assert not feat[live:].any() and not conf[live:].any()
+    t0 = time.time()
+    sd = pdsc_cases.shared_weights(1)
+    f64, c64 = pdsc_cpu.encode_slabbed(src[:live], tgt[:live], sd, 1, SIGMA, np.float64)
+    bounds = live_bound(src[:live], tgt[:live], sd, 1, SIGMA, f64, c64, fn=pdsc_cpu.encode_slabbed)
+    print(f"the slabbed restatement of 8 192 rows, fp64 and fp32: {time.time() - t0:.1f} s on the CPU")
+    check("8 192 live of 8 320", host(f1), host(c1), f64, c64, bounds)
+
+
+def test_ragged_batch_at_the_largest_m():
+    """[32 768, 2 048] in one call at 1 layer: pair 1 uses 128 of the 512 launched blocks and gives the bits of its single call."""
+    enc = encoder(1)
+    s, t = pdsc_cases.planted(32768)
+    s2, t2 = pdsc_cases.planted(2048)
+    out = enc.encode_batch([s, s2], [t, t2], poison=0xFF)
+    assert out[0][2] == dict(status=0, m=32768, dead=0) and out[1][2] == dict(status=0, m=2048, dead=0)
+    f2, c2 = enc.encode(s2, t2)
+    assert torch.equal(out[1][0], f2) and torch.equal(out[1][1], c2)
+    f1, c1 = enc.encode(s, t)
+    assert torch.equal(out[0][0], f1) and torch.equal(out[0][1], c1)
+
+
+# ---- dead tiles, chunks and query blocks (m = 320: 3 query blocks, 5 chunks of 64 keys, i.e. of two tiles) ------------------------------
+DEAD_BLOCKS = {"chunk 0 dead": (0, 64), "a chunk opens on a dead tile": (64, 96), "a chunk closes on a dead tile": (96, 128),
+               "query block 0 and two chunks dead": (0, 128), "last chunk and last query block dead": (256, 320),
+               "one live key": (0, 320, (200,))}
+
+
+@pytest.mark.parametrize("what", list(DEAD_BLOCKS))
+def test_dead_blocks(what):
+    """E1 where a whole tile, chunk or query block is dead -- the states in which an online softmax meets -inf - -inf."""
+    assert pdsc_cpu.plan(320) == (3, 5, 64)
+    enc = encoder()
+    (src, tgt, bad), f64, c64, bounds = yardstick("dead_block", 320, extra=DEAD_BLOCKS[what])
+    keep = np.setdiff1d(np.arange(320), bad)
+    assert len(bad) + len(keep) == 320 and (len(keep) == 1) == (what == "one live key")
+    feat, conf = enc.encode(src, tgt)
+    feat, conf = host(feat), host(conf)
+    assert enc.last_info == dict(status=0, m=320, dead=len(bad))
+    assert not feat[bad].any() and (conf[bad] == -np.inf).all()
+    assert np.isfinite(feat).all() and np.isfinite(conf[keep]).all()
+    check(f"{what}, against the restatement", feat, conf, f64, c64, bounds)
+    f2, c2 = enc.encode(src[keep], tgt[keep])
+    assert enc.last_info == dict(status=0, m=len(keep), dead=0)
+    check(f"{what}, against the call without the dead rows", feat[keep], conf[keep], host(f2).astype(np.float64), host(c2).astype(np.float64),
+          (2 * bounds[0], 2 * bounds[1]))            # (two device results: each within the bound of the fp64 reference)
+
+
+# ---- live counts, NULL outputs, parameters, capture ------------------------------------------------------------------------------------
+def test_live_counts_in_a_batch():
+    """m_dev below m, absent, 0, above m (clamped) and negative (0) in one call: status / m / dead per pair, zeros at and past the live
+    count wherever the host m is positive (a live count of 0 included), the live rows bit for bit what the single call on them gives."""
+    enc = encoder()
+    table = ((700, 33, 0, 33), (700, None, 0, 700), (300, 0, 1, 0), (129, 1000, 0, 129), (64, -5, 1, 0))
+    cases = [pdsc_cases.planted(m) for m, _, _, _ in table]
+    m_devs = [None if v is None else torch.tensor([v], dtype=torch.int32, device="cuda") for _, v, _, _ in table]
+    out = enc.encode_batch([c[0] for c in cases], [c[1] for c in cases], m_devs=m_devs, poison=0xFF)
+    for k, (m, _, status, live) in enumerate(table):
+        feat, conf, info = out[k]
+        assert info == dict(status=status, m=live, dead=0), (k, info)
+        assert feat.shape == (m, 128) and conf.shape == (m,)
+        assert not feat[live:].any() and not conf[live:].any(), k
+        if live:
+            f1, c1 = enc.encode(cases[k][0][:live], cases[k][1][:live])
+            assert torch.equal(feat[:live], f1) and torch.equal(conf[:live], c1), k
+
+
+def test_live_count_decides_the_plan():
+    """m = 2 048 with 257 live rows: the plan is that of 257 (5 chunks of 64 keys), not that of 2 048 (8 chunks of 256)."""
+    assert pdsc_cpu.plan(2048)[1:] == (8, 256) and pdsc_cpu.plan(257)[1:] == (5, 64)
+    enc = encoder()
+    src, tgt = pdsc_cases.planted(2048)
+    live = 257
+    feat, conf = enc.encode(src, tgt, m_dev=torch.tensor([live], dtype=torch.int32, device="cuda"), poison=0xFF)
+    assert enc.last_info == dict(status=0, m=live, dead=0)
+    assert not feat[live:].any() and not conf[live:].any()
+    f1, c1 = enc.encode(src[:live], tgt[:live])
+    assert torch.equal(feat[:live], f1) and torch.equal(conf[:live], c1)
+    sd = pdsc_cases.shared_weights(12)
+    f64, c64 = pdsc_cpu.encode(src, tgt, sd, 12, SIGMA, np.float64, m=live)
+    check("m_dev 257 of 2 048", host(feat[:live]), host(conf[:live]), f64, c64, live_bound(src[:live], tgt[:live], sd, 12, SIGMA, f64, c64))
+
+
+def _untouched(t):
+    return bool((t == -1.0).all())
+
+
+def test_null_outputs_single_call():
+    """feat_out or conf_out NULL: the other output has the bits of the call that asks for both; nothing is stored for the one not asked for."""
+    enc = encoder()
+    (src, tgt), _, _, _ = yardstick("planted", 700)
+    f, c = enc.encode(src, tgt)
+    _, c1 = enc.encode(src, tgt, want_feat=False)
+    assert enc.last_info == dict(status=0, m=700, dead=0) and torch.equal(c1, c) and _untouched(enc.last_raw[0][0])
+    f2, _ = enc.encode(src, tgt, want_conf=False)
+    assert enc.last_info == dict(status=0, m=700, dead=0) and torch.equal(f2, f) and _untouched(enc.last_raw[1][0])
+    enc.encode(src, tgt, want_feat=False, want_conf=False)
+    assert enc.last_info == dict(status=0, m=700, dead=0) and _untouched(enc.last_raw[0][0]) and _untouched(enc.last_raw[1][0])
+
+
+def test_null_outputs_in_a_batch():
+    """NULL entries of feat_out / conf_out, and NULL for either array as a whole."""
+    enc = encoder()
+    ms = (129, 700, 63)
+    cases = [yardstick("planted", m)[0] for m in ms]
+    srcs, tgts = [c[0] for c in cases], [c[1] for c in cases]
+    both = enc.encode_batch(srcs, tgts)
+    for wf, wc in (([True, False, True], [False, True, True]), (False, None), (None, False), ([False, False, False], [True, False, True])):
+        out = enc.encode_batch(srcs, tgts, want_feat=wf, want_conf=wc, poison=0xFF)
+        feats, confs = enc.last_raw
+        for k, m in enumerate(ms):
+            assert out[k][2] == dict(status=0, m=m, dead=0)
+            if wf is None or (wf is not False and wf[k]):
+                assert torch.equal(out[k][0], both[k][0]), (wf, k)
+            else:
+                assert _untouched(feats[k]), (wf, k)
+            if wc is None or (wc is not False and wc[k]):
+                assert torch.equal(out[k][1], both[k][1]), (wc, k)
+            else:
+                assert _untouched(confs[k]), (wc, k)
+
+
+@pytest.mark.parametrize("sigma_d", (float(np.float32(0.05)), float(np.float32(50.0))))
+def test_sigma_d(sigma_d):
+    """sigma_d = 0.05: 97.5 % of the compatibilities are 0, their logits 0 and the softmax close to uniform; 50: 93 % are positive, 45 %
+    above 0.9 (1.2 leaves 7-9 %): the largest logits.  m = 257, 2 layers."""
+    (src, tgt), f64, c64, bounds = yardstick("planted", 257, 1.0, 2, sigma_d)
+    Cm = pdsc_cpu.compat(src, tgt, sigma_d)
+    off = Cm[~np.eye(257, dtype=bool)]
+    print(f"sigma_d {sigma_d}: {np.mean(off == 0):.4f} of the compatibilities are 0, {np.mean(off > 0.9):.4f} above 0.9")
+    assert np.mean(off == 0) > 0.95 if sigma_d < 1 else np.mean(off > 0) > 0.9
+    feat, conf = encoder(2, 1.0, sigma_d).encode(src, tgt)
+    check(f"sigma_d {sigma_d}", host(feat), host(conf), f64, c64, bounds)
+
+
+def test_sixteen_layers():
+    (src, tgt), f64, c64, bounds = yardstick("planted", 129, 1.0, 16)
+    feat, conf = encoder(16).encode(src, tgt)
+    check("16 layers, m = 129", host(feat), host(conf), f64, c64, bounds)
+
+
+def test_large_logits_across_eight_tiles_per_chunk():
+    """scale = 3 on the q and k projections (logits 9 x larger) at m = 2 048: a chunk is 8 tiles behind one running maximum."""
+    assert pdsc_cpu.plan(2048) == (16, 8, 256)
+    (src, tgt), f64, c64, bounds = yardstick("planted", 2048, 3.0)
+    feat, conf = encoder(12, 3.0).encode(src, tgt)
+    check("planted 2 048, scale 3", host(feat), host(conf), f64, c64, bounds)
+
+
+def test_call_can_be_captured_into_a_graph():
+    """No host synchronisation, no allocation, the live count read on the device: one lr_pdsc_encode (m = 700, an m_dev buffer) recorded
+    once on a side stream and replayed on other coordinates and other live counts -- 700, 129, 0 -- gives the bytes of the eager calls,
+    whatever the scratch held."""
+    L = _ext.lib()
+    enc = encoder()
+    m = 700
+    configs = [(pdsc_cases.planted(m, seed=s), live) for s, live in ((1, 700), (2, 129), (3, 0))]
+    src = torch.empty((m, 3), dtype=torch.float32, device="cuda"); tgt = torch.empty_like(src)
+    m_dev = torch.empty(1, dtype=torch.int32, device="cuda")
+    feat = torch.empty((m, 128), dtype=torch.float32, device="cuda"); conf = torch.empty(m, dtype=torch.float32, device="cuda")
+    res = torch.zeros(ctypes.sizeof(_ext.PdscResult), dtype=torch.uint8, device="cuda")
+    sc = torch.empty(L.lr_pdsc_scratch_bytes(m), dtype=torch.uint8, device="cuda")
+    s = torch.cuda.Stream()
+
+    def call():
+        _ext.check(L.lr_pdsc_encode(src.data_ptr(), tgt.data_ptr(), m, m_dev.data_ptr(), enc.weights.data_ptr(), enc.weights.numel() * 4,
+                                    ctypes.byref(enc.params), res.data_ptr(), feat.data_ptr(), conf.data_ptr(), sc.data_ptr(), sc.numel(), s.cuda_stream))
+
+    def load(cfg, poison):
+        (a, b), live = cfg
+        src.copy_(torch.from_numpy(a)); tgt.copy_(torch.from_numpy(b)); m_dev.fill_(live)
+        feat.fill_(7.0); conf.fill_(7.0); res.fill_(0x55); sc.fill_(poison)
+        torch.cuda.synchronize()
+
+    def outputs():
+        torch.cuda.synchronize()
+        return [x.cpu().numpy().tobytes() for x in (res, feat, conf)]
+    eager = []
+    for cfg in configs:
+        load(cfg, 0x00); call(); eager.append(outputs())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=s):
+        call()
+    for k, (cfg, want) in list(enumerate(zip(configs, eager)))[::-1] + [(0, (configs[0], eager[0]))]:
+        load(cfg, 0xFF if k & 1 else 0x00); g.replay()
+        assert outputs() == want, k
+    assert len(set(e[1] for e in eager)) == 3
+    # the eager calls are what the wrapper returns
+    for ((a, b), live), e in zip(configs, eager):
+        r = _ext.PdscResult.from_buffer_copy(e[0])
+        assert (r.status, r.m, r.dead) == (0 if live else 1, live, 0)
+        f = np.frombuffer(e[1], np.float32).reshape(m, 128); c = np.frombuffer(e[2], np.float32)
+        assert not f[live:].any() and not c[live:].any()
+        if live:
+            f1, c1 = enc.encode(a[:live], b[:live])
+            assert np.array_equal(f[:live], host(f1)) and np.array_equal(c[:live], host(c1))

@@ -1,5 +1,7 @@
 """The yardsticks of the PointDSC encoder, without a GPU: the numpy restatement (tests/pdsc_cpu.py) against what the reference's own model
-returned (tests/golden/g24_pdsc.npz), rule E1 by hand, the state-dict packing, the refusals and the size functions of the C ABI."""
+returned (tests/golden/g24_pdsc.npz), rule E1 by hand, the state-dict packing, the refusals and the size functions of the C ABI; the
+slabbed and the tiled restatement that reach m = 32 768, the attention plan and the scratch layout over every m, and the recorded large
+cases (tests/golden/g25_pdsc_large.npz)."""
 import ctypes
 import os
 import re
@@ -233,3 +235,118 @@ def test_scratch_bytes_is_linear_in_m():
         if 2 * m <= 32768:
             assert f(2 * m) <= 2 * f(m) + f(0), m
     assert f(32768) <= 32768 * 5500 + f(0)                                   # no M x M term: a few KB per correspondence
+
+
+# ---- the restatements that reach m = 32 768, the plan and the layout ----------------------------------------------------------------
+def _slab_case(kind, m):
+    return getattr(pdsc_cases, kind)(m)[:2]
+
+
+@pytest.mark.parametrize("kind,m", (("planted", 1), ("planted", 33), ("planted", 257), ("planted", 1000), ("nonfinite", 300)))
+def test_slabbed_equals_the_whole_matrix_restatement(kind, m):
+    """The same formulas per slab of query rows: 1e-12 abs in fp64 (another blocking of the same matrix products), 2 layers; the default
+    slab of 512 and one that divides nothing."""
+    src, tgt = _slab_case(kind, m)
+    sd = pdsc_cases.shared_weights(2)
+    f, c = pdsc_cpu.encode(src, tgt, sd, 2, pdsc_cases.SIGMA_D)
+    dead = ~pdsc_cpu.live_rows(src, tgt)
+    assert dead.any() == (kind == "nonfinite")
+    for slab in (512, 96):
+        fs, cs = pdsc_cpu.encode_slabbed(src, tgt, sd, 2, pdsc_cases.SIGMA_D, slab=slab)
+        df, dc = np.abs(fs - f).max(), np.abs(cs[~dead] - c[~dead]).max()
+        print(f"{kind} {m}, slab {slab}: slabbed vs whole, fp64: features {df:.2e}, confidence {dc:.2e}")
+        assert df <= 1e-12 and dc <= 1e-12
+        assert not fs[dead].any() and (cs[dead] == -np.inf).all() and np.isfinite(cs[~dead]).all()
+    f32, c32 = pdsc_cpu.encode_slabbed(src, tgt, sd, 2, pdsc_cases.SIGMA_D, dtype=np.float32)
+    assert f32.dtype == np.float32 and c32.dtype == np.float32 and f32.shape == f.shape
+
+
+@pytest.mark.parametrize("m", (257, 1000))
+def test_tiled32_is_a_valid_fp32_evaluation(m):
+    """The fp32 restatement in the contract's order (E6) on two golden cases: within the rule the device is held to, of the fp64 one."""
+    c = pdsc_cases.golden_case(m, 12)
+    f64, c64 = pdsc_cpu.golden_reference(m, 12)
+    ft, ct = pdsc_cpu.encode_tiled32(c["src"], c["tgt"], c["sd"], 12, pdsc_cases.SIGMA_D)
+    assert ft.dtype == np.float32 and ct.dtype == np.float32
+    rf, rc = float(GOLD[c["name"] + "/dev_feat"]), float(GOLD[c["name"] + "/dev_conf"])
+    bf, bc = pdsc_cpu.bound(rf, rc, f64, c64)
+    df, dc = np.abs(ft - f64).max(), np.abs(ct - c64).max()
+    print(f"{c['name']}: tiled fp32 vs fp64: features {df:.2e} of {bf:.2e} allowed ({df / rf:.2f} x the reference's own), confidence {dc:.2e} of {bc:.2e} ({dc / rc:.2f} x)")
+    assert df <= bf and dc <= bc
+
+
+def test_tiled32_evaluates_the_live_rows_as_a_set_of_their_own():
+    """encode_tiled32 evaluates the live rows as a set of their own, as encode() does."""
+    src, tgt, bad = pdsc_cases.nonfinite(70)
+    sd = pdsc_cases.shared_weights(1)
+    keep = np.setdiff1d(np.arange(70), bad)
+    f, c = pdsc_cpu.encode_tiled32(src, tgt, sd, 1, pdsc_cases.SIGMA_D)
+    f2, c2 = pdsc_cpu.encode_tiled32(src[keep], tgt[keep], sd, 1, pdsc_cases.SIGMA_D)
+    assert np.array_equal(f[keep], f2) and np.array_equal(c[keep], c2) and not f[bad].any() and (c[bad] == -np.inf).all()
+
+
+def test_plan_of_every_m():
+    """pd_make_plan restated, every m of the contract: at least one chunk, no chunk empty, whole tiles per chunk, and no live count
+    m <= mx asks for more blocks than the launch of a call with largest m = mx has (pd_max_blocks)."""
+    most, first = 0, {}
+    for m in range(0, pdsc_cpu.MAX_M + 1):
+        nb, chunks, per = pdsc_cpu.plan(m)
+        assert nb == max(1, -(-m // 128))
+        assert 1 <= chunks <= 8, m
+        assert (chunks - 1) * per < max(m, 1) <= chunks * per, m
+        assert per % 32 == 0 and per > 0, m
+        most = max(most, nb * chunks)
+        assert most <= pdsc_cpu.max_blocks(m) <= 512, m
+        if m > 8192:
+            first.setdefault(chunks, m)
+    assert all(pdsc_cpu.plan(m)[1] == 8 for m in range(7 * 1024 + 1, 8193)) and all(pdsc_cpu.plan(m)[1] < 8 for m in range(8193, 32769))
+    assert first == {7: 8193, 6: 9345, 5: 10881, 4: 13057, 3: 16385, 2: 21761}
+    assert pdsc_cpu.plan(8193) == (65, 7, 1184) and pdsc_cpu.plan(32768) == (256, 2, 16384)
+    assert pdsc_cpu.plan(8192) == (64, 8, 1024) and pdsc_cpu.max_blocks(8192) == 512 and 65 * 7 == 455
+    assert pdsc_cpu.plan(320) == (3, 5, 64) and pdsc_cpu.plan(257) == (3, 5, 64) and pdsc_cpu.plan(2048) == (16, 8, 256)
+
+
+def test_layout_restated_is_the_c_librarys():
+    """pd_make_layout restated (with it pd_max_blocks, which sizes the partials) against lr_pdsc_scratch_bytes, every m."""
+    f = _ext.lib().lr_pdsc_scratch_bytes
+    assert all(pdsc_cpu.scratch_bytes(m) == f(m) for m in range(0, pdsc_cpu.MAX_M + 1))
+    assert pdsc_cpu.scratch_bytes(32768) == 256 + 32768 * 3652 + 65536 * 520
+
+
+# ---- the recorded large cases (tests/golden/make_golden_pdsc_large.py) ----------------------------------------------------------------
+LARGE_PATH = os.path.join(ROOT, "tests", "golden", "g25_pdsc_large.npz")
+LARGE_IDS = [pdsc_cases.golden_name(m, L) for m, L in pdsc_cases.LARGE]
+
+
+def test_large_is_the_set_of_plans_and_stays_small():
+    assert set(pdsc_cases.LARGE) == {(8192, 1), (8193, 1), (9345, 1), (13057, 1), (16385, 1), (21761, 1), (32768, 1), (10881, 12)}
+    assert len(pdsc_cases.LARGE) == 8
+    assert sorted(pdsc_cpu.plan(m)[1] for m, _ in pdsc_cases.LARGE) == [2, 2, 3, 4, 5, 6, 7, 8]
+    assert os.path.getsize(LARGE_PATH) < os.path.getsize(os.path.join(ROOT, "tests", "golden", "g12_full_30k.npz"))
+    with np.load(LARGE_PATH) as g:
+        assert sorted(g.files) == sorted(f"{n}/{k}" for n in LARGE_IDS for k in ("sha256", "feat", "conf", "d32_feat", "d32_conf", "d32t_feat", "d32t_conf"))
+
+
+def test_conf_rows_take_four_rows_of_every_query_block():
+    for m in (1, 127, 129, 8192, 8193, 32768):
+        rows = pdsc_cases.conf_rows(m)
+        assert rows[-1] == m - 1 and (np.diff(rows) > 0).all() and rows[0] >= 0
+        for b in range(-(-m // 128)):
+            want = [r for r in (128 * b + (37 * b + 32 * w) % 128 for w in range(4)) if r < m]
+            assert set(want) <= set(rows.tolist())
+            if 128 * (b + 1) <= m:
+                assert sorted((r % 128) // 32 for r in want) == [0, 1, 2, 3]             # one row per wave
+    assert len({int(r) % 32 for r in pdsc_cases.conf_rows(8192)}) == 32                    # every lane
+
+
+@pytest.mark.parametrize("m,num_layers", pdsc_cases.LARGE, ids=LARGE_IDS)
+def test_large_fixture_belongs_to_these_inputs(m, num_layers):
+    c = pdsc_cases.large_case(m, num_layers)
+    with np.load(LARGE_PATH) as g:
+        n = c["name"]
+        assert str(g[n + "/sha256"]) == pdsc_cases.checksum(c), "tests/pdsc_cases.py changed: regenerate with tests/golden/make_golden_pdsc_large.py"
+        feat, conf = g[n + "/feat"], g[n + "/conf"]
+        assert feat.shape == (32, 128) and feat.dtype == np.float64 and conf.shape == (len(pdsc_cases.conf_rows(m)),) and conf.dtype == np.float64
+        assert np.isfinite(feat).all() and np.isfinite(conf).all()
+        for k in ("d32_feat", "d32_conf", "d32t_feat", "d32t_conf"):
+            assert np.isfinite(g[f"{n}/{k}"]) and float(g[f"{n}/{k}"]) > 0.0, k
