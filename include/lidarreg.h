@@ -111,7 +111,9 @@ typedef struct lr_pair_result {
     double   T_ransac[16];  /* winning minimal-sample model before the refit                          */
     lr_ransac_result ransac;
     int32_t  n_corr;        /* correspondences after filtering (num_pairs_filtered, FR.py:60)         */
-    int32_t  n_refit;       /* inliers used by the refit (FR.py:104-108)                              */
+    int32_t  n_refit;       /* inliers used by the refit (FR.py:104-108): the NUMBER of pairs within refit_thr2 of T_ransac, also under the
+                               weights of refit = 3 (not their weight sum) and when the refit left T = T_ransac (unweighted: fewer than 3
+                               of them); 0 when there was no model (status 1)                          */
     int32_t  n_nn_fixed;    /* NN rows/cols that needed the exact sqrt tie-break path                 */
     int32_t  status;        /* 0 ok, 1 = no valid hypothesis (T = identity, GC_RANSAC.py:51-52)       */
     int32_t  reserved[8];   /* [0]: diagnostic, like n_nn_fixed -- (model, correspondence) evaluations of the scoring passes in ppm of
@@ -213,7 +215,8 @@ LR_API int lr_gpf_bb_first(lr_workspace *ws, const float *F0, int n0, const floa
 /* ---- a10/a12: RANSAC over M correspondences src[i] <-> tgt[i]  ([M,3] float32 each) ---------------
  * Replaces pygcransac.findRigidTransform(x1y1z1, x2y2z2, ...) (GC_RANSAC.py:46-49; native side
  * gcransac_python.cpp:404-416) and o3d registration_ransac_based_on_correspondence (FR.py:128-137).
- * m_dev, if not NULL, is a device int32 holding the live M (<= m).  Writes T_out[16] and *res.    */
+ * m_dev, if not NULL, is a device int32 holding the live M (<= m).  Writes T_out[16] and *res, and leaves a copy of the model on
+ * the workspace, where lr_inlier_mask(T = NULL) reads it (one device-to-device copy of 128 bytes on the call's stream).          */
 LR_API int lr_ransac(lr_workspace *ws, const float *src, const float *tgt, int m, const int32_t *m_dev,
                      const lr_ransac_params *p, double *T_out, lr_ransac_result *res, void *stream);
 
@@ -227,7 +230,9 @@ LR_API int lr_inlier_mask(lr_workspace *ws, const float *src, const float *tgt, 
 LR_API int lr_workspace_mask_at(lr_workspace *ws, int pair, const float *xyz0, const float *xyz1, int n0, float thr2,
                                 uint8_t *mask, int32_t *n_inliers, void *stream);
 
-/* ---- a11: LS refit on the original NN pairs within thr of T_in  (FR.py:99-111) -------------------- */
+/* ---- a11: LS refit on the original NN pairs within thr of T_in  (FR.py:99-111) --------------------
+ * Pairs (i, idx1[i]), i < n0, with |T_in xyz0[i] - xyz1[idx1[i]]|^2 < thr2 (fp64, strict) are the inliers; a row with idx1[i] < 0
+ * has no partner and is skipped.  *n_inliers (device, may be NULL) = their number; T_out = T_in when there are fewer than 3.  */
 LR_API int lr_refit(lr_workspace *ws, const float *xyz0, int n0, const float *xyz1, const int32_t *idx1,
                     const double *T_in, double thr2, double *T_out, int32_t *n_inliers, void *stream);
 

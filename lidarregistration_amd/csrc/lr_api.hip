@@ -563,7 +563,10 @@ extern "C" int lr_ransac(lr_workspace *ws, const float *src, const float *tgt, i
     LR_REQUIRE(m >= 0 && m <= ws->max_n0, LR_ESIZE, "lr_ransac: m exceeds the workspace");
     const lr_call c = lr_call_single(ws, stream);
     LR_TRY(lr_pack_corr(c, src, tgt, nullptr, nullptr, m, m_dev, ws->corr8));
-    return lr_ransac_run(c, ws->corr8, m, m_dev, p, T_out, res);
+    LR_TRY(lr_ransac_run(c, ws->corr8, m, m_dev, p, T_out, res));
+    // lr_inlier_mask(T = NULL) reads the model of the last call from the workspace (lr_register_pair leaves it there itself)
+    if (T_out != ws->T_tmp) LR_HIP(hipMemcpyAsync(ws->T_tmp, T_out, 16 * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return LR_OK;
 }
 
 // the inlier mask pygcransac returns next to the pose (gcransac_python.cpp:594-603)

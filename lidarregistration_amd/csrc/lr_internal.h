@@ -190,7 +190,7 @@ struct lr_workspace {
     float *models2; double *models64_2; int32_t *model_h2;   // the same three for the models that survived the SPRT pre-verification
     uint32_t *score_cnt;         // [max_iters]
     unsigned long long *score_ssq; // [max_iters]
-    double *refit_part;          // [blocks][16] moment partials
+    double *refit_part;          // [blocks][16] moment partials, then [blocks] inlier counts (blocks of 1024 pairs: 17 per block fit the 64 allocated)
     int32_t *lo_list;            // [max_n0] inlier list of the model under local optimisation
     void *lo_ctl;                // lr_lo_ctl (LR_LO_CTL_BYTES): jobs the master block of a local optimisation publishes for its helper blocks
     // pilot-ordered scoring (lr_score.hip): head / order passes -> main pass

@@ -58,19 +58,24 @@ __device__ void refit_solve_body(const double *__restrict__ partial, int nblocks
         __syncthreads();
     }
     if (threadIdx.x < 16) mom[threadIdx.x] = acc;
+    // n_refit counts the inlier pairs (lidarreg.h); mom[0] is their weight sum, which is that count only when every weight is 1
+    __shared__ int cnt_w[4];
+    int cnt = 0;
+    for (int b = threadIdx.x; b < nblocks; b += blockDim.x) cnt += (int)partial[(size_t)nblocks * 16 + b];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m);
+    if ((threadIdx.x & 63) == 0) cnt_w[threadIdx.x >> 6] = cnt;
     __syncthreads();
     if (threadIdx.x != 0) return;
+    const int count = cnt_w[0] + cnt_w[1] + cnt_w[2] + cnt_w[3];
     const bool have_model = gate ? gate->best_h >= 0 : true;
     const double n = mom[0];
     double T[16];
-    int n_used;
-    if (!have_model || !(n > 0.0) || (!weighted && n < 3.0)) {
+    if (!have_model || !(n > 0.0) || (!weighted && n < 3.0))
         for (int k = 0; k < 16; ++k) T[k] = T_in[k];
-        n_used = have_model ? (int)n : 0;
-    } else {
+    else
         lr_rt_from_moments(mom, T);
-        n_used = (int)n;
-    }
+    const int n_used = have_model ? count : 0;
     for (int k = 0; k < 16; ++k) T_out[k] = T[k];
     if (n_inl) *n_inl = n_used;
     if (pair_out) {          // result block of lr_register_pair (fused: saves a launch)
@@ -95,7 +100,8 @@ __device__ void refit_solve_body(const double *__restrict__ partial, int nblocks
 
 // ------------------------------------------------------------------ refit (FR.py:99-111)
 #define LR_REFIT_PER 4
-// partial[b][0] = n, [1..3] = sum p, [4..6] = sum q, [7..15] = sum p q^T over the inliers of block b
+// partial[b][0] = n, [1..3] = sum p, [4..6] = sum q, [7..15] = sum p q^T over the inliers of block b (n: their weight sum);
+// behind the gridDim.x moment rows, partial[16 gridDim.x + b] = the number of inliers of block b
 __global__ void __launch_bounds__(256)
 refit_moments_kernel(const float *__restrict__ xyz0, int n0, const float *__restrict__ xyz1, const int32_t *__restrict__ idx1,
                      const double *__restrict__ T_in, double thr2, double *__restrict__ partial,
@@ -105,6 +111,7 @@ refit_moments_kernel(const float *__restrict__ xyz0, int n0, const float *__rest
                      int32_t *__restrict__ n_inl, lr_pair_result *__restrict__ pair_out, const int32_t *__restrict__ counters, lr_zargs z)
 {
     __shared__ double sm[4][16];
+    __shared__ int s_cnt[4];
     __shared__ int s_last;
     if (z.descs) {
         const lr_pair_desc d = z.descs[blockIdx.z];
@@ -119,6 +126,7 @@ refit_moments_kernel(const float *__restrict__ xyz0, int n0, const float *__rest
     double v[16];
 #pragma unroll
     for (int k = 0; k < 16; ++k) v[k] = 0.0;
+    int cnt = 0;
     // pairs (i, idx1[i]) over all n0 rows, or -- with idx0 -- the listed pairs (idx0[c], idx1[c]), c < *m_dev
     if (m_dev) n0 = min(n0, *m_dev);
     // LR_REFIT_PER pairs per thread (the 16 fp64 wave reductions below cost far more than a pair's moments: one pair per thread spent
@@ -151,7 +159,7 @@ refit_moments_kernel(const float *__restrict__ xyz0, int n0, const float *__rest
                 for (int k = 0; k < 32; ++k) { const float e = fa[k] - fb[k]; const float q2 = e * e; acc = acc + q2; }
                 w = 1.0 / (double)fmaxf(__builtin_sqrtf(acc), 1e-12f);
             }
-            v[0] += w;
+            v[0] += w; cnt += 1;
 #pragma unroll
             for (int a = 0; a < 3; ++a) { v[1 + a] += w * p[a]; v[4 + a] += w * q[a]; }
 #pragma unroll
@@ -168,9 +176,14 @@ refit_moments_kernel(const float *__restrict__ xyz0, int n0, const float *__rest
         for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
         if (lane == 0) sm[wave][k] = s;
     }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cnt += __shfl_xor(cnt, m);
+    if (lane == 0) s_cnt[wave] = cnt;
     __syncthreads();
     if (threadIdx.x < 16)
         partial[(size_t)blockIdx.x * 16 + threadIdx.x] = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+    if (threadIdx.x == 16)
+        partial[(size_t)gridDim.x * 16 + blockIdx.x] = (double)(s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);
     // ---- last block done: agent-scope release of the partials, ticket, acquire, then the solve (saves a launch)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();

@@ -59,17 +59,46 @@ def ransac_dev(src, tgt, iters, sample_size=3, use_elc=True, thr=0.6, seed=DEFAU
     return T.cpu().numpy().reshape(4, 4), info
 
 
-def refit_dev(xyz0, xyz1, idx1, T, thr=0.6):
-    """FR.py:99-111: LS refit over the original NN pairs within thr of T.  Returns (T 4x4, n_inliers)."""
+def refit_dev(xyz0, xyz1, idx1, T, thr=0.6, thr2=None, ws=None):
+    """FR.py:99-111: LS refit over the original NN pairs within thr of T (thr2: the fp64 squared threshold itself instead of thr * thr).
+    Returns (T 4x4, n_inliers).  The listed-pairs and weighted forms of the stage (lr_pair_params.refit 2 and 3) have no entry point
+    of their own: they run inside lr_register_pair / lr_register_batch (FR.register_pair_dev with params.refit set)."""
     xyz0, xyz1, idx1 = _f32(xyz0), _f32(xyz1), _i32(idx1)
     n0 = xyz0.shape[0]
-    ws = workspace(n0, 1)
+    if ws is None:
+        ws = workspace(n0, 1)
     Tin = torch.as_tensor(np.ascontiguousarray(T, np.float64).reshape(16)).to(xyz0.device)
     Tout = torch.empty(16, dtype=torch.float64, device=xyz0.device)
     n = torch.zeros(1, dtype=torch.int32, device=xyz0.device)
     _ext.check(_ext.lib().lr_refit(ws.handle, xyz0.data_ptr(), n0, xyz1.data_ptr(), idx1.data_ptr(), Tin.data_ptr(),
-                                    float(thr) * float(thr), Tout.data_ptr(), n.data_ptr(), _stream()))
+                                    float(thr) * float(thr) if thr2 is None else float(thr2), Tout.data_ptr(), n.data_ptr(), _stream()))
     return Tout.cpu().numpy().reshape(4, 4), int(n.item())
+
+
+def inlier_mask_dev(src, tgt, T, thr2, ws=None, fill=0, room=None):
+    """lr_inlier_mask over the pairs src[c] <-> tgt[c] ([m,3] float32) with float32(thr2).  T: a 4x4 transform, or None for the model
+    the last lr_ransac / lr_register_pair left on `ws`.  The mask buffer has `room` bytes (default m) and starts out as `fill`.
+    Returns (the whole buffer as uint8 numpy: its first m bytes are the mask, n_inliers)."""
+    src, tgt = _f32(src), _f32(tgt)
+    m = src.shape[0]
+    Td = None if T is None else torch.as_tensor(np.ascontiguousarray(T, np.float64).reshape(16)).to(src.device)
+    mask = torch.full((max(m, 1) if room is None else int(room),), int(fill), dtype=torch.uint8, device=src.device)
+    nin = torch.zeros(1, dtype=torch.int32, device=src.device)
+    _ext.check(_ext.lib().lr_inlier_mask(None if ws is None else ws.handle, src.data_ptr(), tgt.data_ptr(), m, None if Td is None else Td.data_ptr(),
+                                          ctypes.c_float(thr2), mask.data_ptr(), nin.data_ptr(), _stream()))
+    return mask.cpu().numpy(), int(nin.item())
+
+
+def mask_at_dev(ws, pair, xyz0, xyz1, thr2, fill=0):
+    """lr_workspace_mask_at: the mask over the filtered pairs of pair `pair` of the last lr_register_pair / lr_register_batch on `ws`, under
+    that pair's RANSAC model.  xyz0, xyz1: the pair's float32 device clouds.  Returns (uint8 [n0] numpy, prefilled with `fill`: the first
+    n_corr bytes are the mask; n_inliers)."""
+    n0 = xyz0.shape[0]
+    mask = torch.full((n0,), int(fill), dtype=torch.uint8, device=xyz0.device)
+    nin = torch.zeros(1, dtype=torch.int32, device=xyz0.device)
+    _ext.check(_ext.lib().lr_workspace_mask_at(ws.handle, int(pair), xyz0.data_ptr(), xyz1.data_ptr(), n0, ctypes.c_float(thr2),
+                                                mask.data_ptr(), nin.data_ptr(), _stream()))
+    return mask.cpu().numpy(), int(nin.item())
 
 
 def icp_launch(ws, xyz0, xyz1, T_ptr, stream, max_dist=0.6, max_iter=30, rel_fitness=1e-6, rel_rmse=1e-6):

@@ -360,19 +360,32 @@ def ransac(src, tgt, iters, sample_size=3, use_elc=True, thr=0.6, seed=51, confi
     return T.reshape(4, 4), dict(best_h=r.best_h, best_count=r.best_count, best_ssq=r.best_ssq, n_valid=r.n_valid, n_ids=r.n_ids)
 
 
-def refit(xyz0, xyz1, idx1, T, thr=0.6, feats0=None, feats1=None):
-    """FR.py:99-111 (with feats: DGR's inverse-feature-distance weighted form).  Returns (T 4x4 float64, inlier count)."""
-    xyz0, xyz1, idx1 = _f32(xyz0), _f32(xyz1), _i32(idx1)
+def refit(xyz0, xyz1, idx1, T, thr=0.6, feats0=None, feats1=None, thr2=None):
+    """FR.py:99-111 (with feats: DGR's inverse-feature-distance weighted form).  Returns (T 4x4 float64, inlier count).  thr2: the fp64
+    squared threshold itself instead of thr * thr."""
+    xyz0, xyz1, idx1 = _f32(xyz0).reshape(-1, 3), _f32(xyz1).reshape(-1, 3), _i32(idx1)
+    thr2 = float(thr) * float(thr) if thr2 is None else float(thr2)
     Tin = np.ascontiguousarray(T, np.float64).reshape(16)
     Tout = np.empty(16, np.float64)
     if feats0 is not None:
-        F0, F1 = _f32(feats0), _f32(feats1)
+        # orc_refit_weighted reads rows of 32 floats: narrower descriptors are zero-padded, as the library pads them (pad_feats_kernel)
+        F0, F1 = (_f32(np.pad(np.asarray(f, np.float32), ((0, 0), (0, 32 - np.shape(f)[1])))) for f in (feats0, feats1))
         n = lib().orc_refit_weighted(_p(xyz0, c_f32p), xyz0.shape[0], _p(xyz1, c_f32p), _p(idx1, c_i32p), _p(Tin, c_f64p),
-                                     ctypes.c_double(float(thr) * float(thr)), _p(Tout, c_f64p), _p(F0, c_f32p), _p(F1, c_f32p))
+                                     ctypes.c_double(thr2), _p(Tout, c_f64p), _p(F0, c_f32p), _p(F1, c_f32p))
         return Tout.reshape(4, 4), n
     n = lib().orc_refit(_p(xyz0, c_f32p), xyz0.shape[0], _p(xyz1, c_f32p), _p(idx1, c_i32p),
-                        _p(Tin, c_f64p), ctypes.c_double(float(thr) * float(thr)), _p(Tout, c_f64p))
+                        _p(Tin, c_f64p), ctypes.c_double(thr2), _p(Tout, c_f64p))
     return Tout.reshape(4, 4), n
+
+
+def inlier_mask(src, tgt, T, thr2):
+    """lr_inlier_mask: (mask bool [m], count) of the pairs src[c] <-> tgt[c] with lr_score_d2 under float32(T) below float32(thr2)."""
+    src, tgt = _f32(src), _f32(tgt)
+    Tin = np.ascontiguousarray(T, np.float64).reshape(16)
+    mask = np.zeros(max(src.shape[0], 1), np.uint8)
+    n = lib().orc_inlier_mask(_p(src, c_f32p), _p(tgt, c_f32p), src.shape[0], _p(Tin, c_f64p), ctypes.c_float(np.float32(thr2)),
+                              mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    return mask[:src.shape[0]].astype(bool), n
 
 
 # ----------------------------------------------------------------------------- ICP (f1)
