@@ -219,7 +219,12 @@ nn16_passb_kernel(lr_pb_tail tail_first /* read at the end only, through lr_pb_t
         if (tau) s_Y[tid] = rw < na ? 0.5f * tau[rw] : -LR_INF;          // rows past the end never pass the test
         else {
             // ---- phase 1: every sstride-th tile of the strip, rows on the lanes
-            const int sstride = thr.sstride;
+            // (a batched call's stride is planned for its LARGEST column cloud.  A pair with fewer tiles takes what lr_nn16_plan_fwd's rule
+            // gives its own strip, never more than the call's: at the call's stride a strip of a few tiles is sampled once or not at all,
+            // fewer than `need` samples are no threshold, every column is a candidate, the segments overflow and the exact stage re-does
+            // the wave's rows by the full scan -- 119 552 of the 196 609 rows of a 300-column pair next to a 2^21-column one)
+            int sstride = thr.sstride;
+            if (z.descs) sstride = min(sstride, max(pg.gy > 1 ? min(ntiles >> 6, 16) : min((t_end - t_begin) >> 5, 32), 1));
             const int nsamp = t_end > t_begin ? (t_end - t_begin + sstride - 1) / sstride : 0;     // tiles this block samples
             const int nsch = (nsamp + CH - 1) / CH;
             constexpr bool P1E = SIGN;      // (see fold() below)
