@@ -31,7 +31,7 @@ logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s", datefm
 
 # --algo -> the module of lidarregistration_amd whose eval_pairs runs it (a correspondence-set solver on corrset.eval_pairs); every other
 # --algo goes through the FR pipeline's engines (harness.eval_pairs / eval_pairs_serial)
-CORRSET_ENGINES = {"TEASER": "teaser", "SM": "sm"}
+CORRSET_ENGINES = {"TEASER": "teaser", "SM": "sm", "PointDSC": "pointdsc"}
 
 
 def str2bool(v):
@@ -51,7 +51,7 @@ def get_args(argv=None):
         world_size, rank, do_analysis = 1, 0, True
     p = argparse.ArgumentParser()
     p.add_argument("--dataset", type=str, default="synthetic", help="A, B, S, K, L (balanced sets) or synthetic")
-    p.add_argument("--algo", type=str, default="RANSAC", choices=["RANSAC", "TEASER", "SM"])
+    p.add_argument("--algo", type=str, default="RANSAC", choices=["RANSAC", "TEASER", "SM", "PointDSC"])
     p.add_argument("--codebase", type=str, default="GC", choices=["open3D", "GC"])
     p.add_argument("--mode", type=str, default="MNN", help="MNN (alias MMN), GPF or no_filter; with --algo TEASER: FAIL_TOLERANT or anything else")
     p.add_argument("--max_samples", type=int, default=None)
@@ -67,7 +67,10 @@ def get_args(argv=None):
     p.add_argument("--GC_LO", type=str2bool, default=True)
     p.add_argument("--SM_top_ratio", type=float, default=0.05, help="--algo SM: share of the correspondences kept as inliers (baseline_KITTI.py:52)")
     p.add_argument("--SM_iters", type=int, default=10, help="--algo SM: power iterations (baseline_3DMatch.py:41)")
+    p.add_argument("--chosen_snapshot", type=str, default="", help="--algo PointDSC: directory with config.json and models/model_best.pkl (the reference's snapshot layout)")
+    p.add_argument("--solver", type=str, default="SVD", choices=["SVD", "RANSAC"], help="--algo PointDSC: SVD; RANSAC is not built and is refused")
     # additions of this implementation
+    p.add_argument("--num_node", type=int, default=12000, help="--algo PointDSC: at most this many source points per pair (test.py:247)")
     p.add_argument("--num_pairs", type=int, default=32, help="synthetic: number of pairs")
     p.add_argument("--synthetic_n", type=int, default=30000, help="synthetic: points per cloud")
     p.add_argument("--seed", type=int, default=51)
@@ -79,6 +82,10 @@ def get_args(argv=None):
     p.add_argument("--icp", type=str2bool, default=True, help="refine by point-to-point ICP and fill stats columns 11-14 (test.py:183-193)")
     p.add_argument("--o3d_conf", type=float, default=0.9995, help="confidence of the open3D codebase (FR.py:136)")
     args = p.parse_args(argv)
+    if args.algo == "PointDSC" and args.solver == "RANSAC":
+        p.error("--solver RANSAC is not built: --algo PointDSC fits by SVD")
+    if args.algo == "PointDSC" and not args.chosen_snapshot:
+        p.error("--algo PointDSC needs --chosen_snapshot DIR (DIR/config.json and DIR/models/model_best.pkl)")
     args.start_time, args.tmp_file_base, args.world_size, args.rank, args.do_analysis = start_time, tmp_file_base, world_size, rank, do_analysis
     from lidarregistration_amd import io_lists
     args.dataset_name = io_lists.DATASET_NAMES.get(args.dataset, args.dataset)

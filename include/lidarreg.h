@@ -668,7 +668,7 @@ LR_API int lr_balanced_select(const double *fields, const int32_t *session, cons
  * Replaces NonLocalNet (Experiments/models/PointDSC.py:9-77), the spatial-consistency matrix it attends with (:150-153) and the
  * classification head (:107-113, :171) in inference mode: a 128-d feature and an inlier logit per correspondence.  The M x M
  * matrices (compatibility, logits, softmax weights) are never stored.  Seed picking, the neural spectral matching, the per-seed fits
- * and post_refinement are not built.  Contract (restated in tests/pdsc_cpu.py):
+ * and post_refinement are p2 below.  Contract (restated in tests/pdsc_cpu.py):
  *  E1 a correspondence with a non-finite coordinate is dead (deviation: the reference propagates NaN into every output): its key gets
  *     weight 0 in every softmax, its feature is 0 and its confidence -inf, and it does not enter the mean of E2;
  *  E2 corr_pos = [src, tgt] - column mean over the live rows (demo_registration.py:107-108): the sums in fp64 (thread t of 1024 adds
@@ -724,6 +724,96 @@ LR_API int lr_pdsc_encode(const float *src, const float *tgt, int m, const int32
 LR_API int lr_pdsc_encode_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
                                 const float *weights, size_t weights_bytes, const lr_pdsc_params *p, lr_pdsc_result *results,
                                 float *const *feat_out, float *const *conf_out, void *scratch, size_t scratch_bytes, void *stream);
+
+/* ---- p2: PointDSC's tail: seeds, neural spectral matching, per-seed fits, hypothesis selection, post refinement ------------------
+ * Replaces pick_seeds (Experiments/models/PointDSC.py:199-217), cal_seed_trans (:234-336), cal_leading_eigenvector (:338-358) and
+ * post_refinement (:403-438) with rigid_transform_3d and knn of models/common.py:7-69, in inference mode, on the features and the
+ * confidence lr_pdsc_encode returns.  Contract (restated in tests/pdsc_solve_cpu.py); m = m_dev clamped to 0..m:
+ *  S1 a row is dead if E1 holds, if its conf is not finite or if its feature row holds a non-finite value; live = m - dead.  A dead row is
+ *     never a seed, never a neighbour, never counted; its label is 0 (deviation: the reference propagates NaN).
+ *  S2 local_max(i): for all live j, conf_i >= conf_j or |s_i - s_j| >= (float)nms_radius, the distance by E3's fp32 expression.
+ *     key_i = conf_i if local_max(i), else 0 (the reference's scores * is_local_max: a maximum of negative score sorts BEHIND the zeros).
+ *     Seeds: the first n_seeds live rows by descending key, ASCENDING INDEX ON EQUAL KEYS (the reference's argsort leaves ties open);
+ *     n_seeds = (int)((double)live * ratio), and 0 when live < 2.  n_seeds = 0: status 2, the identity, labels 0 (the reference raises).
+ *  S3 fn = f / max(|f|, 1e-12) in fp32 (F.normalize): |f| = sqrtf(t), t from p_l = f[2l] f[2l] + f[2l+1] f[2l+1], l = 0..63, by the
+ *     butterfly p_l = p_l + p_(l^d), d = 32, 16, 8, 4, 2, 1 (every l ends with the same value).
+ *  S4 per seed s: the k' = min(k, live - 1) live rows j != s of largest sim(s,j), by descending sim, ascending index on ties (deviation:
+ *     the reference takes k + 1 and drops the first, assuming it is s itself).  sim(s,j) in fp32: acc = 0; for c = 0..63:
+ *     acc = fmaf(fn_j[64+c], fn_s[64+c], fmaf(fn_j[c], fn_s[c], acc)) -- the chain of v_mfma_f32_32x32x2_f32.  No M x M or n_seeds x M
+ *     matrix is stored.
+ *  S5 per seed, over its neighbours a, b in S4's order, fp32: dot = fmaf chain of fn_a[c] fn_b[c] over c = 0..127 from 0;
+ *     M_ab = fmaxf(0, fmaf(1 - dot, (float)(-1 / sigma^2), 1)) * compat_E3(a, b), M_aa = 0.
+ *  S6 v = 1; num_iterations times (deviation: the reference leaves early when ALL seeds of the call pass allclose): u_a = fmaf chain of
+ *     M_ab v_b over ascending b from 0; v = u / (sqrtf(B(u u)) + 1e-6f), B the butterfly of S3 over the lanes a (0 past k').  Then
+ *     w = v / (B(v) + 1e-6f).
+ *  S7 fit (rigid_transform_3d, its + 1e-6 kept): fp64 on the fp32 inputs, every sum from 0 in ascending order of a:
+ *     W = sum w, ca = sum(w a) / (W + 1e-6), cb alike, H_xy = sum (w (a_x - ca_x)) (b_y - cb_y); R, t by lr_rt_from_cov (Horn's closed form
+ *     of lr_kabsch).  A rank-deficient H still gives a proper rotation -- an eigenvector of the largest eigenvalue of Horn's matrix, from the
+ *     Jacobi path; H = 0 gives R = I and t = cb - ca.
+ *  S8 count_s = #{live j : sqrt(dx dx + dy dy + dz dz) < inlier_threshold}, fp64 without fused multiply-add, d = (((R_x0 s_x + R_x1 s_y) +
+ *     R_x2 s_z) + t_x) - t_jx.  Best: the FIRST seed in seed order of largest count.  labels = that seed's inliers (final_labels).
+ *  S9 refinement, on the device: T = T_best, previous = 0; up to refine_iters rounds: residuals d by S8's expression, inliers d <
+ *     refine_threshold; their number equal to previous: stop; else previous = it, weights 1 / (1 + (d / refine_threshold)^2), S7's fit over
+ *     the inliers with every sum in the fixed tree of E2.
+ * S10 no floating-point atomics; the same input gives the same bits on every run, whatever the scratch held, alone or as pair k of a batch.
+ * The kNN's work plan (seed blocks of 128 x up to 8 chunks of keys) is a function of n_seeds and m alone and changes no result.          */
+typedef struct lr_pdsc_solve_params {
+    uint32_t struct_size;        /* = sizeof(lr_pdsc_solve_params)                                                                  */
+    int32_t  num_iterations;     /* 10 (PointDSC.py:94); 1..1000                                                                    */
+    int32_t  k;                  /* 40; 1..64                                                                                       */
+    int32_t  refine_iters;       /* 20 (:416-418); 0 = no refinement; 0..1000                                                       */
+    double   ratio;              /* 0.1; (0, 1]                                                                                     */
+    double   nms_radius;         /* 0.6 for Lidar; >= 0, finite                                                                     */
+    double   inlier_threshold;   /* 0.6; positive and finite                                                                        */
+    double   refine_threshold;   /* 1.2: what the reference hard-codes whenever its threshold is not 0.10 (:415-418)                */
+    double   sigma_d;            /* 1.2 (sigma_spat); positive and finite                                                           */
+    double   sigma;              /* 1.0: the state dict's learned `sigma`; positive and finite                                      */
+} lr_pdsc_solve_params;
+
+/* Written to device memory by lr_pdsc_solve / _batch / lr_pdsc_register / _batch (304 bytes). */
+typedef struct lr_pdsc_solve_result {
+    double   T[16];              /* src -> tgt, row-major, after the refinement                                                     */
+    double   T_best[16];         /* the best seed's transform, before it                                                            */
+    int32_t  status;             /* 0 ok, 1 = no live correspondence, 2 = no seed (T = T_best = the identity, labels 0)             */
+    int32_t  m;                  /* m_dev clamped to 0..m                                                                           */
+    int32_t  dead;               /* of those, dead rows (S1)                                                                        */
+    int32_t  n_seeds;
+    int32_t  best_rank;          /* position of the best seed in seed order, -1: none                                               */
+    int32_t  best_index;         /* its row, -1: none                                                                               */
+    int32_t  best_count;         /* its count (S8)                                                                                  */
+    int32_t  n_labels;           /* labels set                                                                                      */
+    int32_t  refine_rounds;      /* fits the refinement ran                                                                         */
+    int32_t  reserved[3];        /* 0                                                                                               */
+} lr_pdsc_solve_result;
+
+/* Caller-owned device scratch per pair for up to max_m correspondences (0 when max_m is outside 0..32768). */
+LR_API size_t lr_pdsc_solve_scratch_bytes(int max_m);
+/* feat [m,128] and conf [m]: device float32, what lr_pdsc_encode wrote.  labels_out (nullable, uint8 [m]): S8's labels, 0 at and past the
+ * live count.  seeds_out (nullable, int32 [(int)(m * ratio)]): the seeds in order, -1 at and past n_seeds.  Trace outputs of this entry
+ * only, all nullable, rows at and past n_seeds not written: knn_out int32 [n_seeds][k] (S4's order, -1 past k'), weight_out float32
+ * [n_seeds][k] (w of S6, 0 past k'), seedT_out float64 [n_seeds][16], count_out int32 [n_seeds].  Refusals: LR_EINVAL before any launch,
+ * lr_last_error naming the argument (struct_size, a parameter out of range, null feat / conf with m > 0, and the front end's).  No host
+ * synchronisation, no allocation: graph-capturable.                                                                                */
+LR_API int lr_pdsc_solve(const float *src, const float *tgt, int m, const int32_t *m_dev, const float *feat, const float *conf,
+                         const lr_pdsc_solve_params *p, lr_pdsc_solve_result *result, uint8_t *labels_out, int32_t *seeds_out,
+                         int32_t *knn_out, float *weight_out, double *seedT_out, int32_t *count_out, void *scratch, size_t scratch_bytes,
+                         void *stream);
+/* npairs (1..64) ragged pairs; the arrays are HOST arrays of length npairs (m_dev, labels_out, seeds_out and their entries may be NULL);
+ * scratch >= npairs * lr_pdsc_solve_scratch_bytes(max m).  Pair k is bit-identical to lr_pdsc_solve on that pair.                   */
+LR_API int lr_pdsc_solve_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
+                               const float *const *feat, const float *const *conf, const lr_pdsc_solve_params *p,
+                               lr_pdsc_solve_result *results, uint8_t *const *labels_out, int32_t *const *seeds_out, void *scratch,
+                               size_t scratch_bytes, void *stream);
+/* Encode, then solve, in one call on one scratch of npairs * lr_pdsc_register_scratch_bytes(max m) bytes: bit-identical to lr_pdsc_encode
+ * followed by lr_pdsc_solve.  feat_out / conf_out are nullable (the scratch holds them then).                                       */
+LR_API size_t lr_pdsc_register_scratch_bytes(int max_m);
+LR_API int lr_pdsc_register(const float *src, const float *tgt, int m, const int32_t *m_dev, const float *weights, size_t weights_bytes,
+                            const lr_pdsc_params *ep, const lr_pdsc_solve_params *sp, lr_pdsc_solve_result *result, float *feat_out,
+                            float *conf_out, uint8_t *labels_out, int32_t *seeds_out, void *scratch, size_t scratch_bytes, void *stream);
+LR_API int lr_pdsc_register_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
+                                  const float *weights, size_t weights_bytes, const lr_pdsc_params *ep, const lr_pdsc_solve_params *sp,
+                                  lr_pdsc_solve_result *results, float *const *feat_out, float *const *conf_out, uint8_t *const *labels_out,
+                                  int32_t *const *seeds_out, void *scratch, size_t scratch_bytes, void *stream);
 
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */

@@ -27,6 +27,8 @@ SYMBOLS = [
     "lr_bbrf_scratch_bytes", "lr_bbrf", "lr_normals_scratch_bytes", "lr_normals",
     "lr_balanced_select_scratch_bytes", "lr_balanced_select",
     "lr_pdsc_weights_bytes", "lr_pdsc_scratch_bytes", "lr_pdsc_encode", "lr_pdsc_encode_batch",
+    "lr_pdsc_solve_scratch_bytes", "lr_pdsc_solve", "lr_pdsc_solve_batch",
+    "lr_pdsc_register_scratch_bytes", "lr_pdsc_register", "lr_pdsc_register_batch",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -186,6 +188,23 @@ class PdscResult(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("m", ctypes.c_int32), ("dead", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class PdscSolveParams(KeywordParams):
+    """lr_pdsc_solve_params with the reference's Lidar settings (config.py, test.py:338-339, PointDSC.py:415-418) as defaults; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_iterations", ctypes.c_int32), ("k", ctypes.c_int32), ("refine_iters", ctypes.c_int32),
+                ("ratio", ctypes.c_double), ("nms_radius", ctypes.c_double), ("inlier_threshold", ctypes.c_double),
+                ("refine_threshold", ctypes.c_double), ("sigma_d", ctypes.c_double), ("sigma", ctypes.c_double)]
+    DEFAULTS = dict(num_iterations=10, k=40, refine_iters=20, ratio=0.1, nms_radius=0.6, inlier_threshold=0.6, refine_threshold=1.2,
+                    sigma_d=1.2, sigma=1.0)
+
+
+class PdscSolveResult(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_double * 16), ("T_best", ctypes.c_double * 16), ("status", ctypes.c_int32), ("m", ctypes.c_int32),
+                ("dead", ctypes.c_int32), ("n_seeds", ctypes.c_int32), ("best_rank", ctypes.c_int32), ("best_index", ctypes.c_int32),
+                ("best_count", ctypes.c_int32), ("n_labels", ctypes.c_int32), ("refine_rounds", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 3)]
+
+
+assert ctypes.sizeof(PdscSolveParams) == 64 and ctypes.sizeof(PdscSolveResult) == 304
 assert ctypes.sizeof(PdscParams) == 16 and ctypes.sizeof(PdscResult) == 16
 assert ctypes.sizeof(SelectParams) == 24 and ctypes.sizeof(SelectResult) == 136
 assert ctypes.sizeof(BbrfParams) == 56 and ctypes.sizeof(BbrfResult) == 280
@@ -288,6 +307,13 @@ def lib():
         L.lr_pdsc_scratch_bytes.argtypes = [ci]
         L.lr_pdsc_encode.argtypes = [vp, vp, ci, vp, vp, ctypes.c_size_t, ctypes.POINTER(PdscParams), vp, vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_pdsc_encode_batch.argtypes = [ci, pp, pp, ip, pp, vp, ctypes.c_size_t, ctypes.POINTER(PdscParams), vp, pp, pp, vp, ctypes.c_size_t, vp]
+        sz, ps = ctypes.c_size_t, ctypes.POINTER(PdscSolveParams)
+        L.lr_pdsc_solve_scratch_bytes.argtypes = [ci]
+        L.lr_pdsc_register_scratch_bytes.argtypes = [ci]
+        L.lr_pdsc_solve.argtypes = [vp, vp, ci, vp, vp, vp, ps, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.lr_pdsc_solve_batch.argtypes = [ci, pp, pp, ip, pp, pp, pp, ps, vp, pp, pp, vp, sz, vp]
+        L.lr_pdsc_register.argtypes = [vp, vp, ci, vp, vp, sz, ctypes.POINTER(PdscParams), ps, vp, vp, vp, vp, vp, vp, sz, vp]
+        L.lr_pdsc_register_batch.argtypes = [ci, pp, pp, ip, pp, vp, sz, ctypes.POINTER(PdscParams), ps, vp, pp, pp, pp, pp, vp, sz, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

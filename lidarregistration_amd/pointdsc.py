@@ -1,10 +1,13 @@
-"""PointDSC's SC-NonLocal correspondence encoder and confidence head on top of liblidarreg.so: lr_pdsc_encode / lr_pdsc_encode_batch
-(csrc/lr_pdsc.hip).  Given the correspondences of a pair it returns a 128-d feature and an inlier logit per correspondence -- the
-reference's classifier output (Experiments/models/PointDSC.py:171, :190-191), usable as a learned pre-filter in front of the RANSAC,
-SM and TEASER back ends.  Seed picking, the neural spectral matching, the per-seed fits and post_refinement are not built (DESIGN.md
-§16).  The contract is stated in include/lidarreg.h and restated in numpy in tests/pdsc_cpu.py.  There is no CPU fallback.
+"""PointDSC on top of liblidarreg.so.  The encoder: lr_pdsc_encode / lr_pdsc_encode_batch (csrc/lr_pdsc.hip) return a 128-d feature and
+an inlier logit per correspondence -- the reference's classifier output (Experiments/models/PointDSC.py:171, :190-191), usable as a
+learned pre-filter in front of the RANSAC, SM and TEASER back ends.  The tail: lr_pdsc_solve / lr_pdsc_register
+(csrc/lr_pdsc_solve.hip) pick the seeds, run the per-seed neural spectral matching and fits, select the best hypothesis and refine it
+(DESIGN.md §17): ``solve``, ``PointDSCModel`` and ``eval_pairs``, the engine of ``python -m test --algo PointDSC``.  The contracts are
+stated in include/lidarreg.h and restated in numpy in tests/pdsc_cpu.py and tests/pdsc_solve_cpu.py.  There is no CPU fallback.
 """
 import ctypes
+import json
+import os
 
 import numpy as np
 import torch
@@ -168,3 +171,226 @@ class PointDSCEncoder:
         f, c, self.last_info = self.encode_batch([src], [tgt], None, None if m_dev is None else [m_dev], poison, single=True,
                                                  want_feat=want_feat, want_conf=want_conf)[0]
         return f, c
+
+
+# ---- the tail: seeds, neural spectral matching, fits, selection, refinement (lr_pdsc_solve, lr_pdsc_register) ----------------------
+def solve_params(**kw):
+    """lr_pdsc_solve_params: the reference's Lidar settings unless overridden."""
+    return _ext.PdscSolveParams(**kw)
+
+
+def _solve_info(r):
+    d = devmem.as_dict(r)
+    d.pop("reserved"); d.pop("T")
+    return d
+
+
+def _arr(ts, n):
+    return None if ts is None else (ctypes.c_void_p * n)(*[ptr(t) for t in ts])
+
+
+def _asked(ts, want):
+    """The output tensors as a call sees them: all, none (False: NULL for the whole array) or NULL per entry (a list of bools)."""
+    return ts if want is None else None if want is False else [t if ok else None for t, ok in zip(ts, want)]
+
+
+class _SolveCall:
+    """The buffers of one lr_pdsc_solve(_batch) / lr_pdsc_register(_batch) call and the read-back of its results."""
+
+    def __init__(self, srcs, tgts, ms, params, dev):
+        self.n = n = len(srcs)
+        self.ms = ms
+        self.params = params
+        self.res = torch.zeros(ctypes.sizeof(_ext.PdscSolveResult) * n, dtype=torch.uint8, device=dev)
+        # (the fills are what an entry the library must not write keeps: tests read them)
+        self.labels = [torch.full((max(m, 1),), 255, dtype=torch.uint8, device=dev) for m in ms]
+        self.caps = [int(m * params.ratio) for m in ms]
+        self.seeds = [torch.full((max(c, 1),), -7, dtype=torch.int32, device=dev) for c in self.caps]
+
+    def results(self):
+        host = self.res.cpu()
+        out = []
+        for k, m in enumerate(self.ms):
+            r = devmem.read_struct(host, _ext.PdscSolveResult, k)
+            info = _solve_info(r)
+            info["seeds"] = self.seeds[k][:max(info["n_seeds"], 0)]
+            out.append((np.array(r.T, np.float64).reshape(4, 4), self.labels[k][:m], info))
+        return out
+
+
+def _timed(fn, args):
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    _ext.check(fn(*args, _stream()))
+    ev1.record()
+    torch.cuda.current_stream().synchronize()
+    return ev0.elapsed_time(ev1)
+
+
+def solve_batch(srcs, tgts, feats, confs, ms=None, m_devs=None, poison=None, single=False, timed=False, trace=False, want_labels=None,
+                want_seeds=None, **params):
+    """lr_pdsc_solve_batch over len(srcs) ragged pairs: src / tgt [M_k,3], feat [M_k,128], conf [M_k] float32 (what the encoder returned).
+    ms, m_devs, poison, single as PointDSCEncoder.encode_batch; want_labels / want_seeds as its want_feat.  trace (single only): info
+    also carries 'knn' int32 [n_seeds,k], 'weights' float32 [n_seeds,k], 'seed_T' float64 [n_seeds,4,4] and 'counts' int32 [n_seeds].
+    Returns [(T 4x4 float64 array, labels uint8 device tensor [m], info dict)] -- and, with timed, the device time of the call in ms."""
+    L = _ext.lib()
+    n = len(srcs)
+    srcs = [_f32(s).reshape(-1, 3) for s in srcs]; tgts = [_f32(t).reshape(-1, 3) for t in tgts]
+    feats = [_f32(f).reshape(-1, C) for f in feats]; confs = [_f32(c).reshape(-1) for c in confs]
+    dev = srcs[0].device
+    ms = [int(s.shape[0]) for s in srcs] if ms is None else [int(v) for v in ms]
+    p = solve_params(**params)
+    call = _SolveCall(srcs, tgts, ms, p, dev)
+    scratch = devmem.scratch(L.lr_pdsc_solve_scratch_bytes(max(ms)) * n, dev, poison)
+    lo, so = _asked(call.labels, want_labels), _asked(call.seeds, want_seeds)
+    tr = None
+    if single:
+        assert n == 1
+        cap, k = max(call.caps[0], 1), p.k
+        if trace:
+            tr = (torch.full((cap, k), -7, dtype=torch.int32, device=dev), torch.full((cap, k), -7.0, dtype=torch.float32, device=dev),
+                  torch.full((cap, 16), -7.0, dtype=torch.float64, device=dev), torch.full((cap,), -7, dtype=torch.int32, device=dev))
+        fn = L.lr_pdsc_solve
+        args = (ptr(srcs[0]), ptr(tgts[0]), ms[0], ptr(m_devs and m_devs[0]), ptr(feats[0]), ptr(confs[0]), ctypes.byref(p), call.res.data_ptr(),
+                ptr(lo and lo[0]), ptr(so and so[0]), *([ptr(t) for t in tr] if tr else [None] * 4), scratch.data_ptr(), scratch.numel())
+    else:
+        assert not trace, "the trace outputs belong to the single call"
+        fn = L.lr_pdsc_solve_batch
+        args = (n, _arr(srcs, n), _arr(tgts, n), (ctypes.c_int32 * n)(*ms), _arr(m_devs, n), _arr(feats, n), _arr(confs, n), ctypes.byref(p),
+                call.res.data_ptr(), _arr(lo, n), _arr(so, n), scratch.data_ptr(), scratch.numel())
+    t = _timed(fn, args)
+    out = call.results()
+    if tr:
+        ns = out[0][2]["n_seeds"]
+        out[0][2].update(knn=tr[0][:ns], weights=tr[1][:ns], seed_T=tr[2][:ns].reshape(-1, 4, 4), counts=tr[3][:ns], raw_trace=tr)
+    solve_batch.last_raw = (call.labels, call.seeds)
+    return (out, t) if timed else out
+
+
+def solve(src, tgt, feat, conf, m_dev=None, poison=None, trace=False, want_labels=None, want_seeds=None, **params):
+    """lr_pdsc_solve on one pair: (T 4x4 float64 array, labels uint8 device tensor [m], info dict)."""
+    return solve_batch([src], [tgt], [feat], [conf], None, None if m_dev is None else [m_dev], poison, single=True, trace=trace,
+                       want_labels=want_labels, want_seeds=want_seeds, **params)[0]
+
+
+class PointDSCModel:
+    """The whole network in inference mode: an encoder with its weights and the tail's parameters; sigma comes from the state dict."""
+
+    def __init__(self, encoder, **solve_kw):
+        self.encoder = encoder
+        self.solve_kw = dict(sigma_d=encoder.sigma_d, **solve_kw)
+        solve_params(**self.solve_kw)        # (an unknown keyword fails here)
+
+    @classmethod
+    def from_state_dict(cls, sd, num_layers=12, sigma_d=1.2, device=None, **solve_kw):
+        """sd: the reference's state dict (PointDSCEncoder.from_state_dict); its learned `sigma` (PointDSC.py:97) is S5's sigma unless
+        solve_kw names one."""
+        if "sigma" in sd and "sigma" not in solve_kw:
+            solve_kw["sigma"] = float(_np64(sd["sigma"]).reshape(-1)[0])
+        return cls(PointDSCEncoder.from_state_dict(sd, num_layers, sigma_d, device), **solve_kw)
+
+    def register_batch(self, srcs, tgts, ms=None, m_devs=None, poison=None, single=False, timed=False, want_feat=None, want_conf=None):
+        """lr_pdsc_register_batch (single: lr_pdsc_register): [(T 4x4 float64 array, labels uint8 device tensor [m], info dict)]; info
+        carries 'feat' and 'conf' (device tensors; the -1 fill where want_feat / want_conf did not ask for them)."""
+        L = _ext.lib()
+        enc = self.encoder
+        n = len(srcs)
+        srcs = [_f32(s).reshape(-1, 3) for s in srcs]; tgts = [_f32(t).reshape(-1, 3) for t in tgts]
+        dev = srcs[0].device
+        ms = [int(s.shape[0]) for s in srcs] if ms is None else [int(v) for v in ms]
+        p = solve_params(**self.solve_kw)
+        call = _SolveCall(srcs, tgts, ms, p, dev)
+        scratch = devmem.scratch(L.lr_pdsc_register_scratch_bytes(max(ms)) * n, dev, poison)
+        feats = [torch.full((max(m, 1), C), -1.0, dtype=torch.float32, device=dev) for m in ms]
+        confs = [torch.full((max(m, 1),), -1.0, dtype=torch.float32, device=dev) for m in ms]
+        fo, co = _asked(feats, want_feat), _asked(confs, want_conf)
+        w = (enc.weights.data_ptr(), enc.weights.numel() * 4, ctypes.byref(enc.params), ctypes.byref(p), call.res.data_ptr())
+        if single:
+            assert n == 1
+            fn = L.lr_pdsc_register
+            args = (ptr(srcs[0]), ptr(tgts[0]), ms[0], ptr(m_devs and m_devs[0]), *w, ptr(fo and fo[0]), ptr(co and co[0]),
+                    ptr(call.labels[0]), ptr(call.seeds[0]), scratch.data_ptr(), scratch.numel())
+        else:
+            fn = L.lr_pdsc_register_batch
+            args = (n, _arr(srcs, n), _arr(tgts, n), (ctypes.c_int32 * n)(*ms), _arr(m_devs, n), *w, _arr(fo, n), _arr(co, n),
+                    _arr(call.labels, n), _arr(call.seeds, n), scratch.data_ptr(), scratch.numel())
+        t = _timed(fn, args)
+        out = call.results()
+        for k, m in enumerate(ms):
+            out[k][2].update(feat=feats[k][:m], conf=confs[k][:m])
+        return (out, t) if timed else out
+
+    def register(self, src, tgt, m_dev=None, poison=None):
+        return self.register_batch([src], [tgt], None, None if m_dev is None else [m_dev], poison, single=True)[0]
+
+    def forward(self, data):
+        """The reference's call shape in testing mode (PointDSC.py:121-197): data['src_keypts'], data['tgt_keypts'] [1,M,3] ->
+        {'final_trans' [1,4,4], 'final_labels' [1,M]} float32 tensors on the inputs' device (data['corr_pos'] is their centred
+        concatenation, which the encoder forms itself)."""
+        src, tgt = torch.as_tensor(data["src_keypts"]), torch.as_tensor(data["tgt_keypts"])
+        assert src.shape[0] == 1, "bs = 1, as the reference's pick_seeds and post_refinement"
+        T, labels, _ = self.register(src.reshape(-1, 3), tgt.reshape(-1, 3))
+        return {"final_trans": torch.from_numpy(T).to(dtype=torch.float32, device=labels.device)[None], "final_labels": labels.to(torch.float32)[None]}
+
+    __call__ = forward
+
+
+# ---- the CLI's engine: python -m test --algo PointDSC --chosen_snapshot DIR ------------------------------------------------------------
+NUM_NODE = 12000          # Experiments/test.py:247
+LIDAR_THRESHOLD, LIDAR_SIGMA_D = 0.6, 1.2      # what test.py:338-339 overrides the snapshot's config with
+
+
+def load_snapshot(dirpath, device=None):
+    """The reference's snapshot layout (test.py:333, :392): DIR/config.json and DIR/models/model_best.pkl (a torch.save of the state dict).
+    inlier_threshold and sigma_d are overridden as test.py:338-339 does; nms_radius is the inlier threshold (:389); sigma_d is rounded to
+    float32, as the reference's sigma_spat parameter holds it."""
+    with open(os.path.join(dirpath, "config.json")) as fid:
+        cfg = json.load(fid)
+    if int(cfg.get("in_dim", 6)) != IN_DIM or int(cfg.get("num_channels", C)) != C:
+        raise ValueError(f"PointDSC snapshot {dirpath}: in_dim {cfg.get('in_dim')} / num_channels {cfg.get('num_channels')}; this build is {IN_DIM} / {C}")
+    sd = torch.load(os.path.join(dirpath, "models", "model_best.pkl"), map_location="cpu")
+    return PointDSCModel.from_state_dict(sd, num_layers=int(cfg["num_layers"]), sigma_d=float(np.float32(LIDAR_SIGMA_D)), device=device,
+                                         num_iterations=int(cfg.get("num_iterations", 10)), ratio=float(cfg.get("ratio", 0.1)), k=int(cfg.get("k", 40)),
+                                         nms_radius=LIDAR_THRESHOLD, inlier_threshold=LIDAR_THRESHOLD)
+
+
+def select_source(n0, num_node, seed):
+    """The at most num_node source points of a pair (LidarFeatureExtractor.py:99-100): every point, or the first num_node of a
+    permutation seeded by (seed, n0) -- None when every point is taken."""
+    return None if n0 <= num_node else np.sort(np.random.default_rng([int(seed), int(n0)]).permutation(n0)[:num_node])
+
+
+def correspondences_dev(xyz0, xyz1, F0, F1, args, ws, stream):
+    """The reference's extractor with use_mutual False (LidarFeatureExtractor.py:94-117): every selected source point with its nearest
+    target descriptor, through lr_nn_top2; no filter.  The target is not subsampled (deviation: the reference also draws num_node of its
+    points).  Returns (idx0, idx1 device int32, count device int32 [1]); nothing is synchronised."""
+    n0, n1, d = F0.shape[0], F1.shape[0], F0.shape[1]
+    dev = F0.device
+    sel = select_source(n0, int(getattr(args, "num_node", NUM_NODE)), int(getattr(args, "seed", 51)))
+    if sel is None:
+        idx0 = torch.arange(n0, dtype=torch.int32, device=dev)
+    else:
+        idx0 = torch.from_numpy(sel.astype(np.int32)).to(dev)
+        F0 = F0[idx0.long()].contiguous()
+    m = idx0.shape[0]
+    idx1 = torch.empty(m, dtype=torch.int32, device=dev)
+    _ext.check(_ext.lib().lr_nn_top2(ws.handle, F0.data_ptr(), m, F1.data_ptr(), n1, d, idx1.data_ptr(), None, None, None, stream))
+    return idx0, idx1, torch.full((1,), m, dtype=torch.int32, device=dev)
+
+
+def eval_pairs(source, indices, args, device=None, batch=32, nstreams=3, verbose=False):
+    """--algo PointDSC over `indices` of `source` (corrset.eval_pairs): ONE lr_pdsc_register_batch per window.  Returns a harness.EvalRun.
+    Column 9 = the pair's share of its window's register call (its device time split evenly), as for --algo SM."""
+    from . import corrset
+    if str(getattr(args, "solver", "SVD")).upper() == "RANSAC":
+        raise ValueError("--solver RANSAC is not built: --algo PointDSC fits by SVD (--solver SVD)")
+    snap = getattr(args, "chosen_snapshot", None)
+    if not snap:
+        raise ValueError("--algo PointDSC needs --chosen_snapshot DIR (DIR/config.json, DIR/models/model_best.pkl)")
+    model = load_snapshot(snap, device)
+    batch = min(int(batch), 64)                      # (LR_MAX_BATCH)
+
+    def solve(srcs, tgts):
+        out, ms = model.register_batch(srcs, tgts, timed=True, want_feat=False, want_conf=False)
+        return [(T, info, labels) for T, labels, info in out], ms
+    return corrset.eval_pairs(source, indices, args, correspondences_dev, solve, device=device, batch=batch, nstreams=nstreams, verbose=verbose)
