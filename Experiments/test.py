@@ -6,6 +6,8 @@
 Same flags and defaults for the RANSAC path, same `test_parallel <start_time> <tmp_base> <world> <rank|analysis>` protocol,
 same outputs (`outputs/<dataset>.Test.<time>/{raw_stats.npy,log.txt}`) plus `coarse_motions.txt` (format of
 FCGF_FAST/test.py:86-106).  Datasets and FCGF weights are not part of this repo; pairs come from, in order:
+  0a. the reference's cloud cache + --fcgf_weights_file CHECKPOINT (the reference's own flag): the FCGF descriptors of the de-duplicated
+     scans are computed on the GPU (lidarregistration_amd.fcgf), no feature cache needed,
   0. the reference's cloud cache (env LIDARREG_CLOUD_CACHE=<dir with <session>_<idx>.npy>, voxel-deduplicated on the GPU like the
      reference's loader) + a feature cache for the same voxelisation + LIDARREG_BALANCED_SETS,
   1. a feature cache  (env LIDARREG_FEATURE_CACHE=<dir> + LIDARREG_BALANCED_SETS=<dir with <set>/<phase>.txt>),
@@ -69,6 +71,7 @@ def get_args(argv=None):
     p.add_argument("--SM_iters", type=int, default=10, help="--algo SM: power iterations (baseline_3DMatch.py:41)")
     p.add_argument("--chosen_snapshot", type=str, default="", help="--algo PointDSC: directory with config.json and models/model_best.pkl (the reference's snapshot layout)")
     p.add_argument("--solver", type=str, default="SVD", choices=["SVD", "RANSAC"], help="--algo PointDSC: SVD; RANSAC is not built and is refused")
+    p.add_argument("--fcgf_weights_file", type=str, default=None, help="FCGF checkpoint (torch.load(file)['state_dict'], ResUNetBN2C): compute the descriptors from the cloud cache's raw scans on the GPU instead of reading a feature cache")
     # additions of this implementation
     p.add_argument("--num_node", type=int, default=12000, help="--algo PointDSC: at most this many source points per pair (test.py:247)")
     p.add_argument("--num_pairs", type=int, default=32, help="synthetic: number of pairs")
@@ -86,6 +89,8 @@ def get_args(argv=None):
         p.error("--solver RANSAC is not built: --algo PointDSC fits by SVD")
     if args.algo == "PointDSC" and not args.chosen_snapshot:
         p.error("--algo PointDSC needs --chosen_snapshot DIR (DIR/config.json and DIR/models/model_best.pkl)")
+    if args.fcgf_weights_file and not (os.environ.get("LIDARREG_CLOUD_CACHE") and os.environ.get("LIDARREG_BALANCED_SETS") and args.dataset != "synthetic"):
+        p.error("--fcgf_weights_file computes the descriptors from raw scans and needs a cloud cache: set LIDARREG_CLOUD_CACHE and LIDARREG_BALANCED_SETS and name a list --dataset (A, B, S, K, L)")
     args.start_time, args.tmp_file_base, args.world_size, args.rank, args.do_analysis = start_time, tmp_file_base, world_size, rank, do_analysis
     from lidarregistration_amd import io_lists
     args.dataset_name = io_lists.DATASET_NAMES.get(args.dataset, args.dataset)
@@ -101,6 +106,9 @@ def make_source(args):
     if args.dataset in io_lists.DATASET_NAMES and sets:
         lst = io_lists.read_pair_list(os.path.join(sets, args.dataset_name, args.phase + ".txt"))
         clouds = os.environ.get("LIDARREG_CLOUD_CACHE")
+        if clouds and args.fcgf_weights_file:
+            from lidarregistration_amd import fcgf
+            return harness.RefCloudSource(lst, os.path.join(clouds, args.dataset_name), None, extractor=fcgf.FCGF.from_checkpoint(args.fcgf_weights_file))
         if clouds and cache:
             return harness.RefCloudSource(lst, os.path.join(clouds, args.dataset_name), os.path.join(cache, args.dataset_name, args.phase))
         if cache:

@@ -815,6 +815,68 @@ LR_API int lr_pdsc_register_batch(int npairs, const float *const *src, const flo
                                   lr_pdsc_solve_result *results, float *const *feat_out, float *const *conf_out, uint8_t *const *labels_out,
                                   int32_t *const *seeds_out, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- n1: the FCGF feature extractor: ResUNetBN2C(in_channels = 1, out_channels = 32, conv1_kernel_size 3 | 5, normalize_feature),
+ * inference mode, D = 3, hyper-cube regions (Experiments/misc/fcgf.py:621-851, :864-867): what the reference runs on MinkowskiEngine
+ * for every pair (Experiments/datasets/LidarFeatureExtractor.py:71-81, :166-181).  MinkowskiEngine is not part of the reference tree:
+ * its convolution semantics are upstream-recalled; the one table that would change if a recalled convention were wrong is idx(o) of F2.
+ * Contract (restated twice in tests/fcgf_cpu.py, once on torch's dense convolutions in tests/test_fcgf_cpu.py).
+ * Input: coords [n,3] int32 integer voxel cells at tensor stride 1 (lr_voxel_dedup's `cells`), feat_in [n] float32 or NULL = all ones
+ * (generic_balanced_loader.py:81), 0 <= n <= 2^20.  Output: feat_out [n,32] float32, row i for input row i, and lr_fcgf_result.
+ *  F1  levels: level 0 = the input rows in input order.  Level l+1 = the distinct floor(c / 2^(l+1)) * 2^(l+1) over level l (floor
+ *      division: -1 -> -2), its rows by ascending (x, y, z), lexicographic on the biased 21-bit fields of the packed key (cell + 2^20):
+ *      independent of the input order and of the hash.  Three coarse levels.
+ *  F2  stride-1 convolution, K = 2h+1, tensor stride t, output set = input set: out[u] = sum_o in[u + o t] W[idx(o)], o in {-h..h}^3,
+ *      absent neighbours contribute nothing; W is [K^3, Cin, Cout] (MinkowskiEngine 0.5's `kernel`);
+ *      idx(o) = (o_x+h) + K (o_y+h) + K^2 (o_z+h), x fastest [upstream-recalled].  1x1: in[u] W, the kernel [Cin,Cout] or [1,Cin,Cout].
+ *  F3  stride-2 convolution (K = 3, level l -> l+1): out[v] = sum_o in[v + o t] W[idx(o)], t the input's tensor stride, v a level-(l+1) cell.
+ *  F4  transposed stride-2 convolution (K = 3, level l+1 -> l) onto the EXISTING level-l set, the transpose of F3's map:
+ *      out[u] = sum_{o : u - o t in level l+1} in[u - o t] W[idx(o)].
+ *  F5  fp32 throughout; per output element ONE fmaf chain from +0 over ascending idx(o) and, inside an offset, ascending input channel;
+ *      an absent neighbour is a zero operand or skipped (the same bits with finite weights).  v_mfma_f32_32x32x2_f32 is this chain bit
+ *      for bit: the contract is bit-exact.  No floating-point atomics.
+ *  F6  epilogue: y = fmaf(scale, acc, offset); then `+ residual` (one fp32 add) where the stage has one; then ReLU where it has one
+ *      (y > 0 ? y : 0, a NaN stays).  BatchNorm (eps 1e-5) folded in fp64 and rounded once: scale = gamma / sqrt(var + eps),
+ *      offset = (0 - mean) scale + beta; no BatchNorm: scale 1, offset = bias or 0.
+ *  F7  stages (BN = fold, R = ReLU, +r = residual = the block's input): 1 conv1 BN (no ReLU: fcgf.py:801-803); 2-3 block1: BN R, BN +r R;
+ *      4 / 7 / 10 conv2 / conv3 / conv4 (F3) BN, each followed by its block (5-6, 8-9, 11-12) as block1; 13 conv4_tr (F4) BN, 14-15
+ *      block4_tr; 16 conv3_tr on cat(up, s4) BN, 17-18 block3_tr; 19 conv2_tr on cat(up, s2) BN, 20-21 block2_tr; 22 conv1_tr 1x1 on
+ *      cat(up, s1), 96 -> 64, R, no BN; 23 final 1x1 64 -> 32 + bias.  cat puts the up path's channels first.  Channels 32 / 64 / 128 /
+ *      256 down, 128 / 64 / 64 / 64 up.
+ *  F8  s = fmaf chain of the 32 squares from 0 in ascending channel; out = f / (sqrtf(s) + 1e-8f), root and division correctly rounded.
+ *  F9  a duplicate coordinate: status 2; |cell| >= 2^20 - 2 on an axis: status 3 (it wins over 2); either way feat_out's n rows are 0
+ *      (a tap stores no rows: n_tap = 0).  A non-finite feat_in is carried.  n = 0: status 0, nothing stored but the result block.
+ *  F10 the same input gives the same bits on every run whatever the scratch held; permuting the input rows permutes the output rows;
+ *      adding a multiple of 8 to every cell of an axis changes no bit.
+ *  F11 weights: one flat float32 device blob of lr_fcgf_weights_bytes(conv1_kernel_size) bytes, 16-byte aligned: per stage in F7's order
+ *      { W[K^3][Cin][Cout], scale[Cout], offset[Cout] }.
+ *  F12 refusals: LR_EINVAL before any launch, lr_last_error naming the argument: struct_size, conv1_kernel_size not 3 or 5, tap outside
+ *      0..23, n outside 0..2^20, null / short / misaligned weights, null result / coords / feat_out, and the scratch, stream and device
+ *      rules of every entry point with a caller-owned scratch.                                                                         */
+typedef struct lr_fcgf_params {
+    uint32_t struct_size;        /* = sizeof(lr_fcgf_params)                                                                        */
+    int32_t  conv1_kernel_size;  /* 5 (LidarFeatureExtractor.py:75); 3 or 5                                                         */
+    int32_t  tap;                /* 0: the network.  s = 1..23: stop behind stage s and store ITS activations [n_tap, Cout] in feat_out
+                                    (which the caller sizes for n x 256) and its level's cells in tap_coords                        */
+} lr_fcgf_params;
+
+/* Written to device memory by lr_fcgf_extract (16 bytes). */
+typedef struct lr_fcgf_result {
+    int32_t  status;             /* 0 ok, 2 = duplicate coordinate, 3 = a cell at or past the range limit                           */
+    int32_t  n;
+    int32_t  n_tap;              /* rows stored in feat_out: n, or the rows of the tapped stage's level; 0 on status 2 / 3          */
+    int32_t  reserved;           /* 0                                                                                               */
+} lr_fcgf_result;
+
+/* Bytes of the weight blob (0 when conv1_kernel_size is not 3 or 5). */
+LR_API size_t lr_fcgf_weights_bytes(int conv1_kernel_size);
+/* Caller-owned device scratch for up to max_n cells (0 when max_n is outside 0..2^20); a constant plus a multiple of max_n rounded up to 64. */
+LR_API size_t lr_fcgf_scratch_bytes(int max_n);
+/* tap_coords: nullable, int32 [n,3], written by a tap only.  scratch: >= lr_fcgf_scratch_bytes(n) bytes, 256-byte aligned, memory of the
+ * current device (checked, like the stream).  No host synchronisation, no allocation.                                               */
+LR_API int lr_fcgf_extract(const int32_t *coords, const float *feat_in, int n, const float *weights, size_t weights_bytes,
+                           const lr_fcgf_params *p, lr_fcgf_result *result, float *feat_out, int32_t *tap_coords, void *scratch,
+                           size_t scratch_bytes, void *stream);
+
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */
 LR_API int lr_workspace_timing(lr_workspace *ws, int enable);

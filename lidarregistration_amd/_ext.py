@@ -29,6 +29,7 @@ SYMBOLS = [
     "lr_pdsc_weights_bytes", "lr_pdsc_scratch_bytes", "lr_pdsc_encode", "lr_pdsc_encode_batch",
     "lr_pdsc_solve_scratch_bytes", "lr_pdsc_solve", "lr_pdsc_solve_batch",
     "lr_pdsc_register_scratch_bytes", "lr_pdsc_register", "lr_pdsc_register_batch",
+    "lr_fcgf_weights_bytes", "lr_fcgf_scratch_bytes", "lr_fcgf_extract",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -204,6 +205,17 @@ class PdscSolveResult(ctypes.Structure):
                 ("reserved", ctypes.c_int32 * 3)]
 
 
+class FcgfParams(KeywordParams):
+    """lr_fcgf_params with the reference's network (LidarFeatureExtractor.py:71-76) as default; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("conv1_kernel_size", ctypes.c_int32), ("tap", ctypes.c_int32)]
+    DEFAULTS = dict(conv1_kernel_size=5, tap=0)
+
+
+class FcgfResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("n", ctypes.c_int32), ("n_tap", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(FcgfParams) == 12 and ctypes.sizeof(FcgfResult) == 16
 assert ctypes.sizeof(PdscSolveParams) == 64 and ctypes.sizeof(PdscSolveResult) == 304
 assert ctypes.sizeof(PdscParams) == 16 and ctypes.sizeof(PdscResult) == 16
 assert ctypes.sizeof(SelectParams) == 24 and ctypes.sizeof(SelectResult) == 136
@@ -314,6 +326,10 @@ def lib():
         L.lr_pdsc_solve_batch.argtypes = [ci, pp, pp, ip, pp, pp, pp, ps, vp, pp, pp, vp, sz, vp]
         L.lr_pdsc_register.argtypes = [vp, vp, ci, vp, vp, sz, ctypes.POINTER(PdscParams), ps, vp, vp, vp, vp, vp, vp, sz, vp]
         L.lr_pdsc_register_batch.argtypes = [ci, pp, pp, ip, pp, vp, sz, ctypes.POINTER(PdscParams), ps, vp, pp, pp, pp, pp, vp, sz, vp]
+        L.lr_fcgf_weights_bytes.restype = ctypes.c_size_t
+        L.lr_fcgf_weights_bytes.argtypes = [ci]
+        L.lr_fcgf_scratch_bytes.argtypes = [ci]
+        L.lr_fcgf_extract.argtypes = [vp, vp, ci, vp, sz, ctypes.POINTER(FcgfParams), vp, vp, vp, vp, sz, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

@@ -1,0 +1,185 @@
+"""FCGF descriptors on top of liblidarreg.so: lr_fcgf_extract (csrc/lr_fcgf.hip) runs the reference's feature network --
+``ResUNetBN2C(1, 32, conv1_kernel_size=5, normalize_feature=True)`` of Experiments/misc/fcgf.py, which the reference evaluates on
+MinkowskiEngine for every pair (Experiments/datasets/LidarFeatureExtractor.py:71-81, :166-181) -- on integer voxel cells.  This module
+packs the reference's checkpoint (``torch.load(file)['state_dict']``) into the library's weight blob and wraps the call.  The contract is
+n1 of include/lidarreg.h, restated in numpy in tests/fcgf_cpu.py.  There is no CPU fallback.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _ext, devmem
+from .devmem import ptr
+
+BN_EPS = 1e-5              # MinkowskiBatchNorm wraps torch.nn.BatchNorm1d and keeps its default
+N_STAGES = 23
+MAX_N = 1 << 20
+
+
+def stage_plan(conv1_kernel_size=5):
+    """The 23 stages in order: (conv module, norm module | None, K^3, Cin, Cout) -- the module names of fcgf.py:644-798."""
+    if conv1_kernel_size not in (3, 5):
+        raise ValueError(f"conv1_kernel_size must be 3 or 5, not {conv1_kernel_size!r}")
+    plan = [("conv1", "norm1", conv1_kernel_size ** 3, 1, 32)]
+
+    def block(name, c):
+        return [(f"{name}.conv1", f"{name}.norm1", 27, c, c), (f"{name}.conv2", f"{name}.norm2", 27, c, c)]
+
+    plan += block("block1", 32)
+    for i, (cin, cout) in zip((2, 3, 4), ((32, 64), (64, 128), (128, 256))):
+        plan += [(f"conv{i}", f"norm{i}", 27, cin, cout)] + block(f"block{i}", cout)
+    for i, (cin, cout) in zip((4, 3, 2), ((256, 128), (256, 64), (128, 64))):
+        plan += [(f"conv{i}_tr", f"norm{i}_tr", 27, cin, cout)] + block(f"block{i}_tr", cout)
+    plan += [("conv1_tr", None, 1, 96, 64), ("final", None, 1, 64, 32)]
+    assert len(plan) == N_STAGES
+    return plan
+
+
+def packed_floats(conv1_kernel_size=5):
+    return sum(k3 * cin * cout + 2 * cout for _, _, k3, cin, cout in stage_plan(conv1_kernel_size))
+
+
+def _np64(sd, key, shape=None):
+    if key not in sd:
+        raise ValueError(f"FCGF state dict: missing key {key!r}")
+    v = sd[key]
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().numpy()
+    v = np.asarray(v, np.float64)
+    if shape is not None:
+        if v.shape != shape and not (v.size == int(np.prod(shape)) and v.squeeze().shape == tuple(s for s in shape if s != 1)):
+            raise ValueError(f"FCGF state dict: {key} has shape {v.shape}, expected {shape}")
+        v = v.reshape(shape)
+    if not np.isfinite(v).all():
+        raise ValueError(f"FCGF state dict: {key} holds a non-finite value")
+    return v
+
+
+def fold(sd, conv1_kernel_size=5, dtype=np.float32):
+    """[(W [K^3,Cin,Cout], scale [Cout], offset [Cout])] per stage, as `dtype`: BatchNorm folded in fp64 and rounded once (float64: not at
+    all -- what tests/fcgf_cpu.py's fp64 restatement evaluates).  A 1x1 kernel may be [Cin,Cout] or [1,Cin,Cout]; a missing key, a wrong
+    shape or a non-finite value is a ValueError naming the key."""
+    out = []
+    for conv, norm, k3, cin, cout in stage_plan(conv1_kernel_size):
+        W = _np64(sd, conv + ".kernel", (k3, cin, cout))
+        if norm:
+            g, b = _np64(sd, norm + ".bn.weight", (cout,)), _np64(sd, norm + ".bn.bias", (cout,))
+            mean, var = _np64(sd, norm + ".bn.running_mean", (cout,)), _np64(sd, norm + ".bn.running_var", (cout,))
+            with np.errstate(invalid="ignore", divide="ignore"):
+                scale = g / np.sqrt(var + BN_EPS)
+                offset = (0.0 - mean) * scale + b
+            if not (np.isfinite(scale).all() and np.isfinite(offset).all()):
+                raise ValueError(f"FCGF state dict: {norm}.bn.running_var does not fold to a finite scale")
+        else:
+            scale = np.ones(cout)
+            offset = _np64(sd, conv + ".bias", (cout,)) if conv == "final" else np.zeros(cout)
+        out.append((W.astype(dtype), scale.astype(dtype), offset.astype(dtype)))
+    return out
+
+
+def pack(sd, conv1_kernel_size=5):
+    """The flat float32 blob of lr_fcgf_weights_bytes(conv1_kernel_size) bytes: per stage W, scale, offset."""
+    return np.concatenate([np.concatenate([W.reshape(-1), s, o]) for W, s, o in fold(sd, conv1_kernel_size)]).astype(np.float32)
+
+
+def unpack(blob, conv1_kernel_size=5):
+    """pack() undone: the stages of a blob."""
+    stages, at = [], 0
+    for _, _, k3, cin, cout in stage_plan(conv1_kernel_size):
+        W = blob[at:at + k3 * cin * cout].reshape(k3, cin, cout); at += k3 * cin * cout
+        stages.append((W, blob[at:at + cout], blob[at + cout:at + 2 * cout])); at += 2 * cout
+    assert at == len(blob), (at, len(blob))
+    return stages
+
+
+class FCGF:
+    """The feature network with one set of weights on one device."""
+
+    def __init__(self, blob, conv1_kernel_size=5, device=None):
+        L = _ext.lib()
+        self.conv1_kernel_size = int(conv1_kernel_size)
+        blob = np.ascontiguousarray(blob, np.float32).reshape(-1)
+        want = L.lr_fcgf_weights_bytes(self.conv1_kernel_size)
+        if want == 0 or blob.nbytes != want:
+            raise ValueError(f"weight blob of {blob.nbytes} bytes, lr_fcgf_weights_bytes({self.conv1_kernel_size}) = {want}")
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.weights = torch.from_numpy(blob).to(self.device)
+        self.last_info = None
+
+    @classmethod
+    def from_state_dict(cls, sd, conv1_kernel_size=5, device=None):
+        """sd: the reference's state dict (tensors or arrays): <conv>.kernel, final.bias and <norm>.bn.{weight,bias,running_mean,
+        running_var}; other keys (num_batches_tracked) are ignored."""
+        return cls(pack(sd, conv1_kernel_size), conv1_kernel_size, device)
+
+    @classmethod
+    def from_checkpoint(cls, path, conv1_kernel_size=None, device=None):
+        """The reference's checkpoint file (LidarFeatureExtractor.py:79-80): torch.load(path)['state_dict'].  conv1_kernel_size: read from
+        conv1.kernel's shape unless given."""
+        ck = torch.load(path, map_location="cpu")
+        sd = ck["state_dict"] if isinstance(ck, dict) and "state_dict" in ck else ck
+        if conv1_kernel_size is None:
+            k3 = int(np.asarray(_np64(sd, "conv1.kernel")).shape[0])
+            conv1_kernel_size = {27: 3, 125: 5}.get(k3)
+            if conv1_kernel_size is None:
+                raise ValueError(f"FCGF state dict: conv1.kernel has {k3} offsets, expected 27 or 125")
+        return cls.from_state_dict(sd, conv1_kernel_size, device)
+
+    def _call(self, coords, feat_in, tap, poison=None):
+        L = _ext.lib()
+        dev = self.device
+        coords = torch.as_tensor(coords).to(device=dev, dtype=torch.int32).contiguous().reshape(-1, 3)
+        n = int(coords.shape[0])
+        if feat_in is not None:
+            feat_in = torch.as_tensor(feat_in).to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+            if feat_in.shape[0] != n:
+                raise ValueError(f"feat_in has {feat_in.shape[0]} rows, coords {n}")
+        scratch = devmem.scratch(L.lr_fcgf_scratch_bytes(n), dev, poison)
+        res = torch.zeros(ctypes.sizeof(_ext.FcgfResult), dtype=torch.uint8, device=dev)
+        out = torch.zeros((max(n, 1), 256 if tap else 32), dtype=torch.float32, device=dev)
+        tc = torch.zeros((max(n, 1), 3), dtype=torch.int32, device=dev) if tap else None
+        params = _ext.FcgfParams(conv1_kernel_size=self.conv1_kernel_size, tap=int(tap))
+        with torch.cuda.device(dev):
+            _ext.check(L.lr_fcgf_extract(ptr(coords, n), ptr(feat_in, n), n, self.weights.data_ptr(), self.weights.numel() * 4, ctypes.byref(params),
+                                         res.data_ptr(), ptr(out, n), ptr(tc, n), scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream().cuda_stream))
+        return n, out, tc, res
+
+    def features(self, coords, feat_in=None, poison=None):
+        """coords [n,3] integer voxel cells (distinct), feat_in [n] or None = ones -> [n,32] float32 device tensor, row i for cell i.
+        self.last_info: the result block (status 2: a duplicate cell, 3: a cell past the range limit; the rows are 0 then).
+        poison: fill the scratch with this byte first (test hook)."""
+        n, out, _, res = self._call(coords, feat_in, 0, poison)
+        r = devmem.read_struct(res, _ext.FcgfResult)
+        self.last_info = dict(status=r.status, n=r.n, n_tap=r.n_tap)
+        return out[:n]
+
+    def tap(self, coords, s, feat_in=None):
+        """Stage s (1..23) alone: (activations [n_level, Cout], the level's cells [n_level, 3]) as device tensors."""
+        if not 1 <= int(s) <= N_STAGES:
+            raise ValueError(f"tap stage must lie in 1..{N_STAGES}")
+        n, out, tc, res = self._call(coords, feat_in, int(s))
+        r = devmem.read_struct(res, _ext.FcgfResult)
+        self.last_info = dict(status=r.status, n=r.n, n_tap=r.n_tap)
+        cout = stage_plan(self.conv1_kernel_size)[int(s) - 1][4]
+        return out.reshape(-1)[:r.n_tap * cout].reshape(r.n_tap, cout), tc[:r.n_tap]
+
+    def extract(self, xyz_raw, voxel_size=0.3):
+        """A raw scan [N,3] -> (xyz_kept [n,3] float32, feats [n,32], sel [n] int64), device tensors: the reference's loader
+        (generic_balanced_loader.py:62-66, :81: voxel de-duplication, floor(xyz / voxel_size), features of ones) and its network."""
+        from . import voxel
+        with torch.cuda.device(self.device):
+            xyz, sel = voxel.voxel_downsample(xyz_raw, voxel_size)
+            x64 = torch.as_tensor(xyz_raw).to(device=self.device, dtype=torch.float64)[sel]
+            cells = torch.floor(x64 / voxel_size).to(torch.int32)
+            feats = self.features(cells)
+        if self.last_info["status"] != 0:
+            raise _ext.LidarRegError(f"lr_fcgf_extract: status {self.last_info['status']} (2: duplicate cell, 3: cell past the range limit of 2^20 - 2)")
+        return xyz, feats, sel
+
+    def extract_pair(self, xyz0_raw, xyz1_raw, voxel_size=0.3):
+        """Two raw scans -> (xyz0, xyz1, feats0, feats1), the arguments of FR() in its order: what LidarFeatureExtractor.process_batch
+        computes for one pair."""
+        xyz0, f0, _ = self.extract(xyz0_raw, voxel_size)
+        xyz1, f1, _ = self.extract(xyz1_raw, voxel_size)
+        return xyz0, xyz1, f0, f1

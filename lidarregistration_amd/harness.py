@@ -94,11 +94,13 @@ class RefCloudSource:
     """Pairs of a balanced list from the REFERENCE's cloud cache (io_lists.load_ref_cloud: raw scans, [N,3] float64): every
     scan is voxel-deduplicated on the GPU exactly as the reference's loader does before the network sees it
     (voxel.voxel_downsample == ME.utils.sparse_quantize(xyz / 0.3, return_index=True), generic_balanced_loader.py:62-66).
-    FCGF itself is out of scope, so the 32-d descriptors of the kept points come from a feature cache written for the same
-    voxelisation (io_lists.save_cloud(feat_dir, session, idx, xyz[sel], feats)); a missing or mismatching entry is an error."""
+    The 32-d descriptors of the kept points come from a feature cache written for the same voxelisation
+    (io_lists.save_cloud(feat_dir, session, idx, xyz[sel], feats)); a missing or mismatching entry is an error.  With an `extractor`
+    (fcgf.FCGF: the CLI's --fcgf_weights_file) they are computed on the device from the de-duplicated cloud instead, as the reference
+    does for every pair (LidarFeatureExtractor.py:166-181), and no feature cache is read (feat_dir may be None)."""
 
-    def __init__(self, pair_list, cloud_dir, feat_dir, voxel_size=0.3):
-        self.pair_list, self.cloud_dir, self.feat_dir, self.voxel_size = pair_list, cloud_dir, feat_dir, voxel_size
+    def __init__(self, pair_list, cloud_dir, feat_dir, voxel_size=0.3, extractor=None):
+        self.pair_list, self.cloud_dir, self.feat_dir, self.voxel_size, self.extractor = pair_list, cloud_dir, feat_dir, voxel_size, extractor
 
     def __len__(self):
         return len(self.pair_list["session"])
@@ -107,11 +109,15 @@ class RefCloudSource:
         return int(self.pair_list["session"][k]), int(self.pair_list["src"][k]), int(self.pair_list["tgt"][k])
 
     def _files(self, s, i):
-        return io_lists.load_ref_cloud(self.cloud_dir, s, i), io_lists.load_cloud(self.feat_dir, s, i)
+        return io_lists.load_ref_cloud(self.cloud_dir, s, i), None if self.extractor else io_lists.load_cloud(self.feat_dir, s, i)
 
     def _cloud(self, s, i, files=None):
         from . import voxel
-        raw, (cx, feats) = files if files is not None else self._files(s, i)
+        raw, cached = files if files is not None else self._files(s, i)
+        if self.extractor:
+            xyz, feats, _ = self.extractor.extract(raw, self.voxel_size)
+            return xyz.cpu().numpy(), feats.cpu().numpy()
+        cx, feats = cached
         xyz, sel = voxel.voxel_downsample(raw, self.voxel_size)
         xyz = xyz.cpu().numpy()
         if feats.shape[0] != xyz.shape[0] or not np.allclose(cx, xyz, atol=1e-4):

@@ -1,4 +1,5 @@
-"""Synthetic FCGF-like pairs: there are no datasets or FCGF weights here.
+"""Synthetic FCGF-like pairs: there are no datasets or trained FCGF weights here (the network itself is
+lidarregistration_amd.fcgf; with a checkpoint it computes real descriptors from a raw scan).
 
 A pair is two clouds with a planted rigid motion and partial overlap ``rho``; descriptors are
 32-d unit vectors (the reference L2-normalises FCGF output, Experiments/misc/fcgf.py:387-391)
