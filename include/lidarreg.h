@@ -877,6 +877,75 @@ LR_API int lr_fcgf_extract(const int32_t *coords, const float *feat_in, int n, c
                            const lr_fcgf_params *p, lr_fcgf_result *result, float *feat_out, int32_t *tap_coords, void *scratch,
                            size_t scratch_bytes, void *stream);
 
+/* ---- d1: Deep Global Registration's robust pose refinement over M weighted correspondences src[i] <-> tgt[i] -----------------------
+ * Replaces what DeepGlobalRegistration.register does once it has the inlier weights (DGR/core/deep_global_registration.py:403-435): the
+ * weight-sum decision and GlobalRegistration (DGR/core/registration.py:16-64, :116-194) under HighDimSmoothL1Loss (DGR/core/loss.py:42-61):
+ * up to 1000 Adam iterations over a 6-D rotation (a, b) and a translation t, the whole loop in one launch.  Contract (restated in
+ * tests/dgr_cpu.py); m = m_dev clamped to 0..m; fp64 throughout, no fused multiply-add, only + - * / sqrt, products and dot
+ * products associated as in f7 ((u0 v0 + u1 v1) + u2 v2; M v likewise):
+ *  G1 row i < m is live iff its six coordinates and its weight are finite, w_i > 0 and w_i >= clip.  weights == NULL: every weight is 1.
+ *     Live rows are compacted in index order; L = their number; w1 = S(w).
+ *  G2 S: thread t of 1024 adds entries t, t + 1024, ... of the compacted list in ascending order from +0.0, then s[t] = s[t] + s[t + h]
+ *     for h = 512 .. 1.
+ *  G3 p = (a, b, t), nine numbers.  With T_init: its first two columns as they are (not re-orthonormalised) and its translation.
+ *     Without: wn = w / (w1 + 2^-23); mom = { S(wn), S(wn X_a), S(wn Y_a), S((wn X_a) Y_b) }; T = lr_rt_from_moments(mom) of lr_contract.h;
+ *     every entry rounded to float32 and widened (the reference's weighted_procrustes ends in .float()).
+ *  G4 R(p) (ortho2rotation): x = a / max(|a|, 1e-8); n2 = max(x.x, 1e-8); c = (x.b) / n2; u = b - c x; y = u / max(|u|, 1e-8); z = x X y;
+ *     R = [x y z] (columns).  max(v, 1e-8) = v < 1e-8 ? 1e-8 : v (a NaN stays one).
+ *  G5 r = ((R X_i + t) - Y_i) / q, q = quantization_size; s = r.r; l_i = 0.5 s if s < 1, else 0.5 (sqrt(s + 2^-23) - 0.5); loss = S(w l) / w1.
+ *  G6 g_i = (((k_i w_i) / w1) / q) r, k_i = 1 if s < 1, else 0.5 / sqrt(s + 2^-23); dt = S(g); G[a][b] = S(g[a] X[b]); then through G4 on
+ *     one lane, with Gx, Gy, Gz the columns of G: Gx += y X Gz; Gy += Gz X x; du = (Gy - y (y.Gy)) / |u| (Gy / 1e-8 where |u| < 1e-8);
+ *     dc = -(du.x); Gx -= c du; t1 = dc / n2; Gx += t1 b; db = du + t1 x; where x.x >= 1e-8: dn2 = -((dc (x.b)) / (n2 n2)), Gx += (2 dn2) x;
+ *     da = (Gx - x (x.Gx)) / |a| (Gx / 1e-8 where |a| < 1e-8).  grad = (da, db, dt).
+ *  G7 Adam, f7's B7 on the nine parameters: beta = (0.9, 0.999), eps = 1e-8, step size lr, and lr = lr gamma after every step.
+ *  G8 for i = 0 .. max_iter - 1: evaluate loss and grad at p (log row i = p, loss); loss not finite: status 3, stop; loss < 1e-7: stop;
+ *     the Adam step; a parameter not finite: status 3, stop; if |loss_prev - loss| < loss_prev ratio: break_count += 1 (cumulative, never
+ *     reset) and stop once break_count >= max_break; loss_prev = loss.  loss_prev starts as iteration 0's loss, so iteration 0 counts
+ *     whenever its loss and ratio are > 0.  iterations = i at the stop, max_iter - 1 without one; loss = the last evaluated;
+ *     T = [R(p) t; 0 1] of the parameters after the last step (status 3: of the initial parameters).
+ *  G9 status 1: L == 0; status 2: w1 < wsum_threshold (the caller's safeguard is due; DGR passes max(4000, m) clip, :407).  Both: the
+ *     identity, nothing run, iterations = break_count = 0, loss = 0, log all +0.0.
+ * G10 no floating-point atomics; the same input gives the same bits on every run, whatever the scratch held, alone or as pair k of a batch.
+ * Deviations: parameters and moments are fp64 (the reference's are float32); non-finite rows and rows with w <= 0 are dead (the reference
+ * propagates NaN and lets negative weights pull); the SVD failure of :428 cannot happen.                                             */
+typedef struct lr_dgr_params {
+    uint32_t struct_size;        /* = sizeof(lr_dgr_params)                                                                         */
+    int32_t  max_iter;           /* 1000 (registration.py:138); 1..1000                                                             */
+    int32_t  max_break;          /* 20 (max_break_count); >= 1                                                                      */
+    int32_t  reserved;           /* 0                                                                                               */
+    double   quantization_size;  /* q; DGR passes 2 * voxel_size (:419); positive and finite                                        */
+    double   lr;                 /* 0.1 (:163); positive and finite                                                                 */
+    double   gamma;              /* 0.999 (:164); (0, 1]                                                                            */
+    double   ratio;              /* break_threshold_ratio: 1e-5, DGR passes 1e-4 (:418); >= 0, finite                               */
+    double   clip;               /* clip_weight_thresh; >= 0, finite                                                                */
+    double   wsum_threshold;     /* G9; >= 0, finite                                                                                */
+} lr_dgr_params;
+
+/* Written to device memory by lr_dgr_refine / _batch (160 bytes). */
+typedef struct lr_dgr_result {
+    double   T[16];              /* src -> tgt, row-major                                                                           */
+    double   loss;               /* the last evaluated loss                                                                         */
+    double   w1;                 /* S(w) over the live rows                                                                         */
+    int32_t  iterations;         /* G8                                                                                              */
+    int32_t  break_count;
+    int32_t  L;                  /* live rows                                                                                       */
+    int32_t  status;             /* 0 refined, 1 no live row, 2 w1 < wsum_threshold, 3 a non-finite loss or parameter               */
+} lr_dgr_result;
+
+/* Caller-owned device scratch per pair for up to max_m correspondences (0 when max_m is outside 0..32768). */
+LR_API size_t lr_dgr_scratch_bytes(int max_m);
+/* weights (nullable): device float32 [m].  T_init (nullable): device float64 [16], row-major 4x4.  log_out (nullable, this entry only):
+ * device float64 [max_iter][10], row i = the nine parameters iteration i was evaluated at and its loss, rows past the last evaluated one
+ * +0.0.  Refusals: LR_EINVAL before any launch, lr_last_error naming the argument (struct_size, a parameter out of range, m > 32768, and
+ * the front end's).  No host synchronisation, no allocation: graph-capturable.                                                       */
+LR_API int lr_dgr_refine(const float *src, const float *tgt, int m, const int32_t *m_dev, const float *weights, const double *T_init,
+                         const lr_dgr_params *p, lr_dgr_result *result, double *log_out, void *scratch, size_t scratch_bytes, void *stream);
+/* npairs (1..64) ragged pairs; the arrays are HOST arrays of length npairs (m_dev, weights, T_init and their entries may be NULL);
+ * scratch >= npairs * lr_dgr_scratch_bytes(max m).  Pair k is bit-identical to lr_dgr_refine on that pair.                           */
+LR_API int lr_dgr_refine_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
+                               const float *const *weights, const double *const *T_init, const lr_dgr_params *p, lr_dgr_result *results,
+                               void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */
 LR_API int lr_workspace_timing(lr_workspace *ws, int enable);

@@ -30,6 +30,7 @@ SYMBOLS = [
     "lr_pdsc_solve_scratch_bytes", "lr_pdsc_solve", "lr_pdsc_solve_batch",
     "lr_pdsc_register_scratch_bytes", "lr_pdsc_register", "lr_pdsc_register_batch",
     "lr_fcgf_weights_bytes", "lr_fcgf_scratch_bytes", "lr_fcgf_extract",
+    "lr_dgr_scratch_bytes", "lr_dgr_refine", "lr_dgr_refine_batch",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -215,6 +216,20 @@ class FcgfResult(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("n", ctypes.c_int32), ("n_tap", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class DgrParams(KeywordParams):
+    """lr_dgr_params with GlobalRegistration's defaults (DGR/core/registration.py:135-144, :163-164) as defaults; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("max_iter", ctypes.c_int32), ("max_break", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("quantization_size", ctypes.c_double), ("lr", ctypes.c_double), ("gamma", ctypes.c_double), ("ratio", ctypes.c_double),
+                ("clip", ctypes.c_double), ("wsum_threshold", ctypes.c_double)]
+    DEFAULTS = dict(max_iter=1000, max_break=20, quantization_size=1.0, lr=0.1, gamma=0.999, ratio=1e-5, clip=0.0, wsum_threshold=0.0)
+
+
+class DgrResult(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_double * 16), ("loss", ctypes.c_double), ("w1", ctypes.c_double), ("iterations", ctypes.c_int32),
+                ("break_count", ctypes.c_int32), ("L", ctypes.c_int32), ("status", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(DgrParams) == 64 and ctypes.sizeof(DgrResult) == 160
 assert ctypes.sizeof(FcgfParams) == 12 and ctypes.sizeof(FcgfResult) == 16
 assert ctypes.sizeof(PdscSolveParams) == 64 and ctypes.sizeof(PdscSolveResult) == 304
 assert ctypes.sizeof(PdscParams) == 16 and ctypes.sizeof(PdscResult) == 16
@@ -330,6 +345,10 @@ def lib():
         L.lr_fcgf_weights_bytes.argtypes = [ci]
         L.lr_fcgf_scratch_bytes.argtypes = [ci]
         L.lr_fcgf_extract.argtypes = [vp, vp, ci, vp, sz, ctypes.POINTER(FcgfParams), vp, vp, vp, vp, sz, vp]
+        pd = ctypes.POINTER(DgrParams)
+        L.lr_dgr_scratch_bytes.argtypes = [ci]
+        L.lr_dgr_refine.argtypes = [vp, vp, ci, vp, vp, vp, pd, vp, vp, vp, sz, vp]
+        L.lr_dgr_refine_batch.argtypes = [ci, pp, pp, ip, pp, pp, pp, pd, vp, vp, sz, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

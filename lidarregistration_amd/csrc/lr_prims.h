@@ -1,5 +1,6 @@
-// The integer building blocks the cloud-level kernels share (lr_filter.hip, lr_icp.hip, lr_voxel.hip, lr_overlap.hip, lr_sm.hip,
-// lr_teaser.hip; not part of the ABI): wave and block scans, flag counting and ordered compaction, the 64-bit mix hash.  Device only,
+// The building blocks the cloud-level kernels share (lr_filter.hip, lr_icp.hip, lr_voxel.hip, lr_overlap.hip, lr_sm.hip,
+// lr_teaser.hip, lr_dgr.hip; not part of the ABI): wave and block scans, flag counting and ordered compaction, the wave levels of a fixed
+// summation tree, the 64-bit mix hash.  Device only,
 // inlined, no state; a wave is 64 lanes.  The NN files (lr_nn16*.hip) and the RANSAC files (lr_ransac.hip, lr_score.hip, lr_lo.hip) keep their own spellings: the helper re-schedules their kernels.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -82,6 +83,13 @@ __device__ __forceinline__ void lr_block_exscan(int32_t *a, size_t len)
         if (tid == 1023) s_carry = run;
         __syncthreads();
     }
+}
+// the levels h = 32 .. 1 of a fixed summation tree inside a wave: v_l = v_l + v_(l + h); lane 0 ends with the sum (float, double)
+template <typename T> __device__ __forceinline__ T lr_wave_tree_sum(T v)
+{
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_down(v, h);
+    return v;
 }
 // 64-bit finaliser mix (MurmurHash3's fmix64): every input bit reaches every output bit
 __device__ __forceinline__ unsigned long long lr_mix64(unsigned long long k)
