@@ -136,7 +136,6 @@ __device__ __forceinline__ double bb_lane(double v, int j)
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double bb_row(const double *M, int a, double x, double y, double z) { return (M[3 * a] * x + M[3 * a + 1] * y) + M[3 * a + 2] * z; }
-__device__ __forceinline__ double bb_dot(const double *u, const double *v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
 
 // B8 from the control block's best parameters
 __device__ static void bb_write_result(const bb_args &g, const bb_ctl *c)
@@ -210,10 +209,10 @@ __global__ void __launch_bounds__(256) bb_pair_kernel(bb_args g)
                 const double *a = g.A + 3 * (size_t)i, *na = g.nA + 3 * (size_t)i, *b = g.B + 3 * (size_t)j, *nb = g.nB + 3 * (size_t)j;
                 const double *bp = Bp + 3 * (size_t)j, *nbp = nBp + 3 * (size_t)j;
                 const double nav[3] = { na[0], na[1], na[2] }, nbv[3] = { nbp[0], nbp[1], nbp[2] };
-                const double s = bb_dot(nav, nbv) < 0.0 ? -1.0 : 1.0;
+                const double s = lr_dot3(nav, nbv) < 0.0 ? -1.0 : 1.0;
                 const double m[3] = { nav[0] + s * nbv[0], nav[1] + s * nbv[1], nav[2] + s * nbv[2] };
                 const double d[3] = { a[0] - bp[0], a[1] - bp[1], a[2] - bp[2] };
-                const double dot = bb_dot(d, m), ad = fabs(dot);
+                const double dot = lr_dot3(d, m), ad = fabs(dot);
                 v[0] = ad > 1e-15 ? ad : 1e-15;
                 if (!(dot * dot < 1e-30)) {
                     const double sg = dot < 0.0 ? -1.0 : 1.0;
@@ -222,7 +221,7 @@ __global__ void __launch_bounds__(256) bb_pair_kernel(bb_args g)
                         const double *D = c->dW + 9 * q;
                         const double u[3] = { bb_row(D, 0, b[0], b[1], b[2]), bb_row(D, 1, b[0], b[1], b[2]), bb_row(D, 2, b[0], b[1], b[2]) };
                         const double w[3] = { s * bb_row(D, 0, nb[0], nb[1], nb[2]), s * bb_row(D, 1, nb[0], nb[1], nb[2]), s * bb_row(D, 2, nb[0], nb[1], nb[2]) };
-                        v[1 + q] = sg * (bb_dot(d, w) - bb_dot(u, m));
+                        v[1 + q] = sg * (lr_dot3(d, w) - lr_dot3(u, m));
                     }
 #pragma unroll
                     for (int a3 = 0; a3 < 3; ++a3) v[4 + a3] = sg * (-m[a3]);

@@ -1,9 +1,12 @@
-// The front end the correspondence-set solvers share (lr_teaser.hip, lr_sm.hip; not part of the ABI): a batched call takes per-pair
-// correspondence sets a[i] <-> b[i] with an optional live count on the device, nullable per-pair outputs and one caller-owned scratch
-// of npairs arenas.  What differs between the back ends is their params, their arena layout and their kernels.  The align and arena
+// The front end the correspondence-set back ends share (lr_teaser.hip, lr_sm.hip, lr_pdsc.hip, lr_pdsc_solve.hip, lr_dgr.hip; not part
+// of the ABI): a batched call takes per-pair correspondence sets a[i] <-> b[i] with an optional live count on the device, nullable
+// per-pair outputs and one caller-owned scratch of npairs arenas.  What differs between the back ends is their params, their arena
+// layout and their kernels; the device section holds what those kernels read of a pair in the same way: the live count, a row with its
+// finiteness, and the length difference d(i,j) of the compatibility measures (SM's c, PointDSC's E3).  The align and arena
 // pointer helpers, the refusal macro and the scratch checks are those of every caller-owned scratch (lr_scratch.h).
 #pragma once
 #include "lr_scratch.h"
+#include <float.h>
 
 #define CS_MAX_M 32768               // correspondences per pair
 // One pair of a batched call.  The table travels BY VALUE into the back end's setup kernel (no host copy, graph-capturable):
@@ -20,6 +23,30 @@ static_assert(sizeof(cs_desc_table) + 256 <= 4096, "the descriptor table no long
 #ifdef __HIPCC__
 // the pair's live count: m_dev clamped to 0..m
 __device__ __forceinline__ int cs_live_m(const cs_desc &d) { const int v = d.m_dev ? *d.m_dev : d.m; return v < 0 ? 0 : (v < d.m ? v : d.m); }
+// row i of a pair, r = (a_i, b_i); true iff all six are finite (false for NaN and inf).  A back end's further conditions (a weight, a
+// confidence, a feature) stay at its call site.
+__device__ __forceinline__ bool cs_load_row(const float *a, const float *b, int i, float (&r)[6])
+{
+    a += (size_t)3 * i; b += (size_t)3 * i;
+    r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = b[0]; r[4] = b[1]; r[5] = b[2];
+    bool ok = true;
+    for (int k = 0; k < 6; ++k) ok = ok && fabsf(r[k]) <= FLT_MAX;
+    return ok;
+}
+// d = |a_i - a_j| - |b_i - b_j| of the row p = (a_i, b_i) and another one's six scalars, in the contracts' fp32 order: direct
+// differences, (dx dx + dy dy) + dz dz, two correctly rounded square roots, then the subtraction (-ffp-contract=off: nothing is fused)
+__device__ __forceinline__ float cs_len_diff(const float (&p)[6], float a0, float a1, float a2, float b0, float b1, float b2)
+{
+    const float ax = p[0] - a0, ay = p[1] - a1, az = p[2] - a2, bx = p[3] - b0, by = p[4] - b1, bz = p[5] - b2;
+    const float la = sqrtf((ax * ax + ay * ay) + az * az), lb = sqrtf((bx * bx + by * by) + bz * bz);
+    return la - lb;
+}
+// PointDSC's E3 for one (query, key): max(0, 1 + nk d^2), nk = (float)(-1 / sigma_d^2)
+__device__ __forceinline__ float cs_compat(const float (&p)[6], float a0, float a1, float a2, float b0, float b1, float b2, float nk)
+{
+    const float d = cs_len_diff(p, a0, a1, a2, b0, b1, b2);
+    return fmaxf(0.0f, fmaf(d * d, nk, 1.0f));
+}
 #endif
 
 // What the front needs to know of a back end: its batched entry point by name, what the call's scratch takes as the messages word it

@@ -70,20 +70,6 @@ __global__ void dg_ctl_kernel(cs_desc_table t, dg_args g, int npairs)
     c->m = cs_live_m(d);
 }
 
-// G2 with a barrier per level (the setup's sums; the loop has its own form of the same tree)
-__device__ __forceinline__ double dg_block_sum(double v, double *s)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    s[tid] = v;
-    __syncthreads();
-    for (int h = DG_NB / 2; h >= 1; h >>= 1) {
-        if (tid < h) s[tid] = s[tid] + s[tid + h];
-        __syncthreads();
-    }
-    return s[0];
-}
-
 // ---- G1, G3, the decision of G9 ---------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(DG_NB) dg_setup_kernel(dg_ext_table e, dg_args g, dg_consts P, double *log)
 {
@@ -103,6 +89,7 @@ __global__ void __launch_bounds__(DG_NB) dg_setup_kernel(dg_ext_table e, dg_args
         float r[6], w = 0.0f;
         bool live = false;
         if (i < m) {
+            // (cs_load_row in this file's own spelling: the helper's load order re-schedules the kernel)
             for (int x = 0; x < 3; ++x) { r[x] = c->a[(size_t)3 * i + x]; r[3 + x] = c->b[(size_t)3 * i + x]; }
             w = wp ? wp[i] : 1.0f;
             live = fabsf(w) <= FLT_MAX && w > 0.0f && (double)w >= P.clip;      // (false for NaN and inf)
@@ -121,7 +108,7 @@ __global__ void __launch_bounds__(DG_NB) dg_setup_kernel(dg_ext_table e, dg_args
 
     double v = 0.0;
     for (int i = tid; i < L; i += DG_NB) v = v + (double)rec[(size_t)i * 8 + 6];
-    const double w1 = dg_block_sum(v, s_red);
+    const double w1 = lr_block_tree_sum<DG_NB>(v, s_red);
     const int status = L == 0 ? 1 : (w1 < P.wsum ? 2 : 0);
 
     double mom[16];
@@ -141,7 +128,7 @@ __global__ void __launch_bounds__(DG_NB) dg_setup_kernel(dg_ext_table e, dg_args
                 for (int y = 0; y < 3; ++y) acc[7 + 3 * x + y] = acc[7 + 3 * x + y] + wx * (double)r[3 + y];
             }
         }
-        for (int k = 0; k < 16; ++k) mom[k] = dg_block_sum(acc[k], s_red);
+        for (int k = 0; k < 16; ++k) mom[k] = lr_block_tree_sum<DG_NB>(acc[k], s_red);
     }
     if (tid == 0) {
         c->w = wp; c->T_init = Ti; c->log = log;
@@ -163,7 +150,6 @@ __global__ void __launch_bounds__(DG_NB) dg_setup_kernel(dg_ext_table e, dg_args
 // ---- G4 on one lane ---------------------------------------------------------------------------------------------------------------------
 struct dg_rot { double x[3], y[3], z[3], b[3], na, nu, xx, xb, n2, c; };
 
-__device__ __forceinline__ double dg_dot(const double *u, const double *v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
 __device__ __forceinline__ void dg_cross(const double *p, const double *q, double *o)
 {
     o[0] = p[1] * q[2] - p[2] * q[1]; o[1] = p[2] * q[0] - p[0] * q[2]; o[2] = p[0] * q[1] - p[1] * q[0];
@@ -175,16 +161,16 @@ __device__ __forceinline__ void dg_rotation(const double *p, dg_rot &o)
 {
     const double *a = p;
     for (int k = 0; k < 3; ++k) o.b[k] = p[3 + k];
-    o.na = sqrt(dg_dot(a, a));
+    o.na = sqrt(lr_dot3(a, a));
     const double da = dg_clamp(o.na);
     for (int k = 0; k < 3; ++k) o.x[k] = a[k] / da;
-    o.xx = dg_dot(o.x, o.x);
+    o.xx = lr_dot3(o.x, o.x);
     o.n2 = dg_clamp(o.xx);
-    o.xb = dg_dot(o.x, o.b);
+    o.xb = lr_dot3(o.x, o.b);
     o.c = o.xb / o.n2;
     double u[3];
     for (int k = 0; k < 3; ++k) u[k] = o.b[k] - o.c * o.x[k];
-    o.nu = sqrt(dg_dot(u, u));
+    o.nu = sqrt(lr_dot3(u, u));
     const double du = dg_clamp(o.nu);
     for (int k = 0; k < 3; ++k) o.y[k] = u[k] / du;
     dg_cross(o.x, o.y, o.z);
@@ -202,10 +188,10 @@ __device__ __forceinline__ void dg_rotation_back(const dg_rot &o, const double *
     if (o.nu < DG_CLAMP) {
         for (int k = 0; k < 3; ++k) du[k] = Gy[k] / DG_CLAMP;
     } else {
-        const double yg = dg_dot(o.y, Gy);
+        const double yg = lr_dot3(o.y, Gy);
         for (int k = 0; k < 3; ++k) du[k] = (Gy[k] - o.y[k] * yg) / o.nu;
     }
-    const double dc = -dg_dot(du, o.x);
+    const double dc = -lr_dot3(du, o.x);
     for (int k = 0; k < 3; ++k) Gx[k] = Gx[k] - o.c * du[k];
     const double t1 = dc / o.n2;
     for (int k = 0; k < 3; ++k) Gx[k] = Gx[k] + t1 * o.b[k];
@@ -217,7 +203,7 @@ __device__ __forceinline__ void dg_rotation_back(const dg_rot &o, const double *
     if (o.na < DG_CLAMP) {
         for (int k = 0; k < 3; ++k) grad[k] = Gx[k] / DG_CLAMP;
     } else {
-        const double xg = dg_dot(o.x, Gx);
+        const double xg = lr_dot3(o.x, Gx);
         for (int k = 0; k < 3; ++k) grad[k] = (Gx[k] - o.x[k] * xg) / o.na;
     }
 }

@@ -19,16 +19,6 @@
 #include <math.h>
 #include <string.h>
 
-// total order of the doubles as unsigned integers (ov_enc / ov_dec of lr_overlap.hip, which this change leaves as it is)
-__device__ __forceinline__ unsigned long long nn_enc(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double nn_dec(unsigned long long e)
-{
-    return __longlong_as_double((long long)((e >> 63) ? (e & 0x7fffffffffffffffull) : ~e));
-}
 // (d2, j) argmin: smaller d2, then smaller j; j = -1 (nothing yet) loses to every j
 __device__ __forceinline__ void nn_take(double d2, int j, double &best, int &bj)
 {
@@ -73,7 +63,7 @@ __global__ void __launch_bounds__(256) nn_bounds_kernel(nn_args g)
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int a = 0; a < 3; ++a)
-            if (lo[a] <= hi[a]) { atomicMin(&c->lo[a], nn_enc(lo[a])); atomicMax(&c->hi[a], nn_enc(hi[a])); }
+            if (lo[a] <= hi[a]) { atomicMin(&c->lo[a], lr_ord_enc(lo[a])); atomicMax(&c->hi[a], lr_ord_enc(hi[a])); }
         if (nbad) atomicAdd(&c->n1_dropped, __popcll(nbad));
     }
 }
@@ -103,7 +93,7 @@ __global__ void nn_grid_kernel(nn_args g)
     if (c->n1_live <= 0) { c->n1_live = 0; return; }
     double ext[3], E = 0.0;
     for (int a = 0; a < 3; ++a) {
-        c->blo[a] = nn_dec(c->lo[a]); c->bhi[a] = nn_dec(c->hi[a]);
+        c->blo[a] = lr_ord_dec(c->lo[a]); c->bhi[a] = lr_ord_dec(c->hi[a]);
         ext[a] = c->bhi[a] - c->blo[a];
         E = ext[a] > E ? ext[a] : E;
     }

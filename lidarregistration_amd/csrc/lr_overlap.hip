@@ -111,16 +111,6 @@ static size_t ov_make_args(ov_args *g, size_t n0, size_t n1, int clouds)
 }
 
 __device__ __forceinline__ ov_cloud *ov_ctl(const ov_args &g, int pair, int cl) { return &lr_ptr<ov_pair>(g, pair, 0)->c[cl]; }
-// total order of the doubles as unsigned integers
-__device__ __forceinline__ unsigned long long ov_enc(double v)
-{
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double ov_dec(unsigned long long e)
-{
-    return __longlong_as_double((long long)((e >> 63) ? (e & 0x7fffffffffffffffull) : ~e));
-}
 
 // ---- setup: descriptors by value -> control blocks (no host copy, graph-capturable) ------------------------------------------
 __global__ void ov_setup_kernel(ov_desc_table t, ov_args g, int npairs)
@@ -188,7 +178,7 @@ __global__ void __launch_bounds__(256) ov_xform_kernel(ov_args g)
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int a = 0; a < 3; ++a)
-            if (lo[a] <= hi[a]) { atomicMin(&c->lo[a], ov_enc(lo[a])); atomicMax(&c->hi[a], ov_enc(hi[a])); }
+            if (lo[a] <= hi[a]) { atomicMin(&c->lo[a], lr_ord_enc(lo[a])); atomicMax(&c->hi[a], lr_ord_enc(hi[a])); }
         if (nbad) atomicAdd(&c->dropped, __popcll(nbad));
     }
 }
@@ -202,7 +192,7 @@ __global__ void ov_bounds_kernel(ov_args g)
     if (kept <= 0) status = 1;
     else {
         for (int a = 0; a < 3; ++a) {
-            const double lo = ov_dec(c->lo[a]), hi = ov_dec(c->hi[a]);
+            const double lo = lr_ord_dec(c->lo[a]), hi = lr_ord_dec(c->hi[a]);
             const double vmb = lo - g.voxel * 0.5;
             c->vmb[a] = vmb;
             if (!((hi - vmb) / g.voxel < OV_CELLS)) status = 2;

@@ -22,6 +22,7 @@
 // No floating-point atomics anywhere: every sum has one order, which depends on the pair's own live M only -- never on the batch the
 // pair is in, on the device, on scheduling or on what the scratch held.
 #include "lr_corrset.h"
+#include "lr_prims.h"
 #include <math.h>
 #include <float.h>
 
@@ -130,29 +131,6 @@ __global__ void pd_setup_kernel(cs_desc_table t, pd_args g, int npairs)
 }
 
 // ---- E1, E2: dead rows, the column means, records and the centred input ---------------------------------------------------------
-// fixed-order block sum of one double per thread
-__device__ __forceinline__ double pd_block_sum(double v, double *s)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    s[tid] = v;
-    __syncthreads();
-    for (int h = PD_NB / 2; h >= 1; h >>= 1) {
-        if (tid < h) s[tid] = s[tid] + s[tid + h];
-        __syncthreads();
-    }
-    return s[0];
-}
-
-__device__ __forceinline__ bool pd_load_row(const pd_ctl *c, int i, float (&r)[6])
-{
-    const float *a = c->a + (size_t)3 * i, *b = c->b + (size_t)3 * i;
-    r[0] = a[0]; r[1] = a[1]; r[2] = a[2]; r[3] = b[0]; r[4] = b[1]; r[5] = b[2];
-    bool ok = true;
-    for (int k = 0; k < 6; ++k) ok = ok && fabsf(r[k]) <= FLT_MAX;      // (false for NaN and inf)
-    return ok;
-}
-
 __global__ void __launch_bounds__(PD_NB) pd_prep_kernel(pd_args g, lr_pdsc_result *results)
 {
     __shared__ double s_red[PD_NB];
@@ -162,18 +140,18 @@ __global__ void __launch_bounds__(PD_NB) pd_prep_kernel(pd_args g, lr_pdsc_resul
     double sum[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 }, cnt = 0.0;
     for (int i = tid; i < m; i += PD_NB) {
         float r[6];
-        if (pd_load_row(c, i, r)) {
+        if (cs_load_row(c->a, c->b, i, r)) {
             for (int k = 0; k < 6; ++k) sum[k] += (double)r[k];
             cnt += 1.0;
         }
     }
     double mean[6];
-    const double n = pd_block_sum(cnt, s_red);
-    for (int k = 0; k < 6; ++k) { const double s = pd_block_sum(sum[k], s_red); mean[k] = n > 0.0 ? s / n : 0.0; }
+    const double n = lr_block_tree_sum<PD_NB>(cnt, s_red);
+    for (int k = 0; k < 6; ++k) { const double s = lr_block_tree_sum<PD_NB>(sum[k], s_red); mean[k] = n > 0.0 ? s / n : 0.0; }
     float *rec = lr_ptr<float>(g, pair, g.L.rec), *x0 = lr_ptr<float>(g, pair, g.L.x0);
     for (int i = tid; i < m; i += PD_NB) {
         float r[6];
-        const bool ok = pd_load_row(c, i, r);
+        const bool ok = cs_load_row(c->a, c->b, i, r);
         for (int k = 0; k < 6; ++k) {
             rec[(size_t)i * 8 + k] = ok ? r[k] : 0.0f;
             x0[(size_t)i * PD_IN + k] = ok ? (float)((double)r[k] - mean[k]) : 0.0f;
@@ -265,15 +243,6 @@ __global__ void __launch_bounds__(256) pd_rowtile_kernel(pd_args g, pd_layer y, 
 }
 
 // ---- the hot path -----------------------------------------------------------------------------------------------------------------
-// E3 for one (query, key): nk = (float)(-1 / sigma_d^2)
-__device__ __forceinline__ float pd_compat(const float (&p)[6], const pd_f32x4 r0, const pd_f32x4 r1, float nk)
-{
-    const float ax = p[0] - r0[0], ay = p[1] - r0[1], az = p[2] - r0[2], bx = p[3] - r0[3], by = p[4] - r1[0], bz = p[5] - r1[1];
-    const float la = sqrtf((ax * ax + ay * ay) + az * az), lb = sqrtf((bx * bx + by * by) + bz * bz);
-    const float d = la - lb;
-    return fmaxf(0.0f, fmaf(d * d, nk, 1.0f));
-}
-
 struct pd_tile_regs { pd_f32x4 k[4], v[4], r; };
 
 // tile t of the chunk [k0, k1) -> registers (keys at and past k1: zeros, i.e. records that are not live)
@@ -365,7 +334,7 @@ __global__ void __launch_bounds__(256) pd_attn_kernel(pd_args g, float nk, float
         for (int r = 0; r < 16; ++r) {
             const int key = (r & 3) + 8 * (r >> 2) + 4 * h;
             const pd_f32x4 r0 = *reinterpret_cast<const pd_f32x4 *>(&s_r[buf][key * 8]), r1 = *reinterpret_cast<const pd_f32x4 *>(&s_r[buf][key * 8 + 4]);
-            const float cij = pd_compat(own, r0, r1, nk);
+            const float cij = cs_compat(own, r0[0], r0[1], r0[2], r0[3], r1[0], r1[1], nk);
             x[r] = r1[2] > 0.0f ? cij * (S[r] * qscale) : -INFINITY;
             tmax = fmaxf(tmax, x[r]);
         }

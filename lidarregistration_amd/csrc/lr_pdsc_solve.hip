@@ -164,11 +164,10 @@ __global__ void __launch_bounds__(256) ps_prep_kernel(ps_args g)
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= c->m) return;
     float r[6];
-    for (int x = 0; x < 3; ++x) { r[x] = c->a[(size_t)3 * i + x]; r[3 + x] = c->b[(size_t)3 * i + x]; }
+    const bool finite = cs_load_row(c->a, c->b, i, r);
     const float cf = c->conf[i];
     const ps_f32x2 f = *reinterpret_cast<const ps_f32x2 *>(c->feat + (size_t)i * PS_C + 2 * lane);
-    bool ok = fabsf(cf) <= FLT_MAX && fabsf(f[0]) <= FLT_MAX && fabsf(f[1]) <= FLT_MAX;      // (false for NaN and inf)
-    for (int x = 0; x < 6; ++x) ok = ok && fabsf(r[x]) <= FLT_MAX;
+    const bool ok = fabsf(cf) <= FLT_MAX && fabsf(f[0]) <= FLT_MAX && fabsf(f[1]) <= FLT_MAX && finite;      // (false for NaN and inf)
     const bool live = __all(ok);
     const float nrm = sqrtf(ps_wave_sum(f[0] * f[0] + f[1] * f[1]));
     const float den = fmaxf(nrm, 1e-12f);
@@ -437,15 +436,6 @@ __global__ void __launch_bounds__(256) ps_merge_kernel(ps_args g, int k)
 }
 
 // ---- S5, S6, S7: a wave per seed --------------------------------------------------------------------------------------------------------
-// E3 (pd_compat of lr_pdsc.hip)
-__device__ __forceinline__ float ps_compat(const float *p, const float *r, float nk)
-{
-    const float ax = p[0] - r[0], ay = p[1] - r[1], az = p[2] - r[2], bx = p[3] - r[3], by = p[4] - r[4], bz = p[5] - r[5];
-    const float la = sqrtf((ax * ax + ay * ay) + az * az), lb = sqrtf((bx * bx + by * by) + bz * bz);
-    const float d = la - lb;
-    return fmaxf(0.0f, fmaf(d * d, nk, 1.0f));
-}
-
 __global__ void __launch_bounds__(64) ps_seedfit_kernel(ps_args g, ps_consts P)
 {
     __shared__ float s_f[PS_KMAX * PS_FS];
@@ -481,7 +471,7 @@ __global__ void __launch_bounds__(64) ps_seedfit_kernel(ps_args g, ps_consts P)
 #pragma unroll
         for (int x = 0; x < PS_C; ++x) dot = fmaf(fa[x], s_f[b * PS_FS + x], dot);
         const float fs = fmaxf(0.0f, fmaf(1.0f - dot, P.nk_f, 1.0f));
-        s_M[a][b] = (in && a != b) ? fs * ps_compat(own, s_p[b], P.nk_d) : 0.0f;
+        s_M[a][b] = (in && a != b) ? fs * cs_compat(own, s_p[b][0], s_p[b][1], s_p[b][2], s_p[b][3], s_p[b][4], s_p[b][5], P.nk_d) : 0.0f;
     }
     // S6
     float v = in ? 1.0f : 0.0f;
@@ -577,20 +567,6 @@ __global__ void __launch_bounds__(256) ps_score_kernel(ps_args g, double thr)
 }
 
 // ---- the best seed, labels, S9, the result ------------------------------------------------------------------------------------------
-// fixed-order block sum of one double per thread (E2's tree)
-__device__ __forceinline__ double ps_block_sum(double v, double *s)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    s[tid] = v;
-    __syncthreads();
-    for (int h = PS_NB / 2; h >= 1; h >>= 1) {
-        if (tid < h) s[tid] = s[tid] + s[tid + h];
-        __syncthreads();
-    }
-    return s[0];
-}
-
 __global__ void __launch_bounds__(PS_NB) ps_final_kernel(ps_args g, ps_consts P, lr_pdsc_solve_result *results)
 {
     __shared__ double s_red[PS_NB];
@@ -662,9 +638,9 @@ __global__ void __launch_bounds__(PS_NB) ps_final_kernel(ps_args g, ps_consts P,
             v[0] += w;
             for (int x = 0; x < 6; ++x) v[1 + x] += w * (double)r[x];
         }
-        const double den = ps_block_sum(v[0], s_red) + 1e-6;
+        const double den = lr_block_tree_sum<PS_NB>(v[0], s_red) + 1e-6;
         double cen[6];
-        for (int x = 0; x < 6; ++x) cen[x] = ps_block_sum(v[1 + x], s_red) / den;
+        for (int x = 0; x < 6; ++x) cen[x] = lr_block_tree_sum<PS_NB>(v[1 + x], s_red) / den;
         for (int x = 0; x < 9; ++x) v[x] = 0.0;
         for (int i = tid; i < m; i += PS_NB) {
             const float *r = rec + (size_t)i * 8;
@@ -676,7 +652,7 @@ __global__ void __launch_bounds__(PS_NB) ps_final_kernel(ps_args g, ps_consts P,
                 for (int y = 0; y < 3; ++y) v[3 * x + y] += (w * ((double)r[x] - cen[x])) * ((double)r[3 + y] - cen[3 + y]);
         }
         double H[3][3];
-        for (int x = 0; x < 9; ++x) H[x / 3][x % 3] = ps_block_sum(v[x], s_red);
+        for (int x = 0; x < 9; ++x) H[x / 3][x % 3] = lr_block_tree_sum<PS_NB>(v[x], s_red);
         if (tid == 0) { double Tn[16]; lr_rt_from_cov(H, cen, cen + 3, Tn); for (int x = 0; x < 16; ++x) s_T[x] = Tn[x]; }
         __syncthreads();
         for (int x = 0; x < 12; ++x) T[x] = s_T[x];

@@ -1,7 +1,7 @@
-// The building blocks the cloud-level kernels share (lr_filter.hip, lr_icp.hip, lr_voxel.hip, lr_overlap.hip, lr_sm.hip,
-// lr_teaser.hip, lr_dgr.hip; not part of the ABI): wave and block scans, flag counting and ordered compaction, the wave levels of a fixed
-// summation tree, the 64-bit mix hash.  Device only,
-// inlined, no state; a wave is 64 lanes.  The NN files (lr_nn16*.hip) and the RANSAC files (lr_ransac.hip, lr_score.hip, lr_lo.hip) keep their own spellings: the helper re-schedules their kernels.
+// The building blocks the cloud-level kernels share (lr_filter.hip, lr_icp.hip, lr_voxel.hip, lr_overlap.hip, lr_nn3.hip, lr_bbrf.hip,
+// lr_sm.hip, lr_teaser.hip, lr_pdsc.hip, lr_pdsc_solve.hip, lr_dgr.hip; not part of the ABI): wave and block scans, flag counting and
+// ordered compaction, the fixed summation tree over a block and its wave levels, the total order of the doubles as integers, the
+// three-term dot product, the 64-bit mix hash.  Device only, inlined, no state; a wave is 64 lanes.  The NN files (lr_nn16*.hip) and the RANSAC files (lr_ransac.hip, lr_score.hip, lr_lo.hip) keep their own spellings: the helper re-schedules their kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -91,6 +91,36 @@ template <typename T> __device__ __forceinline__ T lr_wave_tree_sum(T v)
     for (int h = 32; h >= 1; h >>= 1) v = v + __shfl_down(v, h);
     return v;
 }
+// The fixed summation tree over a block of n threads (a power of two; the kernel is launched with exactly n), one double per thread:
+// s[t] = s[t] + s[t + h] for h = n / 2 .. 1, a barrier per level; every thread returns the sum.  s: n doubles of LDS, the caller's.
+// The ORDER is contract, not an implementation choice: G2 (DGR), E2 (PointDSC) and DESIGN.md §11.1 (SM) state this tree, and the numpy
+// restatements the kernels are held to bit for bit add in it.  (dg_loop_kernel keeps its own in-loop form of the same tree.)
+// <NT>: the width at compile time, what every caller but one uses; sm_fit_kernel passes blockDim.x.
+__device__ __forceinline__ double lr_block_tree_sum(double v, double *s, int n)
+{
+    const int tid = threadIdx.x;
+    __syncthreads();
+    s[tid] = v;
+    __syncthreads();
+    for (int h = n / 2; h >= 1; h >>= 1) {
+        if (tid < h) s[tid] = s[tid] + s[tid + h];
+        __syncthreads();
+    }
+    return s[0];
+}
+template <int NT> __device__ __forceinline__ double lr_block_tree_sum(double v, double *s) { return lr_block_tree_sum(v, s, NT); }
+// the total order of the doubles as unsigned integers (for atomicMin / atomicMax over doubles), and back
+__device__ __forceinline__ unsigned long long lr_ord_enc(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double lr_ord_dec(unsigned long long e)
+{
+    return __longlong_as_double((long long)((e >> 63) ? (e & 0x7fffffffffffffffull) : ~e));
+}
+// u . v of three doubles; the association (u0 v0 + u1 v1) + u2 v2 is what the fp64 restatements evaluate
+__device__ __forceinline__ double lr_dot3(const double *u, const double *v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
 // 64-bit finaliser mix (MurmurHash3's fmix64): every input bit reaches every output bit
 __device__ __forceinline__ unsigned long long lr_mix64(unsigned long long k)
 {

@@ -133,9 +133,7 @@ __global__ void __launch_bounds__(256) sm_pack_kernel(sm_args g)
 template <bool DIAG>
 __device__ __forceinline__ float sm_elem(const float (&p)[6], const sm_f32x8 r, float nk, float acc, int i, int j)
 {
-    const float ax = p[0] - r[0], ay = p[1] - r[1], az = p[2] - r[2], bx = p[3] - r[3], by = p[4] - r[4], bz = p[5] - r[5];
-    const float la = sqrtf((ax * ax + ay * ay) + az * az), lb = sqrtf((bx * bx + by * by) + bz * bz);
-    const float d = la - lb;
+    const float d = cs_len_diff(p, r[0], r[1], r[2], r[3], r[4], r[5]);
     float cij = fmaxf(0.0f, fmaf(d * d, nk, 4.5f));
     if (DIAG) cij = (i == j) ? 0.0f : cij;           // the diagonal is decided by index: a duplicated correspondence keeps its 4.5
     return fmaf(cij, r[6], acc);
@@ -208,20 +206,6 @@ sm_matvec_kernel(const float *__restrict__ rec_, float *__restrict__ part_, cons
 
 // ---- normalisation ----------------------------------------------------------------------------------------------------------------
 #define SM_NB 1024
-// fixed-order block sum of one double per thread
-__device__ __forceinline__ double sm_block_sum(double v, double *s)
-{
-    const int tid = threadIdx.x, n = blockDim.x;
-    __syncthreads();
-    s[tid] = v;
-    __syncthreads();
-    for (int h = n / 2; h >= 1; h >>= 1) {
-        if (tid < h) s[tid] = s[tid] + s[tid + h];
-        __syncthreads();
-    }
-    return s[0];
-}
-
 __global__ void __launch_bounds__(SM_NB) sm_norm_kernel(sm_args g, int last)
 {
     __shared__ double s_red[SM_NB];
@@ -239,7 +223,7 @@ __global__ void __launch_bounds__(SM_NB) sm_norm_kernel(sm_args g, int last)
         rowsum[i] = s;
         q += s * s;
     }
-    const double den = sqrt(sm_block_sum(q, s_red)) + 1e-6;
+    const double den = sqrt(lr_block_tree_sum<SM_NB>(q, s_red)) + 1e-6;
     float *eig = last ? c->eig_out : nullptr;
     for (int i = tid; i < m; i += SM_NB) {
         const float v = (float)(rowsum[i] / den);
@@ -321,7 +305,7 @@ __global__ void __launch_bounds__(SM_FB) sm_fit_kernel(sm_args g, lr_sm_result *
     double v[9];
     double sw = 0.0;
     for (int k = tid; k < n; k += SM_FB) sw += (double)rec[(size_t)sel[k] * 8 + 6];
-    sw = sm_block_sum(sw, s_red);
+    sw = lr_block_tree_sum(sw, s_red, blockDim.x);
     const int status = (K < 3 || !(sw > 0.0)) ? 1 : 0;
     double T[16];
     for (int i = 0; i < 16; ++i) T[i] = (i % 5 == 0) ? 1.0 : 0.0;
@@ -336,7 +320,7 @@ __global__ void __launch_bounds__(SM_FB) sm_fit_kernel(sm_args g, lr_sm_result *
                 for (int x = 0; x < 3; ++x) { v[x] += w * (double)a[(size_t)3 * i + x]; v[3 + x] += w * (double)b[(size_t)3 * i + x]; }
             }
         }
-        for (int x = 0; x < 6; ++x) cen[x] = sm_block_sum(v[x], s_red) / den;
+        for (int x = 0; x < 6; ++x) cen[x] = lr_block_tree_sum(v[x], s_red, blockDim.x) / den;
         for (int x = 0; x < 9; ++x) v[x] = 0.0;
         for (int k = tid; k < n; k += SM_FB) {
             const int i = sel[k];
@@ -349,7 +333,7 @@ __global__ void __launch_bounds__(SM_FB) sm_fit_kernel(sm_args g, lr_sm_result *
             }
         }
         double H[3][3];
-        for (int x = 0; x < 9; ++x) H[x / 3][x % 3] = sm_block_sum(v[x], s_red);
+        for (int x = 0; x < 9; ++x) H[x / 3][x % 3] = lr_block_tree_sum(v[x], s_red, blockDim.x);
         if (tid == 0) lr_rt_from_cov(H, cen, cen + 3, T);
     }
     if (tid == 0) {

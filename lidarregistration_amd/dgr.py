@@ -10,8 +10,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _ext, devmem
-from .devmem import ptr, read_struct
+from . import _ext, corrset
 from .matching import _f32, _stream
 
 RESULT_BYTES = ctypes.sizeof(_ext.DgrResult)
@@ -28,66 +27,17 @@ def _info(r):
     return dict(status=r.status, iterations=r.iterations, break_count=r.break_count, loss=r.loss, L=r.L, w1=r.w1)
 
 
-class Call:
-    """One lr_dgr_refine_batch call (single=True: lr_dgr_refine, one pair) over len(srcs) pairs ([M_k,3] float32 each, any M_k incl. 0),
-    built once and launched as often as wanted.  weights: per pair None or float32 [M_k]; T_inits: per pair None or a 4x4; ms: the counts
-    passed as m (default: the rows); m_devs: optional device int32 tensors with a smaller live count; log (single only): keep the
-    per-iteration log; poison: fill the scratch with this byte first (test hook); kw: the params."""
-
-    def __init__(self, srcs, tgts, weights=None, T_inits=None, ms=None, m_devs=None, single=False, log=False, poison=None, **kw):
-        L = _ext.lib()
-        self.n = len(srcs)
-        self.srcs = [_f32(s).reshape(-1, 3) for s in srcs]
-        self.tgts = [_f32(t).reshape(-1, 3) for t in tgts]
-        dev = self.srcs[0].device
-        self.ms = [int(s.shape[0]) for s in self.srcs] if ms is None else [int(v) for v in ms]
-        self.weights = None if weights is None else [None if w is None else _f32(w).reshape(-1) for w in weights]
-        self.T_inits = None if T_inits is None else [devmem.T_dev(T, dev) for T in T_inits]
-        self.m_devs = m_devs
-        self.params = params(**kw)
-        self.scratch = devmem.scratch(L.lr_dgr_scratch_bytes(max(self.ms)) * self.n, dev, poison)
-        self.res = torch.zeros(RESULT_BYTES * self.n, dtype=torch.uint8, device=dev)
-        self.log = torch.full((self.params.max_iter, 10), np.nan, dtype=torch.float64, device=dev) if log else None
-        if single:
-            assert self.n == 1
-            self._fn = L.lr_dgr_refine
-            self._args = (ptr(self.srcs[0]), ptr(self.tgts[0]), self.ms[0], ptr(m_devs and m_devs[0]), ptr(self.weights and self.weights[0]),
-                          ptr(self.T_inits and self.T_inits[0]), ctypes.byref(self.params), self.res.data_ptr(), ptr(self.log),
-                          self.scratch.data_ptr(), self.scratch.numel())
-        else:
-            assert not log, "the log belongs to the single-pair entry point"
-            arr = lambda ts: None if ts is None else (ctypes.c_void_p * self.n)(*[ptr(t) for t in ts])
-            self._fn = L.lr_dgr_refine_batch
-            self._args = (self.n, arr(self.srcs), arr(self.tgts), (ctypes.c_int32 * self.n)(*self.ms), arr(m_devs), arr(self.weights),
-                          arr(self.T_inits), ctypes.byref(self.params), self.res.data_ptr(), self.scratch.data_ptr(), self.scratch.numel())
-
-    def launch(self, stream):
-        _ext.check(self._fn(*self._args, stream))
-
-    def timed(self):
-        """launch() on the current stream between two events, synchronised: the device time of the call in ms."""
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        self.launch(_stream())
-        ev1.record()
-        torch.cuda.current_stream().synchronize()
-        return ev0.elapsed_time(ev1)
-
-    def raw(self):
-        """The result blocks as bytes, one per pair (the copy synchronises with the current stream)."""
-        host = self.res.cpu().numpy().tobytes()
-        return [host[k * RESULT_BYTES:(k + 1) * RESULT_BYTES] for k in range(self.n)]
-
-    def results(self):
-        """[(T 4x4 float64, info dict)] per pair (the copy synchronises with the current stream)."""
-        host = self.res.cpu()
-        rs = [read_struct(host, _ext.DgrResult, k) for k in range(self.n)]
-        return [(np.array(r.T[:], np.float64).reshape(4, 4), _info(r)) for r in rs]
+# the refinement as corrset.BatchCall sees it: after the pairs come the weights and the initial transforms (keywords weights, T_inits:
+# per pair None or float32 [M_k] / a 4x4); the single-pair entry point alone keeps the per-iteration log (keyword log)
+SOLVER = corrset.Solver("lr_dgr_refine", "lr_dgr_refine_batch", "lr_dgr_scratch_bytes", (params,), _ext.DgrResult, (), _info,
+                        inputs=(corrset.In("weights", torch.float32, (-1,)), corrset.In("T_inits", torch.float64, (16,))),
+                        extras=(corrset.Out("log", torch.float64, np.nan, 10, lambda m, p: p.max_iter),), extras_flag="log",
+                        extras_msg="the log belongs to the single-pair entry point")
 
 
 def refine_batch(srcs, tgts, weights=None, T_inits=None, ms=None, m_devs=None, poison=None, **kw):
     """lr_dgr_refine_batch: [(T 4x4, info dict)] per pair and the device time of the call in ms."""
-    call = Call(srcs, tgts, weights, T_inits, ms, m_devs, poison=poison, **kw)
+    call = corrset.BatchCall(SOLVER, srcs, tgts, ms, m_devs, poison, weights=weights, T_inits=T_inits, **kw)
     ms_ = call.timed()
     return call.results(), ms_
 
@@ -95,12 +45,12 @@ def refine_batch(srcs, tgts, weights=None, T_inits=None, ms=None, m_devs=None, p
 def refine(src, tgt, weights=None, T_init=None, m_dev=None, log=False, poison=None, **kw):
     """lr_dgr_refine on one weighted correspondence set: (T 4x4 float64, info dict); with log, info["log"] is the [max_iter,10] float64 log
     (row i: the nine parameters iteration i was evaluated at, its loss)."""
-    call = Call([src], [tgt], None if weights is None else [weights], None if T_init is None else [T_init], None,
-                None if m_dev is None else [m_dev], single=True, log=log, poison=poison, **kw)
+    call = corrset.BatchCall(SOLVER, [src], [tgt], None, None if m_dev is None else [m_dev], poison, single=True, log=log,
+                             weights=None if weights is None else [weights], T_inits=None if T_init is None else [T_init], **kw)
     call.launch(_stream())
     T, info = call.results()[0]
     if log:
-        info["log"] = call.log.cpu().numpy()
+        info["log"] = call.extras[0].cpu().numpy()
     return T, info
 
 

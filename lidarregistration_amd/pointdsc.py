@@ -5,16 +5,13 @@ learned pre-filter in front of the RANSAC, SM and TEASER back ends (DESIGN.md §
 (DESIGN.md §17): ``solve``, ``PointDSCModel`` and ``eval_pairs``, the engine of ``python -m test --algo PointDSC``.  The contracts are
 stated in include/lidarreg.h and restated in numpy in tests/pdsc_cpu.py and tests/pdsc_solve_cpu.py.  There is no CPU fallback.
 """
-import ctypes
 import json
 import os
 
 import numpy as np
 import torch
 
-from . import _ext, devmem
-from .devmem import ptr
-from .matching import _f32, _stream
+from . import _ext, corrset, devmem
 
 C = 128                    # channels (fixed)
 IN_DIM, IN_PAD = 6, 8      # input features; rows of the packed first layer (two zero rows)
@@ -132,38 +129,14 @@ class PointDSCEncoder:
         asked for -- None: all; False: none, the call gets NULL for the whole feat_out / conf_out array; a list of bools: NULL for the
         entries that are False.  The tensor of an output that was not asked for comes back with its -1 fill.  Returns [(features
         [m,128], confidence [m], info dict)] with device tensors -- and, with timed, the device time of the call in ms."""
-        L = _ext.lib()
-        n = len(srcs)
-        srcs = [_f32(s).reshape(-1, 3) for s in srcs]; tgts = [_f32(t).reshape(-1, 3) for t in tgts]
-        dev = srcs[0].device
-        ms = [int(s.shape[0]) for s in srcs] if ms is None else [int(v) for v in ms]
-        scratch = devmem.scratch(L.lr_pdsc_scratch_bytes(max(ms)) * n, dev, poison)
-        res = torch.zeros(ctypes.sizeof(_ext.PdscResult) * n, dtype=torch.uint8, device=dev)
-        # (the fills are what an entry the library must not write keeps: tests read them)
-        feats = [torch.full((max(m, 1), C), -1.0, dtype=torch.float32, device=dev) for m in ms]
-        confs = [torch.full((max(m, 1),), -1.0, dtype=torch.float32, device=dev) for m in ms]
-        w = (self.weights.data_ptr(), self.weights.numel() * 4, ctypes.byref(self.params), res.data_ptr())
-        # the output tensors as the call sees them: None for the whole array, or None per entry
-        asked = lambda ts, want: ts if want is None else None if want is False else [t if ok else None for t, ok in zip(ts, want)]
-        fo, co = asked(feats, want_feat), asked(confs, want_conf)
-        if single:
-            assert n == 1
-            fn = L.lr_pdsc_encode
-            args = (ptr(srcs[0]), ptr(tgts[0]), ms[0], ptr(m_devs and m_devs[0]), *w, ptr(fo and fo[0]), ptr(co and co[0]))
-        else:
-            arr = lambda ts: None if ts is None else (ctypes.c_void_p * n)(*[ptr(t) for t in ts])
-            fn = L.lr_pdsc_encode_batch
-            args = (n, arr(srcs), arr(tgts), (ctypes.c_int32 * n)(*ms), arr(m_devs), *w, arr(fo), arr(co))
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-        _ext.check(fn(*args, scratch.data_ptr(), scratch.numel(), _stream()))
-        ev1.record()
-        torch.cuda.current_stream().synchronize()
-        host = res.cpu()
-        infos = [devmem.read_struct(host, _ext.PdscResult, k) for k in range(n)]
-        out = [(feats[k][:m], confs[k][:m], dict(status=r.status, m=r.m, dead=r.dead)) for k, (m, r) in enumerate(zip(ms, infos))]
-        self.last_raw = (feats, confs)
-        return (out, ev0.elapsed_time(ev1)) if timed else out
+        call = corrset.BatchCall(ENCODE, srcs, tgts, ms, m_devs, poison, single, params=(self.params,), **self._blob(), want_feat=want_feat, want_conf=want_conf)
+        t = call.timed()
+        feats, confs = self.last_raw = tuple(call.outs)
+        out = [(feats[k][:m], confs[k][:m], dict(status=r.status, m=r.m, dead=r.dead)) for k, (m, r) in enumerate(zip(call.ms, call.structs()))]
+        return (out, t) if timed else out
+
+    def _blob(self):
+        return dict(blob=self.weights.data_ptr(), blob_bytes=self.weights.numel() * 4)
 
     def encode(self, src, tgt, m_dev=None, poison=None, want_feat=None, want_conf=None):
         """lr_pdsc_encode on one correspondence set: (features [m,128], confidence [m]) as device tensors; want_feat / want_conf = False
@@ -185,46 +158,30 @@ def _solve_info(r):
     return d
 
 
-def _arr(ts, n):
-    return None if ts is None else (ctypes.c_void_p * n)(*[ptr(t) for t in ts])
+_cap = lambda m, p: int(m * p.ratio)        # rows of seeds_out and of the trace arrays
+_FEAT, _CONF = corrset.Out("feat", torch.float32, -1.0, C), corrset.Out("conf", torch.float32, -1.0)
+_LABELS, _SEEDS = corrset.Out("labels", torch.uint8, 255), corrset.Out("seeds", torch.int32, -7, rows=_cap)
+_BLOB = ("blob", "blob_bytes")              # the weight blob's device address and its byte count
+# the three entry-point families as corrset.BatchCall sees them, inputs and outputs in the ABI's order
+ENCODE = corrset.Solver("lr_pdsc_encode", "lr_pdsc_encode_batch", "lr_pdsc_scratch_bytes", (_ext.PdscParams,), _ext.PdscResult, (_FEAT, _CONF),
+                        call_args=_BLOB)
+SOLVE = corrset.Solver("lr_pdsc_solve", "lr_pdsc_solve_batch", "lr_pdsc_solve_scratch_bytes", (solve_params,), _ext.PdscSolveResult, (_LABELS, _SEEDS),
+                       inputs=(corrset.In("feat", torch.float32, (-1, C)), corrset.In("conf", torch.float32, (-1,))),
+                       extras=(corrset.Out("knn", torch.int32, -7, "k", _cap), corrset.Out("weights", torch.float32, -7.0, "k", _cap),
+                               corrset.Out("seed_T", torch.float64, -7.0, 16, _cap), corrset.Out("counts", torch.int32, -7, None, _cap)),
+                       extras_flag="trace", extras_msg="the trace outputs belong to the single call")
+REGISTER = corrset.Solver("lr_pdsc_register", "lr_pdsc_register_batch", "lr_pdsc_register_scratch_bytes", (_ext.PdscParams, solve_params),
+                          _ext.PdscSolveResult, (_FEAT, _CONF, _LABELS, _SEEDS), call_args=_BLOB)
 
 
-def _asked(ts, want):
-    """The output tensors as a call sees them: all, none (False: NULL for the whole array) or NULL per entry (a list of bools)."""
-    return ts if want is None else None if want is False else [t if ok else None for t, ok in zip(ts, want)]
-
-
-class _SolveCall:
-    """The buffers of one lr_pdsc_solve(_batch) / lr_pdsc_register(_batch) call and the read-back of its results."""
-
-    def __init__(self, srcs, tgts, ms, params, dev):
-        self.n = n = len(srcs)
-        self.ms = ms
-        self.params = params
-        self.res = torch.zeros(ctypes.sizeof(_ext.PdscSolveResult) * n, dtype=torch.uint8, device=dev)
-        # (the fills are what an entry the library must not write keeps: tests read them)
-        self.labels = [torch.full((max(m, 1),), 255, dtype=torch.uint8, device=dev) for m in ms]
-        self.caps = [int(m * params.ratio) for m in ms]
-        self.seeds = [torch.full((max(c, 1),), -7, dtype=torch.int32, device=dev) for c in self.caps]
-
-    def results(self):
-        host = self.res.cpu()
-        out = []
-        for k, m in enumerate(self.ms):
-            r = devmem.read_struct(host, _ext.PdscSolveResult, k)
-            info = _solve_info(r)
-            info["seeds"] = self.seeds[k][:max(info["n_seeds"], 0)]
-            out.append((np.array(r.T, np.float64).reshape(4, 4), self.labels[k][:m], info))
-        return out
-
-
-def _timed(fn, args):
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    _ext.check(fn(*args, _stream()))
-    ev1.record()
-    torch.cuda.current_stream().synchronize()
-    return ev0.elapsed_time(ev1)
+def _decode(call, labels, seeds):
+    """[(T, labels [m], info)] of a solve / register call; info["seeds"] are the seeds that were written."""
+    out = []
+    for k, (m, r) in enumerate(zip(call.ms, call.structs())):
+        info = _solve_info(r)
+        info["seeds"] = seeds[k][:max(info["n_seeds"], 0)]
+        out.append((np.array(r.T, np.float64).reshape(4, 4), labels[k][:m], info))
+    return out
 
 
 def solve_batch(srcs, tgts, feats, confs, ms=None, m_devs=None, poison=None, single=False, timed=False, trace=False, want_labels=None,
@@ -233,37 +190,14 @@ def solve_batch(srcs, tgts, feats, confs, ms=None, m_devs=None, poison=None, sin
     ms, m_devs, poison, single as PointDSCEncoder.encode_batch; want_labels / want_seeds as its want_feat.  trace (single only): info
     also carries 'knn' int32 [n_seeds,k], 'weights' float32 [n_seeds,k], 'seed_T' float64 [n_seeds,4,4] and 'counts' int32 [n_seeds].
     Returns [(T 4x4 float64 array, labels uint8 device tensor [m], info dict)] -- and, with timed, the device time of the call in ms."""
-    L = _ext.lib()
-    n = len(srcs)
-    srcs = [_f32(s).reshape(-1, 3) for s in srcs]; tgts = [_f32(t).reshape(-1, 3) for t in tgts]
-    feats = [_f32(f).reshape(-1, C) for f in feats]; confs = [_f32(c).reshape(-1) for c in confs]
-    dev = srcs[0].device
-    ms = [int(s.shape[0]) for s in srcs] if ms is None else [int(v) for v in ms]
-    p = solve_params(**params)
-    call = _SolveCall(srcs, tgts, ms, p, dev)
-    scratch = devmem.scratch(L.lr_pdsc_solve_scratch_bytes(max(ms)) * n, dev, poison)
-    lo, so = _asked(call.labels, want_labels), _asked(call.seeds, want_seeds)
-    tr = None
-    if single:
-        assert n == 1
-        cap, k = max(call.caps[0], 1), p.k
-        if trace:
-            tr = (torch.full((cap, k), -7, dtype=torch.int32, device=dev), torch.full((cap, k), -7.0, dtype=torch.float32, device=dev),
-                  torch.full((cap, 16), -7.0, dtype=torch.float64, device=dev), torch.full((cap,), -7, dtype=torch.int32, device=dev))
-        fn = L.lr_pdsc_solve
-        args = (ptr(srcs[0]), ptr(tgts[0]), ms[0], ptr(m_devs and m_devs[0]), ptr(feats[0]), ptr(confs[0]), ctypes.byref(p), call.res.data_ptr(),
-                ptr(lo and lo[0]), ptr(so and so[0]), *([ptr(t) for t in tr] if tr else [None] * 4), scratch.data_ptr(), scratch.numel())
-    else:
-        assert not trace, "the trace outputs belong to the single call"
-        fn = L.lr_pdsc_solve_batch
-        args = (n, _arr(srcs, n), _arr(tgts, n), (ctypes.c_int32 * n)(*ms), _arr(m_devs, n), _arr(feats, n), _arr(confs, n), ctypes.byref(p),
-                call.res.data_ptr(), _arr(lo, n), _arr(so, n), scratch.data_ptr(), scratch.numel())
-    t = _timed(fn, args)
-    out = call.results()
-    if tr:
-        ns = out[0][2]["n_seeds"]
+    call = corrset.BatchCall(SOLVE, srcs, tgts, ms, m_devs, poison, single, feat=feats, conf=confs, trace=trace, want_labels=want_labels,
+                             want_seeds=want_seeds, **params)
+    t = call.timed()
+    solve_batch.last_raw = tuple(call.outs)
+    out = _decode(call, *call.outs)
+    if trace:
+        ns, tr = out[0][2]["n_seeds"], tuple(call.extras)
         out[0][2].update(knn=tr[0][:ns], weights=tr[1][:ns], seed_T=tr[2][:ns].reshape(-1, 4, 4), counts=tr[3][:ns], raw_trace=tr)
-    solve_batch.last_raw = (call.labels, call.seeds)
     return (out, t) if timed else out
 
 
@@ -292,31 +226,12 @@ class PointDSCModel:
     def register_batch(self, srcs, tgts, ms=None, m_devs=None, poison=None, single=False, timed=False, want_feat=None, want_conf=None):
         """lr_pdsc_register_batch (single: lr_pdsc_register): [(T 4x4 float64 array, labels uint8 device tensor [m], info dict)]; info
         carries 'feat' and 'conf' (device tensors; the -1 fill where want_feat / want_conf did not ask for them)."""
-        L = _ext.lib()
-        enc = self.encoder
-        n = len(srcs)
-        srcs = [_f32(s).reshape(-1, 3) for s in srcs]; tgts = [_f32(t).reshape(-1, 3) for t in tgts]
-        dev = srcs[0].device
-        ms = [int(s.shape[0]) for s in srcs] if ms is None else [int(v) for v in ms]
-        p = solve_params(**self.solve_kw)
-        call = _SolveCall(srcs, tgts, ms, p, dev)
-        scratch = devmem.scratch(L.lr_pdsc_register_scratch_bytes(max(ms)) * n, dev, poison)
-        feats = [torch.full((max(m, 1), C), -1.0, dtype=torch.float32, device=dev) for m in ms]
-        confs = [torch.full((max(m, 1),), -1.0, dtype=torch.float32, device=dev) for m in ms]
-        fo, co = _asked(feats, want_feat), _asked(confs, want_conf)
-        w = (enc.weights.data_ptr(), enc.weights.numel() * 4, ctypes.byref(enc.params), ctypes.byref(p), call.res.data_ptr())
-        if single:
-            assert n == 1
-            fn = L.lr_pdsc_register
-            args = (ptr(srcs[0]), ptr(tgts[0]), ms[0], ptr(m_devs and m_devs[0]), *w, ptr(fo and fo[0]), ptr(co and co[0]),
-                    ptr(call.labels[0]), ptr(call.seeds[0]), scratch.data_ptr(), scratch.numel())
-        else:
-            fn = L.lr_pdsc_register_batch
-            args = (n, _arr(srcs, n), _arr(tgts, n), (ctypes.c_int32 * n)(*ms), _arr(m_devs, n), *w, _arr(fo, n), _arr(co, n),
-                    _arr(call.labels, n), _arr(call.seeds, n), scratch.data_ptr(), scratch.numel())
-        t = _timed(fn, args)
-        out = call.results()
-        for k, m in enumerate(ms):
+        call = corrset.BatchCall(REGISTER, srcs, tgts, ms, m_devs, poison, single, params=(self.encoder.params, solve_params(**self.solve_kw)),
+                                 **self.encoder._blob(), want_feat=want_feat, want_conf=want_conf)
+        t = call.timed()
+        feats, confs, labels, seeds = call.outs
+        out = _decode(call, labels, seeds)
+        for k, m in enumerate(call.ms):
             out[k][2].update(feat=feats[k][:m], conf=confs[k][:m])
         return (out, t) if timed else out
 
@@ -381,7 +296,6 @@ def correspondences_dev(xyz0, xyz1, F0, F1, args, ws, stream):
 def eval_pairs(source, indices, args, device=None, batch=32, nstreams=3, verbose=False):
     """--algo PointDSC over `indices` of `source` (corrset.eval_pairs): ONE lr_pdsc_register_batch per window.  Returns a harness.EvalRun.
     Column 9 = the pair's share of its window's register call (its device time split evenly), as for --algo SM."""
-    from . import corrset
     if str(getattr(args, "solver", "SVD")).upper() == "RANSAC":
         raise ValueError("--solver RANSAC is not built: --algo PointDSC fits by SVD (--solver SVD)")
     snap = getattr(args, "chosen_snapshot", None)

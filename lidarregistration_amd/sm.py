@@ -27,7 +27,8 @@ def _info(r):
 
 
 # the solver as corrset.BatchCall sees it; per-pair outputs in the ABI's order: the eigenvector, the labels
-SOLVER = corrset.Solver("lr_sm", "lr_sm_batch", "lr_sm_scratch_bytes", params, _ext.SmResult, ((torch.float32, -1.0), (torch.uint8, 255)), _info)
+SOLVER = corrset.Solver("lr_sm", "lr_sm_batch", "lr_sm_scratch_bytes", (params,), _ext.SmResult,
+                        (corrset.Out("eig", torch.float32, -1.0), corrset.Out("labels", torch.uint8, 255)), _info)
 
 
 def _decode(call):

@@ -29,7 +29,8 @@ def _info(r):
 
 
 # the solver as corrset.BatchCall sees it; the one per-pair output is the clique (int32, -1 where nothing is written)
-SOLVER = corrset.Solver("lr_teaser", "lr_teaser_batch", "lr_teaser_scratch_bytes", params, _ext.TeaserResult, ((torch.int32, -1),), _info)
+SOLVER = corrset.Solver("lr_teaser", "lr_teaser_batch", "lr_teaser_scratch_bytes", (params,), _ext.TeaserResult,
+                        (corrset.Out("clique", torch.int32, -1),), _info)
 
 
 def _decode(call):

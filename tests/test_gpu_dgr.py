@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from lidarregistration_amd import _ext, dgr
+from lidarregistration_amd import _ext, corrset, dgr
 from tests import dgr_cases as cases
 from tests import dgr_cpu as cpu
 
@@ -199,11 +199,11 @@ def test_batch_equals_one_by_one(n):
         ms[3], ms[10] = 0, 2049
     cs = [dense(m, seed=100 + k) for k, m in enumerate(ms)]
     kw = dict(P, max_iter=30, clip=0.1)
-    call = dgr.Call([c["src"] for c in cs], [c["tgt"] for c in cs], [c["weights"] for c in cs], poison=0xFF, **kw)
+    call = corrset.BatchCall(dgr.SOLVER, [c["src"] for c in cs], [c["tgt"] for c in cs], weights=[c["weights"] for c in cs], poison=0xFF, **kw)
     call.launch(torch.cuda.current_stream().cuda_stream)
     raw, out = call.raw(), call.results()
     for k, c in enumerate(cs):
-        one = dgr.Call([c["src"]], [c["tgt"]], [c["weights"]], single=True, poison=0x00, **kw)
+        one = corrset.BatchCall(dgr.SOLVER, [c["src"]], [c["tgt"]], weights=[c["weights"]], single=True, poison=0x00, **kw)
         one.launch(torch.cuda.current_stream().cuda_stream)
         assert one.raw()[0] == raw[k], k
     for k in (0, n - 1):
@@ -215,7 +215,8 @@ def test_batch_with_T_init_m_dev_and_null_entries():
     T0 = cases.planted(0, 1, 1.0, 0.0, 0.35)["T_gt"]
     m_devs = [None, torch.tensor([777], dtype=torch.int32, device="cuda"), None]
     kw = dict(P, max_iter=20)
-    call = dgr.Call([c["src"] for c in cs], [c["tgt"] for c in cs], [cs[0]["weights"], cs[1]["weights"], None], [None, T0, T0], None, m_devs, poison=0xFF, **kw)
+    call = corrset.BatchCall(dgr.SOLVER, [c["src"] for c in cs], [c["tgt"] for c in cs], None, m_devs, weights=[cs[0]["weights"], cs[1]["weights"], None],
+                             T_inits=[None, T0, T0], poison=0xFF, **kw)
     call.launch(torch.cuda.current_stream().cuda_stream)
     out = call.results()
     same(out[0], cpu.refine(cs[0]["src"], cs[0]["tgt"], cs[0]["weights"], **kw), 0)

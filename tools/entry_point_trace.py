@@ -1,10 +1,11 @@
 """One call of every entry point of liblidarreg.so that launches kernels, at dim 32 and dim 3, and every branch of the RANSAC and NN launch plans: the
-workload behind profiles/host_context_trace.txt, profiles/prims_trace.txt, profiles/ransac_split_trace.txt and profiles/nn_split_trace.txt.  Run it under `rocprofv3 --kernel-trace -- python tools/entry_point_trace.py`, once per library
+workload behind profiles/host_context_trace.txt, profiles/prims_trace.txt, profiles/ransac_split_trace.txt, profiles/nn_split_trace.txt and profiles/corrset_shared_trace.txt.  Run it under `rocprofv3 --kernel-trace -- python tools/entry_point_trace.py`, once per library
 (LIDARREG_LIB names an alternate build), and compare the two kernel traces with tools/trace_compare.py."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from lidarregistration_amd import FR, _ext, matching, overlap, ransac, sm, synth, teaser, voxel
+from lidarregistration_amd import FR, _ext, dgr, matching, overlap, pointdsc, ransac, sm, synth, teaser, voxel
+from tests import pdsc_cases
 from types import SimpleNamespace as Args      # (FR.pair_params supplies the reference's defaults for what is not given)
 
 t = torch.from_numpy
@@ -45,6 +46,17 @@ src, tgt = A[o0.long()].contiguous(), B[o1.long()].contiguous()
 sets = [len(src), 300, 65]
 sm.sm_batch_dev([src[:m] for m in sets], [tgt[:m] for m in sets])
 teaser.teaser_batch_dev([src[:m] for m in sets], [tgt[:m] for m in sets])
+# the rest of that family on the same sets, batched and through the single-pair entry points: lr_pdsc_encode, lr_pdsc_solve (fed the
+# encoder's outputs; with the trace arrays), lr_pdsc_register at two layers of synthetic weights, lr_dgr_refine (with the log)
+S, G = [src[:m] for m in sets], [tgt[:m] for m in sets]
+model = pointdsc.PointDSCModel.from_state_dict(pdsc_cases.shared_weights(2), 2)
+enc = model.encoder.encode_batch(S, G)
+pointdsc.solve_batch(S, G, [f for f, _, _ in enc], [c for _, c, _ in enc])
+model.register_batch(S, G)
+pointdsc.solve(S[0], G[0], *model.encoder.encode(S[0], G[0]), trace=True)
+model.register(S[0], G[0])
+dgr.refine_batch(S, G, max_iter=30)
+dgr.refine(S[0], G[0], log=True, max_iter=30)
 torch.cuda.synchronize()
 # the branches of the RANSAC launch plan (lr_ransac_run) the calls above do not reach
 gc = dict(mode="MNN", codebase="GC", prosac=True, iters=4096)      # GC defaults: exit rule (batches of 1 024, then 3 072 ids), PROSAC, ELC, LO + polish

@@ -49,10 +49,12 @@ def demangle(name):
 pa, br = sys.argv[1], sys.argv[2]
 fa, fb = sorted(f for f in os.listdir(pa) if f.endswith(".s")), sorted(f for f in os.listdir(br) if f.endswith(".s"))
 print("# 1. whole files")
+whole = set()      # the files that are identical as a whole
 for f in fa:
     if f not in fb: print(f"{f[:-2]}.hip: parent only"); continue
     a, b = ([mask(l) for l in open(os.path.join(d, f)).read().split("\n")] for d in (pa, br))
     nd = sum(x != y for x, y in zip(a, b)) + abs(len(a) - len(b))
+    if nd == 0: whole.add(f)
     print(f"{f[:-2]}.hip: " + (f"identical ({len(a)} lines)" if nd == 0 else f"{nd} differing lines of {len(a)}: see 2."))
 print("#\n# 2. kernel by kernel, wherever the kernel lives")
 ka = {n: (f, k) for f in fa for n, k in kernels(os.path.join(pa, f)).items()}
@@ -60,7 +62,7 @@ kb = {n: (f, k) for f in fb for n, k in kernels(os.path.join(br, f)).items()}
 bad = 0
 for f in fa:
     names = [n for n, (g, _) in ka.items() if g == f]
-    if f in fb and all(kb.get(n, ("",))[0] == f for n in names) and [n for n, (g, _) in kb.items() if g == f] == names: continue      # same file, same kernels: covered by 1. unless it differs
+    if f in whole and all(kb.get(n, ("",))[0] == f for n in names) and [n for n, (g, _) in kb.items() if g == f] == names: continue      # identical file, same kernels: covered by 1.
     print(f"{f[:-2]}: {len(names)} kernels in the parent")
     for n in names:
         (_, (ta, ra)) = ka[n]
