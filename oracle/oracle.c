@@ -266,6 +266,15 @@ ORC_API void orc_kabsch_moments(double n, const double sp[3], const double sq[3]
     lr_rt_from_moments(mom, T);
 }
 
+/* Kabsch from a centred covariance and the two centroids the caller formed (PointDSC's S7 keeps its own + 1e-6 in the centroids'
+ * denominators): lr_rt_from_cov behind the C ABI.  H is row-major, H[3 x + y] = sum (w (a_x - ca_x)) (b_y - cb_y).                  */
+ORC_API void orc_rt_from_cov(const double H[9], const double ca[3], const double cb[3], double T[16])
+{
+    double Hm[3][3];
+    for (int k = 0; k < 9; ++k) Hm[k / 3][k % 3] = H[k];
+    lr_rt_from_cov(Hm, ca, cb, T);
+}
+
 /* -------------------------------------------------------------- RANSAC ---- */
 
 typedef struct {

@@ -62,6 +62,9 @@ def lib():
             build()
         _LIB = ctypes.CDLL(so)
         _LIB.orc_num_threads.restype = ctypes.c_int
+        f64p = ctypes.POINTER(ctypes.c_double)
+        _LIB.orc_rt_from_cov.argtypes = [f64p, f64p, f64p, f64p]      # H [9] row-major, ca [3], cb [3] -> T [16]
+        _LIB.orc_rt_from_cov.restype = None
     return _LIB
 
 
