@@ -872,10 +872,39 @@ LR_API size_t lr_fcgf_weights_bytes(int conv1_kernel_size);
 /* Caller-owned device scratch for up to max_n cells (0 when max_n is outside 0..2^20); a constant plus a multiple of max_n rounded up to 64. */
 LR_API size_t lr_fcgf_scratch_bytes(int max_n);
 /* tap_coords: nullable, int32 [n,3], written by a tap only.  scratch: >= lr_fcgf_scratch_bytes(n) bytes, 256-byte aligned, memory of the
- * current device (checked, like the stream).  No host synchronisation, no allocation.                                               */
+ * current device (checked, like the stream).  No host synchronisation, no allocation.  It initialises its tables with three memsets of
+ * a few bytes per cell and is NOT tested under graph capture: a caller who replays graphs uses lr_fcgf_extract_batch (n2), which is
+ * kernel launches only and is.                                                                                   */
 LR_API int lr_fcgf_extract(const int32_t *coords, const float *feat_in, int n, const float *weights, size_t weights_bytes,
                            const lr_fcgf_params *p, lr_fcgf_result *result, float *feat_out, int32_t *tap_coords, void *scratch,
                            size_t scratch_bytes, void *stream);
+
+/* ---- n2: the FCGF feature extractor on up to 64 clouds in one call: one sequence of launches for all of them, as the reference batches
+ * the two clouds of a pair into one sparse tensor (LidarFeatureExtractor.py:166-181).  coords / feat_in / n / feat_out are HOST arrays of
+ * length nclouds, carried by value in a kernel-argument table (nothing the caller must keep alive); feat_in, and any entry of it, may be
+ * NULL = ones.  The weight blob is n1's (F11).  DESIGN.md §18.7.
+ *  B1  sizes: 1 <= nclouds <= 64; 0 <= n[b] <= 2^20; sum of n <= 2^20; p->tap must be 0 (a batch has no tap).
+ *  B2  for every cloud b, feat_out[b] [n_b,32] and results[b] hold exactly the bytes lr_fcgf_extract writes for that cloud alone
+ *      ({status, n = n_b, n_tap = status ? 0 : n_b, reserved = 0}), whatever else is in the batch, at whichever position, and whatever the
+ *      scratch held.  The one deviation: the range limit is |cell| >= 2^18 - 2 on an axis (status 3), where n1's is 2^20 - 2: a cell's
+ *      key carries its cloud (6 bits) next to three 19-bit fields.  n_b = 0: status 0, only the result block is written.
+ *  B3  the status is per cloud.  A cloud with status 2 or 3 (3 wins, as in F9) has its n_b rows set to 0, takes no part in the maps and
+ *      changes no bit of another cloud's output.  The same cell in two clouds is not a duplicate.
+ *  B4  refusals: LR_EINVAL before any launch, lr_last_error naming the argument and, where it applies, the cloud: struct_size,
+ *      conv1_kernel_size, tap != 0, nclouds outside 1..64, an n[b] outside its range or a sum above 2^20, a null coords[b] / feat_out[b]
+ *      with n[b] > 0, null results, null / misaligned / short weights, and the scratch, stream and device rules of n1.
+ *  B5  no host synchronisation, no allocation, graph-capturable; integer atomics only.                                                */
+/* Caller-owned device scratch for nclouds clouds of total_n cells together (0 when nclouds is outside 1..64 or total_n outside 0..2^20). */
+LR_API size_t lr_fcgf_batch_scratch_bytes(int nclouds, int total_n);
+/* results: device, [nclouds].  scratch: >= lr_fcgf_batch_scratch_bytes(nclouds, sum of n) bytes, 256-byte aligned. */
+LR_API int lr_fcgf_extract_batch(int nclouds, const int32_t *const *coords, const float *const *feat_in, const int32_t *n,
+                                 const float *weights, size_t weights_bytes, const lr_fcgf_params *p, lr_fcgf_result *results,
+                                 float *const *feat_out, void *scratch, size_t scratch_bytes, void *stream);
+/* Bench hook, like lr_debug_fake_current_device not for production: one unsynchronised process-wide word.  stage = 1..23 makes every
+ * later lr_fcgf_extract_batch of the process end behind that stage: it still returns LR_OK and writes the result blocks (status as
+ * found), but stores NO features (1: the maps and conv1, what tools/fcgf_bench.py times for the maps / convolutions split of a batch,
+ * which has no tap); 0 restores the contract.  Set it, time, and set it back with no other caller of the library running.         */
+LR_API int lr_debug_fcgf_batch_stop_after(int stage);
 
 /* ---- d1: Deep Global Registration's robust pose refinement over M weighted correspondences src[i] <-> tgt[i] -----------------------
  * Replaces what DeepGlobalRegistration.register does once it has the inlier weights (DGR/core/deep_global_registration.py:403-435): the

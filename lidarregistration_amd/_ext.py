@@ -29,7 +29,7 @@ SYMBOLS = [
     "lr_pdsc_weights_bytes", "lr_pdsc_scratch_bytes", "lr_pdsc_encode", "lr_pdsc_encode_batch",
     "lr_pdsc_solve_scratch_bytes", "lr_pdsc_solve", "lr_pdsc_solve_batch",
     "lr_pdsc_register_scratch_bytes", "lr_pdsc_register", "lr_pdsc_register_batch",
-    "lr_fcgf_weights_bytes", "lr_fcgf_scratch_bytes", "lr_fcgf_extract",
+    "lr_fcgf_weights_bytes", "lr_fcgf_scratch_bytes", "lr_fcgf_extract", "lr_fcgf_batch_scratch_bytes", "lr_fcgf_extract_batch", "lr_debug_fcgf_batch_stop_after",
     "lr_dgr_scratch_bytes", "lr_dgr_refine", "lr_dgr_refine_batch",
 ]
 
@@ -345,6 +345,9 @@ def lib():
         L.lr_fcgf_weights_bytes.argtypes = [ci]
         L.lr_fcgf_scratch_bytes.argtypes = [ci]
         L.lr_fcgf_extract.argtypes = [vp, vp, ci, vp, sz, ctypes.POINTER(FcgfParams), vp, vp, vp, vp, sz, vp]
+        L.lr_fcgf_batch_scratch_bytes.argtypes = [ci, ci]
+        L.lr_debug_fcgf_batch_stop_after.argtypes = [ci]
+        L.lr_fcgf_extract_batch.argtypes = [ci, pp, pp, ip, vp, sz, ctypes.POINTER(FcgfParams), vp, pp, vp, sz, vp]
         pd = ctypes.POINTER(DgrParams)
         L.lr_dgr_scratch_bytes.argtypes = [ci]
         L.lr_dgr_refine.argtypes = [vp, vp, ci, vp, vp, vp, pd, vp, vp, vp, sz, vp]

@@ -38,13 +38,13 @@ static inline int fc_stage_table(int k1, fc_stage *t)      // t[1 .. 23]
 static inline size_t fc_stage_floats(const fc_stage &s) { return (size_t)s.k3 * s.cin * s.cout + 2 * (size_t)s.cout; }
 
 struct fc_layout { size_t keys, val, coords, sort, nbr27, nbr125, dn, up, X, Y, Z, S1, S2, S4, total, m, cap_max; };
-static fc_layout fc_make_layout(size_t max_n)
+static fc_layout fc_make_layout(size_t max_n, size_t ctl_bytes = 256)
 {
     fc_layout L;
     const size_t m = (max_n + 63) & ~size_t(63);      // rows every array is sized for: all sizes below are multiples of 256 bytes
     L.m = m;
     L.cap_max = 4 * m + 1024;                         // lr_cells_capacity(n) < 4 n, or 1024
-    size_t o = 256;                                   // fc_ctl
+    size_t o = ctl_bytes;                             // fc_ctl (the batch entry: fb_ctl)
     L.keys = o;   o += 4 * L.cap_max * 8;
     L.val = o;    o += 4 * L.cap_max * 4;
     L.coords = o; o += 3 * m * 12;                    // levels 1 .. 3
@@ -367,6 +367,39 @@ struct fc_run {
 };
 }
 
+// The 23 stages (F7) on the maps and buffers of R, shared by the two entry points: conv1(X) launches stage 1 into X; done(s, buf, lvl) is
+// told that `buf` holds stage s of level lvl and ends the sequence by returning true.  The network's output is left in Y.
+template <typename Conv1, typename Done> static bool fc_stages(const fc_run &R, Conv1 conv1, Done done)
+{
+    const fc_layout &L = R.L;
+    float *X = R.at<float>(L.X), *Y = R.at<float>(L.Y), *Z = R.at<float>(L.Z), *S1 = R.at<float>(L.S1), *S2 = R.at<float>(L.S2), *S4 = R.at<float>(L.S4);
+    int s = 0;
+    // a residual block: its two stages
+    auto block = [&](const float *in, float *tmp, float *out, int C, int lvl) -> bool {
+        R.conv(s + 1, in, C, nullptr, 0, R.nbr27[lvl], nullptr, tmp, 1, lvl);
+        if (done(++s, tmp, lvl)) return true;
+        R.conv(s + 1, tmp, C, nullptr, 0, R.nbr27[lvl], in, out, 1, lvl);
+        return done(++s, out, lvl);
+    };
+    conv1(X);
+    if (done(++s, X, 0)) return true;
+    if (block(X, Y, S1, 32, 0)) return true;
+    R.conv(4, S1, 32, nullptr, 0, R.dn[0], nullptr, X, 0, 1);              if (done(++s, X, 1)) return true;
+    if (block(X, Y, S2, 64, 1)) return true;
+    R.conv(7, S2, 64, nullptr, 0, R.dn[1], nullptr, X, 0, 2);              if (done(++s, X, 2)) return true;
+    if (block(X, Y, S4, 128, 2)) return true;
+    R.conv(10, S4, 128, nullptr, 0, R.dn[2], nullptr, X, 0, 3);            if (done(++s, X, 3)) return true;
+    if (block(X, Y, Z, 256, 3)) return true;
+    R.conv(13, Z, 256, nullptr, 0, R.up[2], nullptr, X, 0, 2);             if (done(++s, X, 2)) return true;
+    if (block(X, Y, Z, 128, 2)) return true;
+    R.conv(16, Z, 128, S4, 128, R.up[1], nullptr, X, 0, 1);                if (done(++s, X, 1)) return true;
+    if (block(X, Y, Z, 64, 1)) return true;
+    R.conv(19, Z, 64, S2, 64, R.up[0], nullptr, X, 0, 0);                  if (done(++s, X, 0)) return true;
+    if (block(X, Y, Z, 64, 0)) return true;
+    R.conv(22, Z, 64, S1, 32, nullptr, nullptr, X, 1, 0);                  if (done(++s, X, 0)) return true;
+    R.conv(23, X, 64, nullptr, 0, nullptr, nullptr, Y, 0, 0);              return done(++s, Y, 0);
+}
+
 extern "C" int lr_fcgf_extract(const int32_t *coords, const float *feat_in, int n, const float *weights, size_t weights_bytes, const lr_fcgf_params *p,
                                lr_fcgf_result *result, float *feat_out, int32_t *tap_coords, void *scratch, size_t scratch_bytes, void *stream)
 {
@@ -441,48 +474,24 @@ extern "C" int lr_fcgf_extract(const int32_t *coords, const float *feat_in, int 
         hipLaunchKernelGGL(fc_nbr_kernel, dim3(R.grid((size_t)n * 27)), dim3(256), 0, st, R.coords[l], l, R.keys[l + 1], R.val[l + 1], mask, 3, -(1 << l), R.up[l], ctl);
     }
 
-    // the 23 stages (F7); a tap ends the call behind its stage
-    float *X = R.at<float>(L.X), *Y = R.at<float>(L.Y), *Z = R.at<float>(L.Z), *S1 = R.at<float>(L.S1), *S2 = R.at<float>(L.S2), *S4 = R.at<float>(L.S4);
+    // a tap ends the call behind its stage
     const int tap = p->tap;
-    int s = 0;
-    // `buf` holds stage s of level lvl: was it the tap?
-    auto done = [&](const float *buf, int lvl) -> bool {
-        ++s;
-        if (tap != s) return false;
-        const int cout = R.t[s].cout;
-        const size_t items = (size_t)n * (cout > 3 ? cout : 3);
-        hipLaunchKernelGGL(fc_tap_kernel, dim3(R.grid(items)), dim3(256), 0, st, buf, cout, lvl, R.coords[lvl], n, feat_out, tap_coords, ctl, result);
-        return true;
-    };
-    // a residual block: its two stages, with the tap between them
-    auto block = [&](const float *in, float *tmp, float *out, int C, int lvl) -> bool {
-        R.conv(s + 1, in, C, nullptr, 0, R.nbr27[lvl], nullptr, tmp, 1, lvl);
-        if (done(tmp, lvl)) return true;
-        R.conv(s + 1, tmp, C, nullptr, 0, R.nbr27[lvl], in, out, 1, lvl);
-        return done(out, lvl);
-    };
-    bool end = false;
-    do {
-        hipLaunchKernelGGL(fc_conv1_kernel, dim3(R.grid((size_t)n * 32)), dim3(256), 0, st, feat_in, K1 == 5 ? nbr125 : R.nbr27[0], K1 * K1 * K1, R.w[1],
-                           R.w[1] + (size_t)K1 * K1 * K1 * 32, R.w[1] + (size_t)K1 * K1 * K1 * 32 + 32, X, ctl);
-        if ((end = done(X, 0))) break;
-        if ((end = block(X, Y, S1, 32, 0))) break;
-        R.conv(4, S1, 32, nullptr, 0, R.dn[0], nullptr, X, 0, 1);              if ((end = done(X, 1))) break;
-        if ((end = block(X, Y, S2, 64, 1))) break;
-        R.conv(7, S2, 64, nullptr, 0, R.dn[1], nullptr, X, 0, 2);              if ((end = done(X, 2))) break;
-        if ((end = block(X, Y, S4, 128, 2))) break;
-        R.conv(10, S4, 128, nullptr, 0, R.dn[2], nullptr, X, 0, 3);            if ((end = done(X, 3))) break;
-        if ((end = block(X, Y, Z, 256, 3))) break;
-        R.conv(13, Z, 256, nullptr, 0, R.up[2], nullptr, X, 0, 2);             if ((end = done(X, 2))) break;
-        if ((end = block(X, Y, Z, 128, 2))) break;
-        R.conv(16, Z, 128, S4, 128, R.up[1], nullptr, X, 0, 1);                if ((end = done(X, 1))) break;
-        if ((end = block(X, Y, Z, 64, 1))) break;
-        R.conv(19, Z, 64, S2, 64, R.up[0], nullptr, X, 0, 0);                  if ((end = done(X, 0))) break;
-        if ((end = block(X, Y, Z, 64, 0))) break;
-        R.conv(22, Z, 64, S1, 32, nullptr, nullptr, X, 1, 0);                  if ((end = done(X, 0))) break;
-        R.conv(23, X, 64, nullptr, 0, nullptr, nullptr, Y, 0, 0);              if ((end = done(Y, 0))) break;
-    } while (0);
+    const bool end = fc_stages(R,
+        [&](float *X) {
+            hipLaunchKernelGGL(fc_conv1_kernel, dim3(R.grid((size_t)n * 32)), dim3(256), 0, st, feat_in, K1 == 5 ? nbr125 : R.nbr27[0], K1 * K1 * K1, R.w[1],
+                               R.w[1] + (size_t)K1 * K1 * K1 * 32, R.w[1] + (size_t)K1 * K1 * K1 * 32 + 32, X, ctl);
+        },
+        [&](int s, const float *buf, int lvl) -> bool {
+            if (tap != s) return false;
+            const int cout = R.t[s].cout;
+            const size_t items = (size_t)n * (cout > 3 ? cout : 3);
+            hipLaunchKernelGGL(fc_tap_kernel, dim3(R.grid(items)), dim3(256), 0, st, buf, cout, lvl, R.coords[lvl], n, feat_out, tap_coords, ctl, result);
+            return true;
+        });
+    const float *Y = R.at<float>(L.Y);
     if (!end) hipLaunchKernelGGL(fc_norm_kernel, dim3(gn), dim3(256), 0, st, Y, n, feat_out, ctl, result);
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
+
+#include "lr_fcgf_batch.h"

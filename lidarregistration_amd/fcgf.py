@@ -2,7 +2,9 @@
 ``ResUNetBN2C(1, 32, conv1_kernel_size=5, normalize_feature=True)`` of Experiments/misc/fcgf.py, which the reference evaluates on
 MinkowskiEngine for every pair (Experiments/datasets/LidarFeatureExtractor.py:71-81, :166-181) -- on integer voxel cells.  This module
 packs the reference's checkpoint (``torch.load(file)['state_dict']``) into the library's weight blob and wraps the call.  The contract is
-n1 of include/lidarreg.h, restated in numpy in tests/fcgf_cpu.py.  There is no CPU fallback.
+n1 of include/lidarreg.h, restated in numpy in tests/fcgf_cpu.py.  lr_fcgf_extract_batch (contract n2, §18.7) takes up
+to 64 clouds per call and gives every cloud the bytes of the one-cloud call: features_batch, extract_batch, extract_pairs.  There is no
+CPU fallback.
 """
 import ctypes
 
@@ -15,6 +17,7 @@ from .devmem import ptr
 BN_EPS = 1e-5              # MinkowskiBatchNorm wraps torch.nn.BatchNorm1d and keeps its default
 N_STAGES = 23
 MAX_N = 1 << 20
+MAX_CLOUDS = 64            # clouds per lr_fcgf_extract_batch (MAX_N rows together)
 
 
 def stage_plan(conv1_kernel_size=5):
@@ -163,6 +166,78 @@ class FCGF:
         self.last_info = dict(status=r.status, n=r.n, n_tap=r.n_tap)
         cout = stage_plan(self.conv1_kernel_size)[int(s) - 1][4]
         return out.reshape(-1)[:r.n_tap * cout].reshape(r.n_tap, cout), tc[:r.n_tap]
+
+    def _call_batch(self, coords, feat_in, poison=None):
+        """One lr_fcgf_extract_batch over device tensors coords[b] [n_b,3] int32 and feat_in[b] [n_b] float32 | None (at most MAX_CLOUDS
+        clouds and MAX_N rows together) -> (outs [n_b,32], the result blocks as one uint8 tensor)."""
+        L = _ext.lib()
+        dev = self.device
+        B = len(coords)
+        ns = [int(c.shape[0]) for c in coords]
+        outs = [torch.zeros((max(n, 1), 32), dtype=torch.float32, device=dev) for n in ns]
+        res = torch.zeros(B * ctypes.sizeof(_ext.FcgfResult), dtype=torch.uint8, device=dev)
+        scratch = devmem.scratch(L.lr_fcgf_batch_scratch_bytes(B, sum(ns)), dev, poison)
+        arr = lambda ts: (ctypes.c_void_p * B)(*[ptr(t, n) for t, n in zip(ts, ns)])
+        params = _ext.FcgfParams(conv1_kernel_size=self.conv1_kernel_size, tap=0)
+        with torch.cuda.device(dev):
+            _ext.check(L.lr_fcgf_extract_batch(B, arr(coords), arr(feat_in), (ctypes.c_int32 * B)(*ns), self.weights.data_ptr(), self.weights.numel() * 4,
+                                               ctypes.byref(params), res.data_ptr(), arr(outs), scratch.data_ptr(), scratch.numel(),
+                                               torch.cuda.current_stream().cuda_stream))
+        return [o[:n] for o, n in zip(outs, ns)], res
+
+    def features_batch(self, cells_list, feat_in_list=None, poison=None):
+        """`features` for many clouds through lr_fcgf_extract_batch (contract n2): cells_list[b] [n_b,3], feat_in_list[b] [n_b] or None = ones
+        -> a list of [n_b,32] device tensors, each holding the bytes `features` gives for that cloud alone.  self.last_info: one dict per
+        cloud; the status is per cloud (3: a cell past +-(2^18 - 2), the batch entry's range).  Lists of more than MAX_CLOUDS clouds or
+        MAX_N rows are split into several calls; a single cloud above MAX_N rows is refused by the library."""
+        dev = self.device
+        coords = [torch.as_tensor(c).to(device=dev, dtype=torch.int32).contiguous().reshape(-1, 3) for c in cells_list]
+        feat_in = list(feat_in_list) if feat_in_list is not None else [None] * len(coords)
+        if len(feat_in) != len(coords):
+            raise ValueError(f"feat_in_list has {len(feat_in)} entries, cells_list {len(coords)}")
+        for b, f in enumerate(feat_in):
+            if f is not None:
+                feat_in[b] = f = torch.as_tensor(f).to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+                if f.shape[0] != coords[b].shape[0]:
+                    raise ValueError(f"feat_in_list[{b}] has {f.shape[0]} rows, cells_list[{b}] {coords[b].shape[0]}")
+        outs, blocks = [], []
+        at = 0
+        while at < len(coords):
+            end, rows = at + 1, int(coords[at].shape[0])
+            while end < len(coords) and end - at < MAX_CLOUDS and rows + int(coords[end].shape[0]) <= MAX_N:
+                rows += int(coords[end].shape[0]); end += 1
+            o, res = self._call_batch(coords[at:end], feat_in[at:end], poison)
+            outs += o; blocks.append(res)
+            at = end
+        self.last_info = []
+        for res in blocks:
+            host = res.cpu()
+            for k in range(host.numel() // ctypes.sizeof(_ext.FcgfResult)):
+                r = devmem.read_struct(host, _ext.FcgfResult, k)
+                self.last_info.append(dict(status=r.status, n=r.n, n_tap=r.n_tap))
+        return outs
+
+    def extract_batch(self, raw_scans, voxel_size=0.3):
+        """`extract` for many raw scans: [(xyz_kept, feats, sel)] in their order, the voxel de-duplication per cloud and the network in one
+        batched call.  A cloud with a non-zero status raises, naming its index."""
+        from . import voxel
+        kept, cells = [], []
+        with torch.cuda.device(self.device):
+            for raw in raw_scans:
+                xyz, sel = voxel.voxel_downsample(raw, voxel_size)
+                x64 = torch.as_tensor(raw).to(device=self.device, dtype=torch.float64)[sel]
+                kept.append((xyz, sel)); cells.append(torch.floor(x64 / voxel_size).to(torch.int32))
+            feats = self.features_batch(cells)
+        for b, info in enumerate(self.last_info):
+            if info["status"] != 0:
+                raise _ext.LidarRegError(f"lr_fcgf_extract_batch: cloud {b}: status {info['status']} (2: duplicate cell, 3: cell past the range limit of 2^18 - 2)")
+        return [(xyz, f, sel) for (xyz, sel), f in zip(kept, feats)]
+
+    def extract_pairs(self, pairs, voxel_size=0.3):
+        """[(xyz0_raw, xyz1_raw)] -> [(xyz0, xyz1, feats0, feats1)], `extract_pair` for every pair with both clouds of every pair in one
+        batched call, as the reference batches a pair into one sparse tensor (LidarFeatureExtractor.py:166-181)."""
+        out = self.extract_batch([raw for pair in pairs for raw in pair], voxel_size)
+        return [(out[2 * k][0], out[2 * k + 1][0], out[2 * k][1], out[2 * k + 1][1]) for k in range(len(pairs))]
 
     def extract(self, xyz_raw, voxel_size=0.3):
         """A raw scan [N,3] -> (xyz_kept [n,3] float32, feats [n,32], sel [n] int64), device tensors: the reference's loader

@@ -140,6 +140,28 @@ class RefCloudSource:
     def finish(self, host, device):
         return _upload(self.get(host[0], host[1]), device)
 
+    def finish_window(self, hosts, device):
+        """finish() for the rows of a window.  With an extractor every distinct (session, idx) of the window is de-duplicated and goes
+        through the network once, all of them in batched calls (fcgf.FCGF.extract_batch), and the pairs' dicts are built from the device
+        tensors: no copy to the host and back.  The tensors hold what the per-cloud path uploads, bit for bit.  Pairs that share a scan
+        share its tensors (the per-cloud path uploads a copy per pair): the registration path only reads xyz and feats; a consumer that
+        writes into them in place must clone first."""
+        if not self.extractor:
+            return [self.finish(h, device) for h in hosts]
+        order, raws = {}, []
+        for k, files in hosts:
+            s, i, j = self.ids(k)
+            for idx, (raw, _) in zip((i, j), files):
+                if (s, idx) not in order:
+                    order[(s, idx)] = len(raws); raws.append(raw)
+        clouds = self.extractor.extract_batch(raws, self.voxel_size)
+        out = []
+        for k, _ in hosts:
+            s, i, j = self.ids(k)
+            (xyz0, f0, _), (xyz1, f1, _) = clouds[order[(s, i)]], clouds[order[(s, j)]]
+            out.append(dict(xyz0=xyz0.to(device), xyz1=xyz1.to(device), feats0=f0.to(device), feats1=f1.to(device), T_gt=self.pair_list["T_gt"][k]))
+        return out
+
 
 def load_list_fixture(dataset):
     """The reference's balanced test list of `dataset` ("A" | "B") from tests/golden/lists (made by tests/golden/make_lists.py from
@@ -390,7 +412,11 @@ def eval_pairs(source, indices, args, device=None, batch=32, in_flight=6, nstrea
             t0 = time.time()
             if pool:
                 mine, ahead = ahead, [pool.submit(source.load_host, indices[row]) for row in range(w0 + window, min(w0 + 2 * window, n))]
-                ps = [source.finish(f.result(), dev) for f in mine]      # (a missing / mismatching file raises here: the finally below stops the readers)
+                # (a missing / mismatching file raises here: the finally below stops the readers)
+                if hasattr(source, "finish_window"):
+                    ps = source.finish_window([f.result() for f in mine], dev)
+                else:
+                    ps = [source.finish(f.result(), dev) for f in mine]
             else:
                 ps = [source.get_dev(indices[row], dev) for row in rows_w]
             torch.cuda.synchronize(dev)

@@ -11,6 +11,13 @@ normalisation.  FLOP rates of that rest, three ways, counted on the host from th
 Prints one JSON line and writes it to --out (default profiles/fcgf_bench.json).
 
     python tools/fcgf_bench.py [--points 4400,40000,180000] [--reps 5]
+
+--batch 1,2,8,32 times the batched entry (lr_fcgf_extract_batch) instead: per batch size B, B frames of about 30 000 voxels through one
+call, per cloud, beside lr_fcgf_extract on each of the same frames in the same run (the yardstick: that code is the single entry's), the
+batch cut behind conv1 for the maps' share, and the effect of the level-0 row order on the single call and on the host-counted
+issued / pair flop.  Writes profiles/fcgf_batch_bench.json.
+
+    python tools/fcgf_bench.py --batch 1,2,8,32 [--reps 5]
 """
 import argparse
 import ctypes
@@ -65,23 +72,96 @@ def make_call(m, cells, tap):
                                                 out.data_ptr(), None, sc.data_ptr(), sc.numel(), st))
 
 
-def timed(fn, reps):
+def timed(fn, reps, per=1):
+    """Median, minimum and maximum over `reps` calls of the time between two events around fn(), divided by `per`; one warm-up."""
     fn(); torch.cuda.synchronize()
     ms = []
     for _ in range(reps):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(); fn(); e1.record(); torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
+        ms.append(e0.elapsed_time(e1) / per)
     return dict(median_ms=float(np.median(ms)), min_ms=float(min(ms)), max_ms=float(max(ms)))
+
+
+def make_batch_call(m, frames):
+    """lr_fcgf_extract_batch alone on these frames, on buffers made once."""
+    L = _ext.lib()
+    B, ns = len(frames), [int(c.shape[0]) for c in frames]
+    dev = frames[0].device
+    sc = devmem.scratch(L.lr_fcgf_batch_scratch_bytes(B, sum(ns)), dev)
+    res = torch.zeros(16 * B, dtype=torch.uint8, device=dev)
+    outs = [torch.zeros((n, 32), dtype=torch.float32, device=dev) for n in ns]
+    p = _ext.FcgfParams(conv1_kernel_size=m.conv1_kernel_size, tap=0)
+    st = torch.cuda.current_stream().cuda_stream
+    vp = lambda ts: (ctypes.c_void_p * B)(*[t.data_ptr() for t in ts])
+    cp, op, np_ = vp(frames), vp(outs), (ctypes.c_int32 * B)(*ns)
+
+    def call(keep=(frames, outs)):          # (the pointer arrays hold addresses only: the closure keeps the tensors alive)
+        _ext.check(L.lr_fcgf_extract_batch(B, cp, None, np_, m.weights.data_ptr(), m.weights.numel() * 4, ctypes.byref(p), res.data_ptr(), op, sc.data_ptr(),
+                                           sc.numel(), st))
+    call()                                   # a refused cloud (status 2 / 3) would be timed as if it had been computed: look once
+    blocks = res.cpu().numpy().view(np.int32).reshape(B, 4)
+    assert (blocks[:, 0] == 0).all() and blocks[:, 1].tolist() == ns, blocks.tolist()
+    return call
+
+
+def frame_cells(n0, seed):
+    """The cells of one frame as fcgf.FCGF.extract_batch builds them: voxel de-duplication, floor(xyz / 0.3) in fp64."""
+    raw = synth.make_scan_pair(n0=n0, seed=seed)[0]
+    _, sel = voxel.voxel_downsample(raw, 0.3)
+    return torch.floor(torch.as_tensor(raw).to(device="cuda", dtype=torch.float64)[sel] / 0.3).to(torch.int32).contiguous()
+
+
+def batch_rows(m, sizes, reps, n0=40000):
+    """One row per batch size B: B frames of about 30 000 voxels (different seeds) through ONE lr_fcgf_extract_batch, per cloud, next to
+    lr_fcgf_extract on each of the same frames in the same run; the batch cut behind conv1 (the library's bench hook) gives the maps'
+    share.  Then the row order alone, on frame 0 and through the single call, whose code is the parent's: the order extract() hands
+    over, a random order and key order (what the batch entry puts level 0 in), with the host-counted issued / pair flop of each."""
+    L = _ext.lib()
+    frames = [frame_cells(n0, 100 + b) for b in range(max(sizes))]
+    single = [timed(make_call(m, c, 0), reps) for c in frames]
+    rows = []
+    for B in sizes:
+        call = make_batch_call(m, frames[:B])
+        whole = timed(call, reps, per=B)
+        L.lr_debug_fcgf_batch_stop_after(1)
+        try:
+            maps = timed(call, reps, per=B)
+        finally:
+            L.lr_debug_fcgf_batch_stop_after(0)
+        del call
+        s = single[:B]
+        rows.append(dict(clouds=B, voxels=[int(c.shape[0]) for c in frames[:B]], batch_per_cloud=whole, batch_maps_and_conv1_per_cloud=maps,
+                         maps_share=maps["median_ms"] / whole["median_ms"],
+                         single_call=dict(median_ms=float(np.median([x["median_ms"] for x in s])), min_ms=min(x["min_ms"] for x in s), max_ms=max(x["max_ms"] for x in s)),
+                         batch_max_below_single_min=whole["max_ms"] < min(x["min_ms"] for x in s)))
+    c0 = frames[0].cpu().numpy()
+    orders = dict(as_extracted=c0, shuffled=c0[np.random.default_rng(1).permutation(len(c0))], key_order=c0[np.lexsort((c0[:, 2], c0[:, 1], c0[:, 0]))])
+    order_rows = {}
+    for name, cells in orders.items():
+        dense, issued, pairs, _ = work(cells)
+        t = torch.from_numpy(np.ascontiguousarray(cells)).cuda()
+        order_rows[name] = dict(issued_flop=issued, pair_flop=pairs, issued_over_pair=issued / pairs, single_call=timed(make_call(m, t, 0), reps),
+                                single_call_maps_and_conv1=timed(make_call(m, t, 1), reps))
+    return rows, order_rows
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", default="4400,40000,180000", help="raw returns per frame (about 4 000, 30 000 and 100 000 voxels)")
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fcgf_bench.json"))
+    ap.add_argument("--batch", default="", help="batch sizes, e.g. 1,2,8,32: time lr_fcgf_extract_batch on that many 30 000-voxel frames instead of the single-frame rows")
+    ap.add_argument("--out", default=None, help="default: profiles/fcgf_bench.json, with --batch profiles/fcgf_batch_bench.json")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "fcgf_batch_bench.json" if a.batch else "fcgf_bench.json")
     m = fcgf.FCGF.from_state_dict(fcgf_cases.make_state_dict(0, 5), 5)
+    if a.batch:
+        rows, orders = batch_rows(m, [int(v) for v in a.batch.split(",")], a.reps)
+        line = json.dumps(dict(tool="fcgf_bench --batch", device=torch.cuda.get_device_name(0), reps=a.reps, rows=rows, row_order_on_frame_0=orders))
+        print(line)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+        return
     rows = []
     for n0 in (int(v) for v in a.points.split(",")):
         raw = synth.make_scan_pair(n0=n0, seed=3)[0]
