@@ -906,6 +906,59 @@ LR_API int lr_fcgf_extract_batch(int nclouds, const int32_t *const *coords, cons
  * which has no tap); 0 restores the contract.  Set it, time, and set it back with no other caller of the library running.         */
 LR_API int lr_debug_fcgf_batch_stop_after(int stage);
 
+/* ---- n3: Deep Global Registration's inlier network: ResUNetBN2C(in_channels = 1, out_channels = 1, conv1_kernel_size = 3,
+ * normalize_feature = False, D = 6), inference mode, hyper-cube regions (DGR/config.py:81-83, DGR/core/deep_global_registration.py:
+ * 140-149, DGR/model/resunet.py:419-665): one inlier logit per correspondence, a 6-D cell (cell of the point in cloud 0, cell of its
+ * match in cloud 1; deep_global_registration.py:382).  The reference runs it on MinkowskiEngine; as for n1 the semantics are
+ * upstream-recalled and the contract below is the specification (restated twice in tests/dgr6_cpu.py).
+ * Input: coords [n,6] int32 cells at tensor stride 1, the feature of every row is 1 (inlier_feature_type 'ones'), 0 <= n <= 131072.
+ * Output: logit_out [n] float32, row i for input row i, and lr_dgr_inlier_result.
+ * The contract is F1 - F7, F9, F10 and F12 of n1 read in six dimensions (o in {-1,0,1}^6, three coarse levels, the same 23 stages), with:
+ *  I1  offsets: K = 3 everywhere, conv1 included; idx(o) = sum_a (o_a + 1) 3^a, axis 0 fastest [upstream-recalled, as F2]; W is
+ *      [729, Cin, Cout].
+ *  I2  levels and keys: a coarse level's rows are in ascending lexicographic order of the six cells, axis 0 most significant,
+ *      independent of the input order and of the hash.  Cells are taken relative to the call's origin, origin_a = 8 floor(min_a / 8)
+ *      per axis (computed on the device), and packed into six 10-bit fields (cell - origin + 8).  Extent limit: cell_a - origin_a <= 1007
+ *      on every axis, which admits every cloud whose extent max_a - min_a + 1 is at most 1001 cells on each axis (300 m at 0.3 m voxels)
+ *      and, with min_a a multiple of 8, 1008 cells.  A wider extent: status 3; a duplicate 6-D coordinate: status 2; 3 wins over 2;
+ *      either way logit_out's n entries are 0 (a tap stores no rows: n_tap = 0).  n = 0: status 0, only the result block is written.
+ *      The origin is a multiple of 8, so F10 holds: adding a multiple of 8 to every cell of an axis changes no bit.
+ *  I3  arithmetic: F5 unchanged: per output element ONE fp32 fmaf chain from +0 over ascending idx(o) and, inside an offset, ascending
+ *      input channel; no floating-point atomics.
+ *  I4  stages: F7's table with 729 offsets for stages 1 - 21 and the widths of I5; 22 conv1_tr 1x1 on cat(up, s1), T2 + C1 -> T1, ReLU,
+ *      no BatchNorm; 23 final 1x1, T1 -> 1: one fmaf chain over the T1 channels from +0, then one add of the bias.  There is no F8: the
+ *      output is the logit.  The sigmoid (deep_global_registration.py:390) is the caller's.
+ *  I5  widths: C1 C2 C3 C4 (down) and T4 T3 T2 T1 (up), each a multiple of 32 in 32 .. 256; ResUNetBN2C is 32 64 128 256, 128 64 64 64.
+ *      Weights: one flat float32 device blob of lr_dgr_inlier_weights_bytes(widths) bytes, 16-byte aligned, per stage in order
+ *      { W[K^6][Cin][Cout], scale[Cout], offset[Cout] } (F6's fold; final: scale 1, offset = bias).
+ * Refusals (F12): LR_EINVAL before any launch, lr_last_error naming the argument: struct_size, a width out of range, tap outside 0..23,
+ * n outside 0..131072, null / short / misaligned weights, null result / coords / logit_out, and the scratch, stream and device rules. */
+typedef struct lr_dgr_inlier_params {
+    uint32_t struct_size;        /* = sizeof(lr_dgr_inlier_params)                                                                  */
+    int32_t  tap;                /* 0: the network.  s = 1..23: stop behind stage s and store ITS activations [n_tap, Cout] in logit_out
+                                    (which the caller sizes for n x the largest width) and its level's cells in tap_coords          */
+    int32_t  widths[8];          /* I5: C1 C2 C3 C4 T4 T3 T2 T1                                                                     */
+} lr_dgr_inlier_params;
+
+/* Written to device memory by lr_dgr_inlier (16 bytes). */
+typedef struct lr_dgr_inlier_result {
+    int32_t  status;             /* 0 ok, 2 = duplicate coordinate, 3 = an axis wider than the extent limit                         */
+    int32_t  n;
+    int32_t  n_tap;              /* entries / rows stored in logit_out: n, or the rows of the tapped stage's level; 0 on status 2 / 3 */
+    int32_t  reserved;           /* 0                                                                                               */
+} lr_dgr_inlier_result;
+
+/* Bytes of the weight blob (0 when a width is out of range or widths is null). */
+LR_API size_t lr_dgr_inlier_weights_bytes(const int32_t widths[8]);
+/* Caller-owned device scratch for up to max_n rows (0 when max_n is outside 0..131072 or a width is out of range): a constant plus a
+ * multiple of max_n rounded up to 64; the ten dense gather tables [rows][729] are 29 160 bytes of it per row.                        */
+LR_API size_t lr_dgr_inlier_scratch_bytes(int max_n, const int32_t widths[8]);
+/* tap_coords: nullable, int32 [n,6], written by a tap only.  scratch: >= lr_dgr_inlier_scratch_bytes(n, p->widths) bytes, 256-byte
+ * aligned, memory of the current device (checked, like the stream).  Kernel launches only: no host synchronisation, no allocation.   */
+LR_API int lr_dgr_inlier(const int32_t *coords, int n, const float *weights, size_t weights_bytes, const lr_dgr_inlier_params *p,
+                         lr_dgr_inlier_result *result, float *logit_out, int32_t *tap_coords, void *scratch, size_t scratch_bytes,
+                         void *stream);
+
 /* ---- d1: Deep Global Registration's robust pose refinement over M weighted correspondences src[i] <-> tgt[i] -----------------------
  * Replaces what DeepGlobalRegistration.register does once it has the inlier weights (DGR/core/deep_global_registration.py:403-435): the
  * weight-sum decision and GlobalRegistration (DGR/core/registration.py:16-64, :116-194) under HighDimSmoothL1Loss (DGR/core/loss.py:42-61):

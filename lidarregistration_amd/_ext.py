@@ -31,6 +31,7 @@ SYMBOLS = [
     "lr_pdsc_register_scratch_bytes", "lr_pdsc_register", "lr_pdsc_register_batch",
     "lr_fcgf_weights_bytes", "lr_fcgf_scratch_bytes", "lr_fcgf_extract", "lr_fcgf_batch_scratch_bytes", "lr_fcgf_extract_batch", "lr_debug_fcgf_batch_stop_after",
     "lr_dgr_scratch_bytes", "lr_dgr_refine", "lr_dgr_refine_batch",
+    "lr_dgr_inlier_weights_bytes", "lr_dgr_inlier_scratch_bytes", "lr_dgr_inlier",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -229,6 +230,24 @@ class DgrResult(ctypes.Structure):
                 ("break_count", ctypes.c_int32), ("L", ctypes.c_int32), ("status", ctypes.c_int32)]
 
 
+class DgrInlierParams(KeywordParams):
+    """lr_dgr_inlier_params with ResUNetBN2C's widths (DGR/model/resunet.py:662-665) as default; struct_size is filled in."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("tap", ctypes.c_int32), ("widths", ctypes.c_int32 * 8)]
+    DEFAULTS = dict(tap=0, widths=(32, 64, 128, 256, 128, 64, 64, 64))
+
+    def __init__(self, **kw):
+        if "widths" in kw:
+            kw["widths"] = (ctypes.c_int32 * 8)(*[int(w) for w in kw["widths"]])
+        else:
+            kw["widths"] = (ctypes.c_int32 * 8)(*self.DEFAULTS["widths"])
+        super().__init__(**kw)
+
+
+class DgrInlierResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("n", ctypes.c_int32), ("n_tap", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+assert ctypes.sizeof(DgrInlierParams) == 40 and ctypes.sizeof(DgrInlierResult) == 16
 assert ctypes.sizeof(DgrParams) == 64 and ctypes.sizeof(DgrResult) == 160
 assert ctypes.sizeof(FcgfParams) == 12 and ctypes.sizeof(FcgfResult) == 16
 assert ctypes.sizeof(PdscSolveParams) == 64 and ctypes.sizeof(PdscSolveResult) == 304
@@ -352,6 +371,11 @@ def lib():
         L.lr_dgr_scratch_bytes.argtypes = [ci]
         L.lr_dgr_refine.argtypes = [vp, vp, ci, vp, vp, vp, pd, vp, vp, vp, sz, vp]
         L.lr_dgr_refine_batch.argtypes = [ci, pp, pp, ip, pp, pp, pp, pd, vp, vp, sz, vp]
+        w8 = ctypes.POINTER(ctypes.c_int32 * 8)
+        L.lr_dgr_inlier_weights_bytes.restype = ctypes.c_size_t
+        L.lr_dgr_inlier_weights_bytes.argtypes = [w8]
+        L.lr_dgr_inlier_scratch_bytes.argtypes = [ci, w8]
+        L.lr_dgr_inlier.argtypes = [vp, ci, vp, sz, ctypes.POINTER(DgrInlierParams), vp, vp, vp, vp, sz, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

@@ -13,16 +13,12 @@
 // LDS (zeros for absent ones), stages the offset's weight slab and accumulates on v_mfma_f32_32x32x2_f32, which is bit for bit the fmaf
 // chain of F5.  The epilogue F6 is fused; a two-source input (the cat) is read in place.  conv1 (Cin = 1) is a vector kernel.
 #include "lr_scratch.h"
-#include "lr_cells.h"
+#include "lr_sparse.h"
 
 #define FC_MAX_N (1 << 20)
 #define FC_BIAS (1 << 20)            // cell + bias is the 21-bit field of lr_cells_pack
 #define FC_LIMIT ((1 << 20) - 2)     // |cell| >= this: status 3
 #define FC_STAGES 23
-#define FC_SORT_CHUNK 2048
-
-typedef unsigned long long fc_u64;
-typedef float fc_f32x16 __attribute__((ext_vector_type(16)));
 
 struct fc_ctl { int32_t status, n[4], pad[3]; };
 struct fc_stage { int k3, cin, cout; };
@@ -64,17 +60,6 @@ static fc_layout fc_make_layout(size_t max_n, size_t ctl_bytes = 256)
 }
 
 // ---- maps -------------------------------------------------------------------------------------------------------------------------
-// the slot of `key`, -1 when the table does not hold it (at most half of the slots are taken: an empty one is met)
-__device__ __forceinline__ int fc_find(const fc_u64 *__restrict__ keys, unsigned mask, fc_u64 key)
-{
-    unsigned s = (unsigned)lr_mix64(key) & mask;
-    for (;;) {
-        const fc_u64 k = keys[s];
-        if (k == key) return (int)s;
-        if (k == LR_CELL_EMPTY) return -1;
-        s = (s + 1) & mask;
-    }
-}
 __device__ __forceinline__ fc_u64 fc_key(int x, int y, int z) { return lr_cells_pack((fc_u64)(x + FC_BIAS), (fc_u64)(y + FC_BIAS), (fc_u64)(z + FC_BIAS)); }
 __device__ __forceinline__ bool fc_in_range(int v) { return v > -FC_LIMIT && v < FC_LIMIT; }
 
@@ -126,32 +111,6 @@ __global__ void __launch_bounds__(256) fc_coarse_mark_kernel(const int32_t *__re
     }
     sortbuf[i] = out;
 }
-// bitonic sort, ascending, of n_sort = 2^p >= 2048 keys: the steps with a distance below 2048 run in LDS, 2048 keys per block
-__global__ void __launch_bounds__(1024) fc_sort_local_kernel(fc_u64 *__restrict__ keys, unsigned k_lo, unsigned k_hi)
-{
-    __shared__ fc_u64 s[FC_SORT_CHUNK];
-    const unsigned tid = threadIdx.x, base = blockIdx.x * FC_SORT_CHUNK;
-    s[tid] = keys[base + tid]; s[tid + 1024] = keys[base + tid + 1024];
-    __syncthreads();
-    for (unsigned k = k_lo; k <= k_hi; k <<= 1)
-        for (unsigned j = (k >> 1) < 1024u ? (k >> 1) : 1024u; j >= 1; j >>= 1) {
-            const unsigned i = ((tid & ~(j - 1)) << 1) | (tid & (j - 1));
-            const bool up = ((base + i) & k) == 0;
-            const fc_u64 a = s[i], b = s[i + j];
-            if ((a > b) == up) { s[i] = b; s[i + j] = a; }
-            __syncthreads();
-        }
-    keys[base + tid] = s[tid]; keys[base + tid + 1024] = s[tid + 1024];
-}
-__global__ void __launch_bounds__(256) fc_sort_global_kernel(fc_u64 *__restrict__ keys, unsigned j, unsigned k, unsigned half)
-{
-    const unsigned t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= half) return;
-    const unsigned i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-    const bool up = (i & k) == 0;
-    const fc_u64 a = keys[i], b = keys[i + j];
-    if ((a > b) == up) { keys[i] = b; keys[i + j] = a; }
-}
 // the sorted keys are the level's rows: row r of level lvl = the cell of rank r
 __global__ void __launch_bounds__(256) fc_coarse_index_kernel(const fc_u64 *__restrict__ sorted, int lvl, const fc_u64 *__restrict__ keys, int32_t *__restrict__ val,
                                                               unsigned mask, int32_t *__restrict__ coords, const fc_ctl *ctl)
@@ -182,8 +141,6 @@ __global__ void __launch_bounds__(256) fc_nbr_kernel(const int32_t *__restrict__
 }
 
 // ---- convolutions -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float fc_relu(float y) { return y > 0.0f ? y : (y != y ? y : 0.0f); }
-
 // conv1: Cin = 1, 32 outputs, K^3 = 27 or 125 offsets; BatchNorm folded, no ReLU
 __global__ void __launch_bounds__(256) fc_conv1_kernel(const float *__restrict__ feat_in, const int32_t *__restrict__ nbr, int nk, const float *__restrict__ W,
                                                        const float *__restrict__ scale, const float *__restrict__ offset, float *__restrict__ out, const fc_ctl *ctl)
@@ -456,12 +413,7 @@ extern "C" int lr_fcgf_extract(const int32_t *coords, const float *feat_in, int 
     for (int l = 0; l < 3; ++l) {
         hipLaunchKernelGGL(fc_coarse_insert_kernel, dim3(gn), dim3(256), 0, st, R.coords[l], l, R.keys[l + 1], R.val[l + 1], mask, ctl);
         hipLaunchKernelGGL(fc_coarse_mark_kernel, dim3(R.grid(n_sort)), dim3(256), 0, st, R.coords[l], l, R.keys[l + 1], R.val[l + 1], mask, sortbuf, (int)n_sort, ctl);
-        hipLaunchKernelGGL(fc_sort_local_kernel, dim3(n_sort / FC_SORT_CHUNK), dim3(1024), 0, st, sortbuf, 2u, (unsigned)FC_SORT_CHUNK);
-        for (unsigned k = 2 * FC_SORT_CHUNK; k <= n_sort; k <<= 1) {
-            for (unsigned j = k >> 1; j >= FC_SORT_CHUNK; j >>= 1)
-                hipLaunchKernelGGL(fc_sort_global_kernel, dim3(R.grid(n_sort / 2)), dim3(256), 0, st, sortbuf, j, k, n_sort / 2);
-            hipLaunchKernelGGL(fc_sort_local_kernel, dim3(n_sort / FC_SORT_CHUNK), dim3(1024), 0, st, sortbuf, k, k);
-        }
+        fc_sort_launch(sortbuf, n_sort, st);
         hipLaunchKernelGGL(fc_coarse_index_kernel, dim3(gn), dim3(256), 0, st, sortbuf, l + 1, R.keys[l + 1], R.val[l + 1], mask, const_cast<int32_t *>(R.coords[l + 1]), ctl);
     }
     const int K1 = p->conv1_kernel_size;

@@ -299,14 +299,7 @@ extern "C" int lr_fcgf_extract_batch(int nclouds, const int32_t *const *coords, 
         const int gn = R.grid((size_t)total);
         unsigned n_sort = FC_SORT_CHUNK;
         while (n_sort < (unsigned)total) n_sort <<= 1;
-        auto sort = [&]() {
-            hipLaunchKernelGGL(fc_sort_local_kernel, dim3(n_sort / FC_SORT_CHUNK), dim3(1024), 0, st, sortbuf, 2u, (unsigned)FC_SORT_CHUNK);
-            for (unsigned k = 2 * FC_SORT_CHUNK; k <= n_sort; k <<= 1) {
-                for (unsigned j = k >> 1; j >= FC_SORT_CHUNK; j >>= 1)
-                    hipLaunchKernelGGL(fc_sort_global_kernel, dim3(R.grid(n_sort / 2)), dim3(256), 0, st, sortbuf, j, k, n_sort / 2);
-                hipLaunchKernelGGL(fc_sort_local_kernel, dim3(n_sort / FC_SORT_CHUNK), dim3(1024), 0, st, sortbuf, k, k);
-            }
-        };
+        auto sort = [&]() { fc_sort_launch(sortbuf, n_sort, st); };
 
         // maps
         hipLaunchKernelGGL(fb_l0_insert_kernel, dim3(gn), dim3(256), 0, st, t, total, R.keys[0], R.val[0], mask, ctl);

@@ -43,19 +43,19 @@ def packed_floats(conv1_kernel_size=5):
     return sum(k3 * cin * cout + 2 * cout for _, _, k3, cin, cout in stage_plan(conv1_kernel_size))
 
 
-def _np64(sd, key, shape=None):
+def _np64(sd, key, shape=None, what="FCGF state dict"):
     if key not in sd:
-        raise ValueError(f"FCGF state dict: missing key {key!r}")
+        raise ValueError(f"{what}: missing key {key!r}")
     v = sd[key]
     if isinstance(v, torch.Tensor):
         v = v.detach().cpu().numpy()
     v = np.asarray(v, np.float64)
     if shape is not None:
         if v.shape != shape and not (v.size == int(np.prod(shape)) and v.squeeze().shape == tuple(s for s in shape if s != 1)):
-            raise ValueError(f"FCGF state dict: {key} has shape {v.shape}, expected {shape}")
+            raise ValueError(f"{what}: {key} has shape {v.shape}, expected {shape}")
         v = v.reshape(shape)
     if not np.isfinite(v).all():
-        raise ValueError(f"FCGF state dict: {key} holds a non-finite value")
+        raise ValueError(f"{what}: {key} holds a non-finite value")
     return v
 
 
