@@ -5,18 +5,18 @@
 //   key = cloud << 57 | (x + 2^18) << 38 | (y + 2^18) << 19 | (z + 2^18)          (top bit clear: LR_CELL_EMPTY sorts behind every row),
 // so one table per level serves every cloud and no cloud can find another cloud's cell.  Level 0 is sorted like the coarse levels: the rows
 // of the accepted clouds (status 0) in ascending (cloud, x, y, z) order, perm[r] = the global input row of rank r; every cloud's rows are
-// contiguous at every level and, inside a cloud, in the order F1 prescribes.  A level's rows are kept as their keys (a coarse cell is the key
-// with the low bits of its three fields cleared: the bias is a multiple of 8).  The gather tables are per row, so fc_conv_kernel runs
-// unchanged over the total rows, a row tile across two clouds included; only the two ends differ: conv1 reads feat_in, and the
-// normalisation writes feat_out, of the row's cloud at perm[r] - start[cloud].  The status is per cloud (fb_ctl.status); the word that
-// fc_conv_kernel leaves on stays 0.
+// contiguous at every level and, inside a cloud, in the order F1 prescribes.  The codec carries the tag through the coarse levels and the
+// gather tables, which are per row, so the maps and sp_conv_kernel of lr_sparse.h run unchanged over the total rows, a row tile across two
+// clouds included; only level 0 and the two ends differ: conv1 reads feat_in, and the normalisation writes feat_out, of the row's cloud
+// at perm[r] - start[cloud].  The status is per cloud (fb_ctl.status); the word that the shared kernels leave on stays 0.  The three
+// level-0 kernels stay here: they find a row's cloud, and with it its status word, by a search in the cloud table.
 #pragma once
 #include <string.h>
 
 #define FB_BIAS (1 << 18)            // cell + bias is a 19-bit field of the tagged key
 #define FB_LIMIT ((1 << 18) - 2)     // |cell| >= this: status 3
-#define FB_FIELD 0x7ffffull
 #define FB_CTL_BYTES 512
+typedef sp_codec<3, 19> fb_codec;      // the tag above bit 57: the cloud
 
 // the clouds of a call: by value into the kernels that need them, like ov_desc_table (1800 bytes)
 struct fb_table {
@@ -28,7 +28,7 @@ struct fb_table {
 };
 static_assert(sizeof(fb_table) + 512 <= 4096, "the cloud table no longer fits the kernel arguments");
 // c.status stays 0, c.n[l] = rows of level l over the accepted clouds
-struct fb_ctl { fc_ctl c; int32_t status[LR_MAX_BATCH]; };
+struct fb_ctl { sp_ctl c; int32_t status[LR_MAX_BATCH]; };
 static_assert(sizeof(fb_ctl) <= FB_CTL_BYTES, "fb_ctl outgrew its place at the head of the scratch");
 
 // ---- maps -------------------------------------------------------------------------------------------------------------------------
@@ -58,21 +58,7 @@ __device__ __forceinline__ bool fb_row_key(const fb_table &t, int i, int &c, fc_
     key = fb_key(c, x, y, z);
     return true;
 }
-// the level-(lvl+1) cell of a level-lvl key: floor(v / 2^sh) 2^sh on every axis
-__device__ __forceinline__ fc_u64 fb_coarse_of(fc_u64 key, int sh)
-{
-    const fc_u64 low = (1ull << sh) - 1;
-    return key & ~((low << 38) | (low << 19) | low);
-}
 
-// the control block and the four tables' words the later kernels accumulate into: a kernel like ov_init_kernel, so that a call is
-// kernel launches only
-__global__ void __launch_bounds__(256) fb_init_kernel(fc_u64 *__restrict__ keys, int32_t *__restrict__ val, size_t slots, fb_ctl *ctl)
-{
-    if (blockIdx.x == 0)
-        for (int w = threadIdx.x; w < FB_CTL_BYTES / 4; w += 256) reinterpret_cast<int32_t *>(ctl)[w] = 0;
-    for (size_t s = (size_t)blockIdx.x * 256 + threadIdx.x; s < slots; s += (size_t)gridDim.x * 256) { keys[s] = LR_CELL_EMPTY; val[s] = 0x7f7f7f7f; }
-}
 __global__ void __launch_bounds__(256) fb_l0_insert_kernel(fb_table t, int total, fc_u64 *keys, int32_t *val, unsigned mask, fb_ctl *ctl)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -106,58 +92,6 @@ __global__ void __launch_bounds__(256) fb_l0_mark_kernel(fb_table t, int total, 
     if (i < n_sort) sortbuf[i] = out;
     const unsigned long long live = __ballot(out != LR_CELL_EMPTY);
     if ((threadIdx.x & 63) == 0 && live) atomicAdd(&ctl->c.n[0], __popcll(live));
-}
-__global__ void __launch_bounds__(256) fb_coarse_insert_kernel(const fc_u64 *__restrict__ rowkey, int lvl, fc_u64 *keys, int32_t *val, unsigned mask, const fb_ctl *ctl)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= ctl->c.n[lvl]) return;
-    atomicMin(&val[lr_cells_claim(keys, mask, fb_coarse_of(rowkey[i], lvl + 1))], i);
-}
-// as fc_coarse_mark_kernel, on the keys of level lvl
-__global__ void __launch_bounds__(256) fb_coarse_mark_kernel(const fc_u64 *__restrict__ rowkey, int lvl, const fc_u64 *__restrict__ keys, const int32_t *__restrict__ val,
-                                                             unsigned mask, fc_u64 *__restrict__ sortbuf, int n_sort, fb_ctl *ctl)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    fc_u64 out = LR_CELL_EMPTY;
-    if (i < ctl->c.n[lvl]) {
-        const fc_u64 key = fb_coarse_of(rowkey[i], lvl + 1);
-        const int s = fc_find(keys, mask, key);
-        if (s >= 0 && val[s] == i) out = key;
-    }
-    if (i < n_sort) sortbuf[i] = out;
-    const unsigned long long live = __ballot(out != LR_CELL_EMPTY);
-    if ((threadIdx.x & 63) == 0 && live) atomicAdd(&ctl->c.n[lvl + 1], __popcll(live));
-}
-// the sorted keys are the level's rows.  Level 0 (perm not null): the table held the cell's global input row, which goes to perm[r]
-__global__ void __launch_bounds__(256) fb_index_kernel(const fc_u64 *__restrict__ sorted, int lvl, const fc_u64 *__restrict__ keys, int32_t *__restrict__ val,
-                                                       unsigned mask, fc_u64 *__restrict__ rowkey, int32_t *__restrict__ perm, const fb_ctl *ctl)
-{
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    if (r >= ctl->c.n[lvl]) return;
-    const fc_u64 key = sorted[r];
-    const int s = fc_find(keys, mask, key);
-    int row = -1;
-    if (s >= 0) { row = val[s]; val[s] = r; }
-    if (perm) perm[r] = row;
-    rowkey[r] = key;
-}
-// as fc_nbr_kernel, on tagged keys: a neighbour outside the 19-bit field is absent, and the cloud's tag goes into the key that is looked up
-__global__ void __launch_bounds__(256) fb_nbr_kernel(const fc_u64 *__restrict__ rowkey, int lvl_out, const fc_u64 *__restrict__ keys, const int32_t *__restrict__ val,
-                                                     unsigned mask, int K, int step, int32_t *__restrict__ tbl, const fb_ctl *ctl)
-{
-    const int k3 = K * K * K, h = K >> 1;
-    const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= (size_t)ctl->c.n[lvl_out] * k3) return;
-    const int r = (int)(gid / k3), k = (int)(gid % k3);
-    const fc_u64 key = rowkey[r];
-    const int x = (int)((key >> 38) & FB_FIELD) + (k % K - h) * step, y = (int)((key >> 19) & FB_FIELD) + (k / K % K - h) * step,
-              z = (int)(key & FB_FIELD) + (k / (K * K) - h) * step;
-    int idx = -1;
-    if (x >= 0 && x < 2 * FB_BIAS && y >= 0 && y < 2 * FB_BIAS && z >= 0 && z < 2 * FB_BIAS) {
-        const int s = fc_find(keys, mask, (key & (63ull << 57)) | ((fc_u64)x << 38) | ((fc_u64)y << 19) | (fc_u64)z);
-        if (s >= 0) idx = val[s];
-    }
-    tbl[gid] = idx;
 }
 
 // ---- the two ends of the network ----------------------------------------------------------------------------------------------------
@@ -267,70 +201,32 @@ extern "C" int lr_fcgf_extract_batch(int nclouds, const int32_t *const *coords, 
     LR_TRY_HIP(lr_check_scratch(who, scratch, scratch_bytes, lr_fcgf_batch_scratch_bytes(nclouds, total), "lr_fcgf_batch_scratch_bytes(nclouds, sum of n)", LR_EINVAL,
                                 stream, nullptr));
 
+    hipStream_t st = (hipStream_t)stream;
+    const int K1 = p->conv1_kernel_size;
     fc_run R;
-    R.st = (hipStream_t)stream;
-    hipStream_t st = R.st;
-    R.base = reinterpret_cast<char *>(scratch);
-    R.L = fc_make_layout((size_t)total, FB_CTL_BYTES);
-    const fc_layout &L = R.L;
+    fc_carve(R, scratch, fc_make_layout((size_t)total, FB_CTL_BYTES), total, K1, weights, st);
+    const sp_layout &L = R.L;
     fb_ctl *ctl = R.at<fb_ctl>(0);
-    R.ctl = &ctl->c;
-    R.n = total;
-    {
-        const size_t slots = total > 0 ? 4 * L.cap_max : 0;
-        const int blocks = slots ? (int)((slots + 255) / 256 < 16384 ? (slots + 255) / 256 : 16384) : 1;
-        hipLaunchKernelGGL(fb_init_kernel, dim3(blocks), dim3(256), 0, st, R.at<fc_u64>(L.keys), R.at<int32_t>(L.val), slots, ctl);
-    }
+    sp_init_launch(R.keys[0], R.val[0], total > 0 ? 4 * L.cap_max : 0, R.ctl, FB_CTL_BYTES, st);
     if (total > 0) {
-        fc_stage_table(p->conv1_kernel_size, R.t);
-        { const float *W = weights; for (int s = 1; s <= FC_STAGES; ++s) { R.w[s] = W; W += fc_stage_floats(R.t[s]); } }
-        const size_t cap = lr_cells_capacity((size_t)total), m = L.m;
-        const unsigned mask = (unsigned)(cap - 1);
-        fc_u64 *rowkey[4];                              // the levels' rows as keys, and perm, in the place of the single call's coords (36 m bytes)
-        for (int l = 0; l < 4; ++l) {
-            R.keys[l] = R.at<fc_u64>(L.keys) + (size_t)l * L.cap_max;
-            R.val[l] = R.at<int32_t>(L.val) + (size_t)l * L.cap_max;
-            R.nbr27[l] = R.at<int32_t>(L.nbr27) + (size_t)l * m * 27;
-            rowkey[l] = R.at<fc_u64>(L.coords) + (size_t)l * m;
-            if (l < 3) { R.dn[l] = R.at<int32_t>(L.dn) + (size_t)l * m * 27; R.up[l] = R.at<int32_t>(L.up) + (size_t)l * m * 27; }
-        }
-        int32_t *perm = R.at<int32_t>(L.coords + 4 * m * 8), *nbr125 = R.at<int32_t>(L.nbr125);
-        fc_u64 *sortbuf = R.at<fc_u64>(L.sort);
         const int gn = R.grid((size_t)total);
-        unsigned n_sort = FC_SORT_CHUNK;
-        while (n_sort < (unsigned)total) n_sort <<= 1;
-        auto sort = [&]() { fc_sort_launch(sortbuf, n_sort, st); };
 
-        // maps
-        hipLaunchKernelGGL(fb_l0_insert_kernel, dim3(gn), dim3(256), 0, st, t, total, R.keys[0], R.val[0], mask, ctl);
-        hipLaunchKernelGGL(fb_l0_check_kernel, dim3(gn), dim3(256), 0, st, t, total, R.keys[0], R.val[0], mask, ctl);
-        hipLaunchKernelGGL(fb_l0_mark_kernel, dim3(R.grid(n_sort)), dim3(256), 0, st, t, total, sortbuf, (int)n_sort, ctl);
-        sort();
-        hipLaunchKernelGGL(fb_index_kernel, dim3(gn), dim3(256), 0, st, sortbuf, 0, R.keys[0], R.val[0], mask, rowkey[0], perm, ctl);
-        for (int l = 0; l < 3; ++l) {
-            hipLaunchKernelGGL(fb_coarse_insert_kernel, dim3(gn), dim3(256), 0, st, rowkey[l], l, R.keys[l + 1], R.val[l + 1], mask, ctl);
-            hipLaunchKernelGGL(fb_coarse_mark_kernel, dim3(R.grid(n_sort)), dim3(256), 0, st, rowkey[l], l, R.keys[l + 1], R.val[l + 1], mask, sortbuf, (int)n_sort, ctl);
-            sort();
-            hipLaunchKernelGGL(fb_index_kernel, dim3(gn), dim3(256), 0, st, sortbuf, l + 1, R.keys[l + 1], R.val[l + 1], mask, rowkey[l + 1], (int32_t *)nullptr, ctl);
-        }
-        const int K1 = p->conv1_kernel_size;
-        for (int l = 0; l < 4; ++l)
-            hipLaunchKernelGGL(fb_nbr_kernel, dim3(R.grid((size_t)total * 27)), dim3(256), 0, st, rowkey[l], l, R.keys[l], R.val[l], mask, 3, 1 << l, R.nbr27[l], ctl);
-        if (K1 == 5)
-            hipLaunchKernelGGL(fb_nbr_kernel, dim3(R.grid((size_t)total * 125)), dim3(256), 0, st, rowkey[0], 0, R.keys[0], R.val[0], mask, 5, 1, nbr125, ctl);
-        for (int l = 0; l < 3; ++l) {
-            hipLaunchKernelGGL(fb_nbr_kernel, dim3(R.grid((size_t)total * 27)), dim3(256), 0, st, rowkey[l + 1], l + 1, R.keys[l], R.val[l], mask, 3, 1 << l, R.dn[l], ctl);
-            hipLaunchKernelGGL(fb_nbr_kernel, dim3(R.grid((size_t)total * 27)), dim3(256), 0, st, rowkey[l], l, R.keys[l + 1], R.val[l + 1], mask, 3, -(1 << l), R.up[l], ctl);
-        }
+        // maps: level 0 sorted, with perm (in the room behind the levels' keys)
+        hipLaunchKernelGGL(fb_l0_insert_kernel, dim3(gn), dim3(256), 0, st, t, total, R.keys[0], R.val[0], R.mask, ctl);
+        hipLaunchKernelGGL(fb_l0_check_kernel, dim3(gn), dim3(256), 0, st, t, total, R.keys[0], R.val[0], R.mask, ctl);
+        hipLaunchKernelGGL(fb_l0_mark_kernel, dim3(R.grid(R.n_sort)), dim3(256), 0, st, t, total, R.sortbuf, (int)R.n_sort, ctl);
+        fc_sort_launch(R.sortbuf, R.n_sort, st);
+        hipLaunchKernelGGL(sp_index_kernel, dim3(gn), dim3(256), 0, st, R.sortbuf, 0, R.keys[0], R.val[0], R.mask, R.rowkey[0], R.perm, R.ctl);
+        fc_maps<fb_codec>(R, K1);
 
         const int stop = g_fb_stop_after;
         const bool cut = fc_stages(R,
             [&](float *X) {
-                hipLaunchKernelGGL(fb_conv1_kernel, dim3(R.grid((size_t)total * 32)), dim3(256), 0, st, t, rowkey[0], perm, K1 == 5 ? nbr125 : R.nbr27[0], K1 * K1 * K1,
-                                   R.w[1], R.w[1] + (size_t)K1 * K1 * K1 * 32, R.w[1] + (size_t)K1 * K1 * K1 * 32 + 32, X, ctl);
+                hipLaunchKernelGGL(fb_conv1_kernel, dim3(R.grid((size_t)total * 32)), dim3(256), 0, st, t, R.rowkey[0], R.perm, fc_conv1_table(R, K1), R.t[1].k3,
+                                   R.w[1], R.w[1] + (size_t)R.t[1].k3 * 32, R.w[1] + (size_t)R.t[1].k3 * 32 + 32, X, ctl);
             },
             [&](int s, const float *, int) { return s == stop; });
-        if (!cut) hipLaunchKernelGGL(fb_norm_kernel, dim3(gn), dim3(256), 0, st, t, R.at<float>(L.Y), rowkey[0], perm, ctl);
+        if (!cut) hipLaunchKernelGGL(fb_norm_kernel, dim3(gn), dim3(256), 0, st, t, R.Y, R.rowkey[0], R.perm, ctl);
     }
     hipLaunchKernelGGL(fb_finish_kernel, dim3(R.grid((size_t)(total > nclouds ? total : nclouds))), dim3(256), 0, st, t, total, ctl, results);
     LR_LAUNCH_CHECK();

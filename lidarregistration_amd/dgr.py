@@ -14,7 +14,7 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _ext, corrset, devmem
+from . import _ext, corrset, devmem, resunet
 from .devmem import ptr
 from .matching import _f32, _stream
 
@@ -116,8 +116,7 @@ class DGRTail:
 
 
 # ---- the 6-D inlier network -----------------------------------------------------------------------------------------------------------
-BN_EPS = 1e-5
-N_STAGES = 23
+N_STAGES = resunet.N_STAGES
 NK = 729                                              # 3^6 offsets
 MAX_N = 131072                                        # rows per lr_dgr_inlier
 MAX_TAIL = 32768                                      # rows per lr_dgr_refine
@@ -145,32 +144,18 @@ def check_widths(widths, key=None):
 
 def inlier_stage_plan(widths=WIDTHS):
     """The 23 stages in order: (conv module, norm module | None, offsets, Cin, Cout) -- the module names of DGR/model/resunet.py:442-596."""
-    C1, C2, C3, C4, T4, T3, T2, T1 = check_widths(widths)
-    plan = [("conv1", "norm1", NK, 1, C1)]
-
-    def block(name, c):
-        return [(f"{name}.conv1", f"{name}.norm1", NK, c, c), (f"{name}.conv2", f"{name}.norm2", NK, c, c)]
-
-    plan += block("block1", C1)
-    for i, (cin, cout) in zip((2, 3, 4), ((C1, C2), (C2, C3), (C3, C4))):
-        plan += [(f"conv{i}", f"norm{i}", NK, cin, cout)] + block(f"block{i}", cout)
-    for i, (cin, cout) in zip((4, 3, 2), ((C4, T4), (T4 + C3, T3), (T3 + C2, T2))):
-        plan += [(f"conv{i}_tr", f"norm{i}_tr", NK, cin, cout)] + block(f"block{i}_tr", cout)
-    plan += [("conv1_tr", None, 1, T2 + C1, T1), ("final", None, 1, T1, 1)]
-    assert len(plan) == N_STAGES
-    return plan
+    return resunet.stage_plan(check_widths(widths), NK, NK, 1)
 
 
 def inlier_packed_floats(widths=WIDTHS):
-    return sum(k * cin * cout + 2 * cout for _, _, k, cin, cout in inlier_stage_plan(widths))
+    return resunet.packed_floats(inlier_stage_plan(widths))
 
 
 def widths_of(sd):
     """I5: the eight widths from the kernels' shapes.  conv1.kernel must be [729, 1, C] (K = 3 and the feature `ones`)."""
-    from .fcgf import _np64
     out = []
     for key in _WIDTH_KEYS:
-        shape = np.asarray(_np64(sd, key + ".kernel", None, _SD)).shape
+        shape = resunet.np64(sd, key + ".kernel", None, _SD).shape
         if key == "conv1" and (len(shape) != 3 or shape[0] != NK or shape[1] != 1):
             raise ValueError(f"{_SD}: conv1.kernel has shape {shape}, expected [729, 1, C]: conv1_kernel_size 3 and inlier_feature_type 'ones'")
         out.append(int(shape[-1]))
@@ -180,37 +165,12 @@ def widths_of(sd):
 def inlier_fold(sd, dtype=np.float32):
     """[(W [offsets,Cin,Cout], scale [Cout], offset [Cout])] per stage as `dtype`, the widths read from the kernels (I5): BatchNorm folded
     in fp64 and rounded once, as fcgf.fold.  A missing or extra key, a wrong shape or a non-finite value is a ValueError naming the key."""
-    from .fcgf import _np64
-    widths = widths_of(sd)
-    known, out = set(), []
-    for conv, norm, k, cin, cout in inlier_stage_plan(widths):
-        W = _np64(sd, conv + ".kernel", (k, cin, cout), _SD)
-        known.add(conv + ".kernel")
-        if norm:
-            names = [f"{norm}.bn.{f}" for f in ("weight", "bias", "running_mean", "running_var")]
-            g, b, mean, var = (_np64(sd, nm, (cout,), _SD) for nm in names)
-            known.update(names + [f"{norm}.bn.num_batches_tracked"])
-            with np.errstate(invalid="ignore", divide="ignore"):
-                scale = g / np.sqrt(var + BN_EPS)
-                offset = (0.0 - mean) * scale + b
-            if not (np.isfinite(scale).all() and np.isfinite(offset).all()):
-                raise ValueError(f"{_SD}: {norm}.bn.running_var does not fold to a finite scale")
-        else:
-            scale = np.ones(cout)
-            offset = np.zeros(cout)
-            if conv == "final":
-                offset = _np64(sd, "final.bias", (cout,), _SD)
-                known.add("final.bias")
-        out.append((W.astype(dtype), scale.astype(dtype), offset.astype(dtype)))
-    extra = sorted(set(sd) - known)
-    if extra:
-        raise ValueError(f"{_SD}: unexpected key {extra[0]!r}")
-    return out
+    return resunet.fold(sd, inlier_stage_plan(widths_of(sd)), _SD, True, dtype)
 
 
 def inlier_pack(stages):
     """The flat float32 blob of lr_dgr_inlier_weights_bytes(widths) bytes from inlier_fold's stages: per stage W, scale, offset."""
-    return np.concatenate([np.concatenate([W.reshape(-1), s, o]) for W, s, o in stages]).astype(np.float32, copy=False)
+    return resunet.pack(stages)
 
 
 def widths_of_stages(stages):

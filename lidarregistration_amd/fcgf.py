@@ -11,89 +11,41 @@ import ctypes
 import numpy as np
 import torch
 
-from . import _ext, devmem
+from . import _ext, devmem, resunet
 from .devmem import ptr
 
-BN_EPS = 1e-5              # MinkowskiBatchNorm wraps torch.nn.BatchNorm1d and keeps its default
-N_STAGES = 23
+N_STAGES = resunet.N_STAGES
 MAX_N = 1 << 20
 MAX_CLOUDS = 64            # clouds per lr_fcgf_extract_batch (MAX_N rows together)
+WIDTHS = (32, 64, 128, 256, 128, 64, 64, 64)          # ResUNetBN2C: C1 C2 C3 C4 (down), T4 T3 T2 T1 (up)
 
 
 def stage_plan(conv1_kernel_size=5):
     """The 23 stages in order: (conv module, norm module | None, K^3, Cin, Cout) -- the module names of fcgf.py:644-798."""
     if conv1_kernel_size not in (3, 5):
         raise ValueError(f"conv1_kernel_size must be 3 or 5, not {conv1_kernel_size!r}")
-    plan = [("conv1", "norm1", conv1_kernel_size ** 3, 1, 32)]
-
-    def block(name, c):
-        return [(f"{name}.conv1", f"{name}.norm1", 27, c, c), (f"{name}.conv2", f"{name}.norm2", 27, c, c)]
-
-    plan += block("block1", 32)
-    for i, (cin, cout) in zip((2, 3, 4), ((32, 64), (64, 128), (128, 256))):
-        plan += [(f"conv{i}", f"norm{i}", 27, cin, cout)] + block(f"block{i}", cout)
-    for i, (cin, cout) in zip((4, 3, 2), ((256, 128), (256, 64), (128, 64))):
-        plan += [(f"conv{i}_tr", f"norm{i}_tr", 27, cin, cout)] + block(f"block{i}_tr", cout)
-    plan += [("conv1_tr", None, 1, 96, 64), ("final", None, 1, 64, 32)]
-    assert len(plan) == N_STAGES
-    return plan
+    return resunet.stage_plan(WIDTHS, conv1_kernel_size ** 3, 27, 32)
 
 
 def packed_floats(conv1_kernel_size=5):
-    return sum(k3 * cin * cout + 2 * cout for _, _, k3, cin, cout in stage_plan(conv1_kernel_size))
-
-
-def _np64(sd, key, shape=None, what="FCGF state dict"):
-    if key not in sd:
-        raise ValueError(f"{what}: missing key {key!r}")
-    v = sd[key]
-    if isinstance(v, torch.Tensor):
-        v = v.detach().cpu().numpy()
-    v = np.asarray(v, np.float64)
-    if shape is not None:
-        if v.shape != shape and not (v.size == int(np.prod(shape)) and v.squeeze().shape == tuple(s for s in shape if s != 1)):
-            raise ValueError(f"{what}: {key} has shape {v.shape}, expected {shape}")
-        v = v.reshape(shape)
-    if not np.isfinite(v).all():
-        raise ValueError(f"{what}: {key} holds a non-finite value")
-    return v
+    return resunet.packed_floats(stage_plan(conv1_kernel_size))
 
 
 def fold(sd, conv1_kernel_size=5, dtype=np.float32):
     """[(W [K^3,Cin,Cout], scale [Cout], offset [Cout])] per stage, as `dtype`: BatchNorm folded in fp64 and rounded once (float64: not at
     all -- what tests/fcgf_cpu.py's fp64 restatement evaluates).  A 1x1 kernel may be [Cin,Cout] or [1,Cin,Cout]; a missing key, a wrong
     shape or a non-finite value is a ValueError naming the key."""
-    out = []
-    for conv, norm, k3, cin, cout in stage_plan(conv1_kernel_size):
-        W = _np64(sd, conv + ".kernel", (k3, cin, cout))
-        if norm:
-            g, b = _np64(sd, norm + ".bn.weight", (cout,)), _np64(sd, norm + ".bn.bias", (cout,))
-            mean, var = _np64(sd, norm + ".bn.running_mean", (cout,)), _np64(sd, norm + ".bn.running_var", (cout,))
-            with np.errstate(invalid="ignore", divide="ignore"):
-                scale = g / np.sqrt(var + BN_EPS)
-                offset = (0.0 - mean) * scale + b
-            if not (np.isfinite(scale).all() and np.isfinite(offset).all()):
-                raise ValueError(f"FCGF state dict: {norm}.bn.running_var does not fold to a finite scale")
-        else:
-            scale = np.ones(cout)
-            offset = _np64(sd, conv + ".bias", (cout,)) if conv == "final" else np.zeros(cout)
-        out.append((W.astype(dtype), scale.astype(dtype), offset.astype(dtype)))
-    return out
+    return resunet.fold(sd, stage_plan(conv1_kernel_size), "FCGF state dict", False, dtype)
 
 
 def pack(sd, conv1_kernel_size=5):
     """The flat float32 blob of lr_fcgf_weights_bytes(conv1_kernel_size) bytes: per stage W, scale, offset."""
-    return np.concatenate([np.concatenate([W.reshape(-1), s, o]) for W, s, o in fold(sd, conv1_kernel_size)]).astype(np.float32)
+    return resunet.pack(fold(sd, conv1_kernel_size))
 
 
 def unpack(blob, conv1_kernel_size=5):
     """pack() undone: the stages of a blob."""
-    stages, at = [], 0
-    for _, _, k3, cin, cout in stage_plan(conv1_kernel_size):
-        W = blob[at:at + k3 * cin * cout].reshape(k3, cin, cout); at += k3 * cin * cout
-        stages.append((W, blob[at:at + cout], blob[at + cout:at + 2 * cout])); at += 2 * cout
-    assert at == len(blob), (at, len(blob))
-    return stages
+    return resunet.unpack(blob, stage_plan(conv1_kernel_size))
 
 
 class FCGF:
@@ -123,7 +75,7 @@ class FCGF:
         ck = torch.load(path, map_location="cpu")
         sd = ck["state_dict"] if isinstance(ck, dict) and "state_dict" in ck else ck
         if conv1_kernel_size is None:
-            k3 = int(np.asarray(_np64(sd, "conv1.kernel")).shape[0])
+            k3 = int(resunet.np64(sd, "conv1.kernel", None, "FCGF state dict").shape[0])
             conv1_kernel_size = {27: 3, 125: 5}.get(k3)
             if conv1_kernel_size is None:
                 raise ValueError(f"FCGF state dict: conv1.kernel has {k3} offsets, expected 27 or 125")

@@ -248,6 +248,16 @@ def test_weights_and_scratch_sizes():
     assert L.lr_dgr_inlier_scratch_bytes(131073, _w8(THIN)) == 0 and L.lr_dgr_inlier_scratch_bytes(-1, _w8(THIN)) == 0
 
 
+def test_the_size_functions_keep_their_values():
+    """Literal values, read from the library of the commit before the maps, the convolution and the layout moved into csrc/lr_sparse.h
+    (built from that commit with the Makefile's flags): the layout function is shared now and must size every call as before."""
+    L = _ext.lib()
+    ns = (0, 1, 64, 65, 131072)
+    assert [L.lr_dgr_inlier_scratch_bytes(n, _w8(dgr6_cpu.WIDTHS)) for n in ns] == [65792, 2201344, 2201344, 4336896, 4373676288]
+    assert [L.lr_dgr_inlier_scratch_bytes(n, _w8(THIN)) for n in ns] == [65792, 1996544, 1996544, 3927296, 3954245888]
+    assert [L.lr_dgr_inlier_weights_bytes(_w8(w)) for w in (dgr6_cpu.WIDTHS, THIN)] == [943707272, 65798920]
+
+
 def test_refusals_before_any_launch():
     """n above the limit, null pointers, struct_size, widths, tap: LR_EINVAL naming the argument; none of these calls reaches a device."""
     L = _ext.lib()

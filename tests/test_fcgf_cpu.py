@@ -181,6 +181,16 @@ def test_weights_bytes_and_one_by_one_kernel_forms():
     assert np.array_equal(fcgf.pack(a, 3), fcgf.pack(b, 3))
 
 
+def test_the_size_functions_keep_their_values():
+    """Literal values, read from the library of the commit before the maps, the convolution and the layout moved into csrc/lr_sparse.h
+    (built from that commit with the Makefile's flags): the layout function is shared now and must size every call as before."""
+    L = _ext.lib()
+    ns = (0, 1, 64, 65, 1 << 20)
+    assert [L.lr_fcgf_scratch_bytes(n) for n in ns] == [65792, 436480, 436480, 807168, 6073417984]
+    assert [L.lr_fcgf_batch_scratch_bytes(3, n) for n in ns] == [66048, 436736, 436736, 807424, 6073418240]
+    assert [L.lr_fcgf_weights_bytes(k) for k in (3, 5)] == [35001728, 35014272]
+
+
 def test_state_dict_refusals_name_the_key():
     sd = fcgf_cases.make_state_dict(4, 3)
     for key in ("conv1.kernel", "block2.norm1.bn.running_var", "final.bias", "conv3_tr.kernel", "norm4_tr.bn.weight"):

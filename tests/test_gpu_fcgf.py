@@ -91,6 +91,22 @@ def test_coarse_coordinate_sets_in_contract_order(name):
         assert act.shape == (len(L[lvl]), 32 << lvl)
 
 
+def test_cells_at_the_ends_of_the_21_bit_fields_decode_and_lose_their_outside_neighbours():
+    """The tap's cells are decoded from the levels' keys.  Four cells at +-(2^20 - 3), the last cells inside the range limit: the level-3
+    parent of -(2^20 - 3) is -2^20, biased field 0, and its -8 neighbour (like the -4 one of stage 10's table) leaves the field: absent."""
+    M = (1 << 20) - 3
+    cells = np.array([[M, 0, 0], [-M, 0, 0], [0, -M, M], [-M, -M, -M]], np.int32)
+    assert fcgf_cpu.status_of(cells) == 0
+    r = fcgf_cpu.run(cells, stages(5), 5, mode="chain")
+    assert r["levels"][3].min() == -(1 << 20) and (r["levels"][3] + fcgf_cpu.BIAS).min() == 0
+    for s, lvl in ((1, 0), (4, 1), (7, 2), (10, 3)):
+        act, tc = model().tap(cells, s)
+        assert model().last_info == dict(status=0, n=4, n_tap=len(r["levels"][lvl]))
+        assert np.array_equal(host(tc), r["levels"][lvl]), (s, host(tc))
+        assert act.shape == r["acts"][s].shape and np.array_equal(bits(host(act)), bits(r["acts"][s])), s
+    assert np.array_equal(bits(host(model().features(cells))), bits(r["out"])) and model().last_info["status"] == 0      # stages 11, 12: the -8 neighbour
+
+
 # ---- 6. F10 ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n0", [4400, 40000], ids=["n4000", "n30000"])
 def test_same_bits_whatever_the_scratch_the_row_order_or_a_shift_by_eight(n0):

@@ -30,7 +30,7 @@ from tests import dgr6_cpu, fcgf_cases  # noqa: E402
 
 
 def tile(cout):
-    return 128 if cout % 64 else 64          # output rows per block of d6_conv_kernel
+    return 128 if cout % 64 else 64          # output rows per block of sp_conv_kernel (csrc/lr_sparse.h)
 
 
 def work(rows, widths):

@@ -33,7 +33,7 @@ sys.path.insert(0, ROOT)
 from lidarregistration_amd import _ext, devmem, fcgf, synth, voxel  # noqa: E402
 from tests import fcgf_cases, fcgf_cpu  # noqa: E402
 
-TILE = {32: 128, 64: 64, 128: 64, 256: 64}        # output rows per block of fc_conv_kernel by Cout (every column tile of a row tile issues the same offsets)
+TILE = {32: 128, 64: 64, 128: 64, 256: 64}        # output rows per block of sp_conv_kernel (csrc/lr_sparse.h) by Cout (every column tile of a row tile issues the same offsets)
 
 
 def work(cells, k1=5):
