@@ -33,7 +33,7 @@ logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s", datefm
 
 # --algo -> the module of lidarregistration_amd whose eval_pairs runs it (a correspondence-set solver on corrset.eval_pairs); every other
 # --algo goes through the FR pipeline's engines (harness.eval_pairs / eval_pairs_serial)
-CORRSET_ENGINES = {"TEASER": "teaser", "SM": "sm", "PointDSC": "pointdsc"}
+CORRSET_ENGINES = {"TEASER": "teaser", "SM": "sm", "PointDSC": "pointdsc", "DGR": "dgr"}
 
 
 def str2bool(v):
@@ -53,7 +53,7 @@ def get_args(argv=None):
         world_size, rank, do_analysis = 1, 0, True
     p = argparse.ArgumentParser()
     p.add_argument("--dataset", type=str, default="synthetic", help="A, B, S, K, L (balanced sets) or synthetic")
-    p.add_argument("--algo", type=str, default="RANSAC", choices=["RANSAC", "TEASER", "SM", "PointDSC"])
+    p.add_argument("--algo", type=str, default="RANSAC", choices=["RANSAC", "TEASER", "SM", "PointDSC", "DGR"])
     p.add_argument("--codebase", type=str, default="GC", choices=["open3D", "GC"])
     p.add_argument("--mode", type=str, default="MNN", help="MNN (alias MMN), GPF or no_filter; with --algo TEASER: FAIL_TOLERANT or anything else")
     p.add_argument("--max_samples", type=int, default=None)
@@ -72,6 +72,8 @@ def get_args(argv=None):
     p.add_argument("--chosen_snapshot", type=str, default="", help="--algo PointDSC: directory with config.json and models/model_best.pkl (the reference's snapshot layout)")
     p.add_argument("--solver", type=str, default="SVD", choices=["SVD", "RANSAC"], help="--algo PointDSC: SVD; RANSAC is not built and is refused")
     p.add_argument("--fcgf_weights_file", type=str, default=None, help="FCGF checkpoint (torch.load(file)['state_dict'], ResUNetBN2C): compute the descriptors from the cloud cache's raw scans on the GPU instead of reading a feature cache")
+    p.add_argument("--dgr_weights", type=str, default="", help="--algo DGR: the reference's DGR checkpoint; only state_dict_inlier and, where present, config are read")
+    p.add_argument("--dgr_clip_weight_thresh", type=float, default=0.05, help="--algo DGR: clip_weight_thresh (DGR/config.py)")
     # additions of this implementation
     p.add_argument("--num_node", type=int, default=12000, help="--algo PointDSC: at most this many source points per pair (test.py:247)")
     p.add_argument("--num_pairs", type=int, default=32, help="synthetic: number of pairs")
@@ -89,6 +91,8 @@ def get_args(argv=None):
         p.error("--solver RANSAC is not built: --algo PointDSC fits by SVD")
     if args.algo == "PointDSC" and not args.chosen_snapshot:
         p.error("--algo PointDSC needs --chosen_snapshot DIR (DIR/config.json and DIR/models/model_best.pkl)")
+    if args.algo == "DGR" and not args.dgr_weights:
+        p.error("--algo DGR needs --dgr_weights FILE (the reference's DGR checkpoint: state_dict_inlier)")
     if args.fcgf_weights_file and not (os.environ.get("LIDARREG_CLOUD_CACHE") and os.environ.get("LIDARREG_BALANCED_SETS") and args.dataset != "synthetic"):
         p.error("--fcgf_weights_file computes the descriptors from raw scans and needs a cloud cache: set LIDARREG_CLOUD_CACHE and LIDARREG_BALANCED_SETS and name a list --dataset (A, B, S, K, L)")
     args.start_time, args.tmp_file_base, args.world_size, args.rank, args.do_analysis = start_time, tmp_file_base, world_size, rank, do_analysis

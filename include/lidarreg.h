@@ -959,6 +959,32 @@ LR_API int lr_dgr_inlier(const int32_t *coords, int n, const float *weights, siz
                          lr_dgr_inlier_result *result, float *logit_out, int32_t *tap_coords, void *scratch, size_t scratch_bytes,
                          void *stream);
 
+/* ---- n4: the inlier network on up to 8 pairs' correspondence sets in one call: one sequence of launches over the concatenated rows.
+ * coords / n / logit_out are HOST arrays of length npairs, carried by value in a kernel-argument table (nothing the caller must keep
+ * alive).  The weight blob and the params struct are n3's.  DESIGN.md §20.7.
+ *  P1  sizes: 1 <= npairs <= 8; 0 <= n[k] <= 131072; sum of n <= 131072; p->tap must be 0 (a batch has no tap).  A cell's key carries its
+ *      pair in bits 60 .. 62, above the six 10-bit fields; bit 63 stays clear (with a fourth tag bit, tag 15 and six fields of 1023 --
+ *      a neighbour query -- would be the table's empty-slot word), hence 8 pairs.
+ *  P2  for every pair k, logit_out[k] [n_k] and results[k] hold exactly the bytes lr_dgr_inlier writes for that pair alone ({status,
+ *      n = n_k, n_tap = status ? 0 : n_k, reserved = 0}), whatever else is in the batch, at whichever position, and whatever the scratch
+ *      held.  There is no deviation in the limits: every pair has its own origin 8 floor(min_a / 8) (six integer minima per pair on the
+ *      device), so I2's extent limit of 1007 and F10 hold per pair, wherever each pair lies.  n_k = 0: status 0, only the result block is
+ *      written.  (I3 fixes the chain of an output element by idx(o) and the channel, not by the order of the rows, and the tag makes
+ *      every pair's maps its own.)
+ *  P3  the status is per pair; 3 (extent) wins over 2 (duplicate).  A refused pair has its n_k logits set to 0, takes no part in the maps
+ *      and changes no bit of another pair's output.  The same 6-D cell in two pairs is not a duplicate; no pair finds another's cell.
+ *  P4  refusals: LR_EINVAL before any launch, lr_last_error naming the argument and, where it applies, the pair: struct_size, a width,
+ *      tap != 0, npairs outside 1..8, an n[k] outside its range or a sum above 131072, null coords / n / logit_out / results, a null
+ *      coords[k] / logit_out[k] with n[k] > 0, null / misaligned / short weights, and the scratch, stream and device rules of n3.
+ *  P5  kernel launches only: no host synchronisation, no allocation, graph-capturable; integer atomics only.                          */
+/* Caller-owned device scratch for npairs pairs of total_n rows together (0 when npairs is outside 1..8, total_n outside 0..131072 or a
+ * width is out of range).                                                                                                          */
+LR_API size_t lr_dgr_inlier_batch_scratch_bytes(int npairs, int total_n, const int32_t widths[8]);
+/* results: device, [npairs].  scratch: >= lr_dgr_inlier_batch_scratch_bytes(npairs, sum of n, p->widths) bytes, 256-byte aligned. */
+LR_API int lr_dgr_inlier_batch(int npairs, const int32_t *const *coords, const int32_t *n, const float *weights, size_t weights_bytes,
+                               const lr_dgr_inlier_params *p, lr_dgr_inlier_result *results, float *const *logit_out,
+                               void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- d1: Deep Global Registration's robust pose refinement over M weighted correspondences src[i] <-> tgt[i] -----------------------
  * Replaces what DeepGlobalRegistration.register does once it has the inlier weights (DGR/core/deep_global_registration.py:403-435): the
  * weight-sum decision and GlobalRegistration (DGR/core/registration.py:16-64, :116-194) under HighDimSmoothL1Loss (DGR/core/loss.py:42-61):

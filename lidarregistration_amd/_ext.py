@@ -32,6 +32,7 @@ SYMBOLS = [
     "lr_fcgf_weights_bytes", "lr_fcgf_scratch_bytes", "lr_fcgf_extract", "lr_fcgf_batch_scratch_bytes", "lr_fcgf_extract_batch", "lr_debug_fcgf_batch_stop_after",
     "lr_dgr_scratch_bytes", "lr_dgr_refine", "lr_dgr_refine_batch",
     "lr_dgr_inlier_weights_bytes", "lr_dgr_inlier_scratch_bytes", "lr_dgr_inlier",
+    "lr_dgr_inlier_batch_scratch_bytes", "lr_dgr_inlier_batch",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -376,6 +377,8 @@ def lib():
         L.lr_dgr_inlier_weights_bytes.argtypes = [w8]
         L.lr_dgr_inlier_scratch_bytes.argtypes = [ci, w8]
         L.lr_dgr_inlier.argtypes = [vp, ci, vp, sz, ctypes.POINTER(DgrInlierParams), vp, vp, vp, vp, sz, vp]
+        L.lr_dgr_inlier_batch_scratch_bytes.argtypes = [ci, ci, w8]
+        L.lr_dgr_inlier_batch.argtypes = [ci, pp, ip, vp, sz, ctypes.POINTER(DgrInlierParams), vp, pp, vp, sz, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

@@ -1,6 +1,6 @@
 """What the correspondence-set back ends (teaser.py, sm.py, pointdsc.py, dgr.py) share: the ctypes plumbing of a lr_*_batch / lr_* call
 (BatchCall: lr_teaser, lr_sm, lr_pdsc_encode, lr_pdsc_solve, lr_pdsc_register, lr_dgr_refine and their _batch forms) and the batched
-engine of ``python -m test --algo TEASER | SM | PointDSC`` (eval_pairs).  A back end describes each entry-point pair to them (Solver,
+engine of ``python -m test --algo TEASER | SM | PointDSC | DGR`` (eval_pairs).  A back end describes each entry-point pair to them (Solver,
 In, Out) and keeps its own correspondences_dev, params and result decoding.  The C side's counterpart is csrc/lr_corrset.h.
 """
 import ctypes

@@ -7,7 +7,8 @@
 // the +8 leaves room for the -8 neighbour of level 3.  Level 0 is kept in input order.
 // The maps (dense gather tables [rows][729], one thread per entry), the gather convolution sp_conv_kernel (its streamed table form), the
 // stage table, the scratch layout and the stage schedule are lr_sparse.h's.  Here: the origin and the key of a row, conv1 (Cin = 1, ones)
-// and final (Cout = 1), which are vector kernels, and the entry point.
+// and final (Cout = 1), which are vector kernels, and the entry point.  The batched entry (lr_dgr_inlier_batch, contract n4) is
+// lr_dgr6_batch.h, included at the end.
 #include "lr_scratch.h"
 #include "lr_sparse.h"
 
@@ -167,3 +168,5 @@ extern "C" int lr_dgr_inlier(const int32_t *coords, int n, const float *weights,
     LR_LAUNCH_CHECK();
     return LR_OK;
 }
+
+#include "lr_dgr6_batch.h"

@@ -7,7 +7,10 @@ include/lidarreg.h (d1) and DESIGN.md §19.
 
 ``InlierNet`` is the 6-D inlier network that gives the weights (lr_dgr_inlier, csrc/lr_dgr6.hip; contract n3, DESIGN.md §20, restated in
 numpy in tests/dgr6_cpu.py) and ``DGR`` the whole DeepGlobalRegistration.register (:352-459): voxel de-duplication, FCGF features, the
-feature nearest neighbour, the inlier network, the tail.  There is no CPU fallback.
+feature nearest neighbour, the inlier network, the tail.  Their batched forms -- ``InlierNet.logits_batch`` / ``weights_batch``
+(lr_dgr_inlier_batch, csrc/lr_dgr6_batch.h; contract n4, DESIGN.md §20.7: up to 8 pairs and 131 072 rows per call), ``DGRTail.register_batch``
+and ``DGR.register_batch`` -- give every pair the bytes of its one-pair call, and ``eval_pairs`` is the engine of ``python -m test --algo
+DGR --dgr_weights FILE``.  There is no CPU fallback.
 """
 import ctypes
 
@@ -19,6 +22,7 @@ from .devmem import ptr
 from .matching import _f32, _stream
 
 RESULT_BYTES = ctypes.sizeof(_ext.DgrResult)
+MAX_REFINE_BATCH = 64                                 # LR_MAX_BATCH: pairs per lr_dgr_refine_batch
 STATUS = {0: "refined", 1: "no live correspondence", 2: "weight sum below the threshold", 3: "non-finite loss or parameter"}
 
 
@@ -114,11 +118,73 @@ class DGRTail:
             res["w_icp"], _ = icp_dev(x0, x1, T, max_dist=thr)
         return res
 
+    def wsum_threshold(self, m):
+        """max(4000, M) * clip_weight_thresh (:407) as the double `register` hands to the library."""
+        return max(4000, int(m)) * self.clip_weight_thresh
+
+    def status_of(self, info, m):
+        """G9 on the host, from the result block of a refinement run with wsum_threshold = 0 (lr_dgr_refine_batch takes ONE threshold per
+        call, DGR's is per pair): 1 no live row, 2 when w1 < max(4000, M) clip -- the comparison of two doubles the device makes -- else
+        the block's own status."""
+        if info["L"] == 0:
+            return 1
+        return 2 if info["w1"] < self.wsum_threshold(m) else info["status"]
+
+    def register_batch(self, xyz0s, xyz1s, idx0s, idx1s, weights, m_thresholds=None, inlier_statuses=None):
+        """`register` for many pairs: -> [{'base', 'w_icp'}], self.last a list of infos.  Every pair is refined in lr_dgr_refine_batch calls
+        of up to 64 pairs with wsum_threshold = 0; the weight-sum decision is status_of's, and the refinement of a pair that takes the
+        safeguard is discarded (its info is G9's: the identity was never returned, iterations = break_count = 0, loss = 0).  A safeguarded
+        pair runs the same RANSAC as in `register`.  inlier_statuses (InlierNet.weights_batch): a pair the network refused (2 / 3) takes
+        the safeguard too, with info['inlier_status'] set, so that one bad pair never ends a shard."""
+        from .ransac import icp_dev, ransac_dev
+        P = len(xyz0s)
+        lists = dict(xyz1s=xyz1s, idx0s=idx0s, idx1s=idx1s, weights=weights, m_thresholds=m_thresholds, inlier_statuses=inlier_statuses)
+        for name, v in lists.items():
+            if v is not None and len(v) != P:
+                raise ValueError(f"{name} has {len(v)} entries, xyz0s {P}")
+        thr = 2 * self.voxel_size
+        x0s, x1s, srcs, tgts, ws = [], [], [], [], []
+        for k in range(P):
+            x0, x1 = _f32(xyz0s[k]).reshape(-1, 3), _f32(xyz1s[k]).reshape(-1, 3)
+            i0, i1 = (torch.as_tensor(np.asarray(i) if not torch.is_tensor(i) else i).to(x0.device).long().reshape(-1) for i in (idx0s[k], idx1s[k]))
+            src, tgt = x0[i0].contiguous(), x1[i1].contiguous()
+            if int(src.shape[0]) > MAX_TAIL:
+                raise ValueError(f"pair {k}: {int(src.shape[0])} correspondences, lr_dgr_refine takes at most {MAX_TAIL}")
+            x0s.append(x0); x1s.append(x1); srcs.append(src); tgts.append(tgt)
+            ws.append(torch.as_tensor(weights[k]).to(device=x0.device, dtype=torch.float32).reshape(-1))
+        out = []
+        for at in range(0, P, MAX_REFINE_BATCH):
+            end = min(P, at + MAX_REFINE_BATCH)
+            out += refine_batch(srcs[at:end], tgts[at:end], weights=ws[at:end], ratio=1e-4, quantization_size=thr, clip=self.clip_weight_thresh,
+                                wsum_threshold=0.0)[0]
+        res, self.last = [], []
+        for k, (T, info) in enumerate(out):
+            m = int(srcs[k].shape[0]) if m_thresholds is None or m_thresholds[k] is None else int(m_thresholds[k])
+            refused = 0 if inlier_statuses is None else int(inlier_statuses[k])
+            info["path"] = "refinement"
+            status = self.status_of(info, m)
+            if refused:
+                info["inlier_status"] = refused
+            if refused or status in (1, 2):
+                if status in (1, 2):
+                    info.update(status=status, iterations=0, break_count=0, loss=0.0)
+                T, r = ransac_dev(srcs[k], tgts[k], 80000, sample_size=4, use_elc=True, thr=thr, seed=self.seed, confidence=0.9999)
+                if r["best_h"] < 0:
+                    T = np.eye(4)
+                info["path"], info["ransac"] = "safeguard", r
+            self.last.append(info)
+            one = {"base": T, "w_icp": T}
+            if self.use_icp:
+                one["w_icp"], _ = icp_dev(x0s[k], x1s[k], T, max_dist=thr)
+            res.append(one)
+        return res
+
 
 # ---- the 6-D inlier network -----------------------------------------------------------------------------------------------------------
 N_STAGES = resunet.N_STAGES
 NK = 729                                              # 3^6 offsets
 MAX_N = 131072                                        # rows per lr_dgr_inlier
+MAX_PAIRS = 8                                         # pairs per lr_dgr_inlier_batch (three tag bits), MAX_N rows together
 MAX_TAIL = 32768                                      # rows per lr_dgr_refine
 WIDTHS = (32, 64, 128, 256, 128, 64, 64, 64)          # ResUNetBN2C: C1 C2 C3 C4 (down), T4 T3 T2 T1 (up)
 _WIDTH_KEYS = ("conv1", "conv2", "conv3", "conv4", "conv4_tr", "conv3_tr", "conv2_tr", "conv1_tr")
@@ -276,6 +342,110 @@ class InlierNet:
             raise _ext.LidarRegError(f"lr_dgr_inlier: status {self.last_info['status']} (2: duplicate correspondence cell, 3: an axis wider than the extent limit)")
         return w
 
+    def _call_batch(self, coords, poison=None):
+        """One lr_dgr_inlier_batch over device tensors coords[k] [n_k,6] int32 (at most MAX_PAIRS pairs and MAX_N rows together) ->
+        (outs [n_k], the result blocks as one uint8 tensor)."""
+        L = _ext.lib()
+        dev = self.device
+        P = len(coords)
+        ns = [int(c.shape[0]) for c in coords]
+        outs = [torch.zeros(max(n, 1), dtype=torch.float32, device=dev) for n in ns]
+        res = torch.zeros(P * ctypes.sizeof(_ext.DgrInlierResult), dtype=torch.uint8, device=dev)
+        scratch = devmem.scratch(L.lr_dgr_inlier_batch_scratch_bytes(P, sum(ns), ctypes.byref(self._w8)), dev, poison)
+        arr = lambda ts: (ctypes.c_void_p * P)(*[ptr(t, n) for t, n in zip(ts, ns)])
+        params = _ext.DgrInlierParams(tap=0, widths=self.widths)
+        with torch.cuda.device(dev):
+            _ext.check(L.lr_dgr_inlier_batch(P, arr(coords), (ctypes.c_int32 * P)(*ns), self.weights_blob.data_ptr(), self.weights_blob.numel() * 4,
+                                             ctypes.byref(params), res.data_ptr(), arr(outs), scratch.data_ptr(), scratch.numel(),
+                                             torch.cuda.current_stream().cuda_stream))
+        return [o[:n] for o, n in zip(outs, ns)], res
+
+    def logits_batch(self, coords6_list, poison=None):
+        """`logits` for many pairs through lr_dgr_inlier_batch (contract n4): coords6_list[k] [n_k,6] -> a list of [n_k] device tensors in
+        the caller's order, each holding the bytes `logits` gives for that pair alone.  self.last_info: one dict per pair; the status is
+        per pair.  A longer list is split, in order, into calls of at most MAX_PAIRS pairs and MAX_N rows; a pair that alone exceeds MAX_N
+        rows is a ValueError naming its index."""
+        dev = self.device
+        coords = [torch.as_tensor(c).to(device=dev, dtype=torch.int32).contiguous().reshape(-1, 6) for c in coords6_list]
+        for k, c in enumerate(coords):
+            if int(c.shape[0]) > MAX_N:
+                raise ValueError(f"coords6_list[{k}] has {int(c.shape[0])} rows: lr_dgr_inlier_batch takes at most {MAX_N}")
+        outs, blocks = [], []
+        at = 0
+        while at < len(coords):
+            end, rows = at + 1, int(coords[at].shape[0])
+            while end < len(coords) and end - at < MAX_PAIRS and rows + int(coords[end].shape[0]) <= MAX_N:
+                rows += int(coords[end].shape[0]); end += 1
+            o, res = self._call_batch(coords[at:end], poison)
+            outs += o; blocks.append(res)
+            at = end
+        self.last_info = []
+        for res in blocks:
+            host = res.cpu()
+            for k in range(host.numel() // ctypes.sizeof(_ext.DgrInlierResult)):
+                r = devmem.read_struct(host, _ext.DgrInlierResult, k)
+                self.last_info.append(dict(status=r.status, n=r.n, n_tap=r.n_tap))
+        return outs
+
+    def weights_batch(self, xyz0s, xyz1s, idx0s, idx1s, voxel_size=0.3):
+        """`weights` for many pairs: ([sigmoid of the logits, [M_k] float32 device tensor], [the network's status per pair]).  It does not
+        raise on a refused pair (status 2 / 3: its logits are 0): DGRTail.register_batch sends such a pair to the safeguard."""
+        logits = self.logits_batch([self.coords6(*a, voxel_size) for a in zip(xyz0s, xyz1s, idx0s, idx1s)])
+        return [torch.sigmoid(l) for l in logits], [i["status"] for i in self.last_info]
+
+
+def correspondences_dev(xyz0, xyz1, F0, F1, args, ws, stream):
+    """fcgf_feature_matching (deep_global_registration.py:206-218): every source point with its nearest target descriptor, through
+    lr_nn_top2; no filter, no subsampling.  Returns (idx0, idx1 device int32, count device int32 [1]); nothing is synchronised."""
+    n0, n1, d = F0.shape[0], F1.shape[0], F0.shape[1]
+    dev = F0.device
+    idx0 = torch.arange(n0, dtype=torch.int32, device=dev)
+    idx1 = torch.empty(n0, dtype=torch.int32, device=dev)
+    _ext.check(_ext.lib().lr_nn_top2(ws.handle, F0.data_ptr(), n0, F1.data_ptr(), n1, d, idx1.data_ptr(), None, None, None, stream))
+    return idx0, idx1, torch.full((1,), n0, dtype=torch.int32, device=dev)
+
+
+def eval_pairs(source, indices, args, device=None, batch=32, nstreams=3, verbose=False):
+    """--algo DGR over `indices` of `source` (corrset.eval_pairs).  Per window one solve(srcs, tgts): the 6-D cells (floor in fp64 of the
+    gathered points / voxel), InlierNet.weights_batch, DGRTail.register_batch without ICP -- the engine's own ICP follows.  Returns a
+    harness.EvalRun.  Column 9 = the pair's share of its window's solve (device time between two events, split evenly), as for --algo SM.
+    A pair above the refinement's MAX_TAIL rows keeps the rows the clip leaves, as DGR.register does."""
+    from . import FR as fr
+    path = getattr(args, "dgr_weights", None)
+    if not path:
+        raise ValueError("--algo DGR needs --dgr_weights FILE (the reference's DGR checkpoint: state_dict_inlier)")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    net = InlierNet.from_checkpoint(path, dev)
+    tail = DGRTail(fr.VOXEL_SIZE, float(getattr(args, "dgr_clip_weight_thresh", 0.05)), use_icp=False, seed=int(getattr(args, "seed", 51)))
+    return corrset.eval_pairs(source, indices, args, correspondences_dev, lambda srcs, tgts: solve_window(net, tail, srcs, tgts), device=device,
+                              batch=min(int(batch), MAX_REFINE_BATCH), nstreams=nstreams, verbose=verbose)
+
+
+def drop_clipped(w, clip, *rows):
+    """DGR.register's path for a set above MAX_TAIL rows: the rows the clip kills never reach the tail (the same live rows in the same
+    order, so the same bits) -> (w, *rows) of the kept ones."""
+    keep = (w > 0) & (w >= clip)
+    return (w[keep],) + tuple(r[keep] for r in rows)
+
+
+def solve_window(net, tail, srcs, tgts):
+    """One window of --algo DGR on gathered correspondences src[i] <-> tgt[i]: ([(T 4x4, info)], device ms)."""
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    ar = [torch.arange(int(s.shape[0]), device=net.device) for s in srcs]
+    ws, statuses = net.weights_batch(srcs, tgts, ar, ar, tail.voxel_size)
+    ms = [int(s.shape[0]) for s in srcs]
+    srcs, tgts = list(srcs), list(tgts)
+    for k, m in enumerate(ms):
+        if m > MAX_TAIL:
+            ws[k], srcs[k], tgts[k] = drop_clipped(ws[k], tail.clip_weight_thresh, srcs[k], tgts[k])
+            if int(srcs[k].shape[0]) > MAX_TAIL:
+                raise ValueError(f"{int(srcs[k].shape[0])} of {m} correspondences survive the clip: lr_dgr_refine takes at most {MAX_TAIL}")
+    ar = [torch.arange(int(s.shape[0]), device=net.device) for s in srcs]
+    res = tail.register_batch(srcs, tgts, ar, ar, ws, m_thresholds=ms, inlier_statuses=statuses)
+    ev1.record(); ev1.synchronize()
+    return [(r["base"], info) for r, info in zip(res, tail.last)], ev0.elapsed_time(ev1)
+
 
 class DGR:
     """DeepGlobalRegistration (deep_global_registration.py:352-459) with safeguard_method 'correspondence': fcgf an fcgf.FCGF, inlier an
@@ -320,4 +490,39 @@ class DGR:
             self.last.update(m_tail=int(idx0.shape[0]), idx0_tail=idx0, idx1_tail=idx1, weights_tail=w, xyz0=x0, xyz1=x1)
             res = self.tail.register(x0, x1, idx0, idx1, weights=w, m_threshold=m)
             self.last["tail"] = self.tail.last
+            return res
+
+    def register_batch(self, pairs):
+        """`register` for a list of (xyz0, xyz1): -> [{'base', 'w_icp'}], each the bytes `register` gives for that pair; self.last a list.
+        The voxel de-duplication per cloud, FCGF.features_batch over all 2 P clouds, the feature nearest neighbour per pair,
+        InlierNet.weights_batch, per pair the drop of the clipped rows of a set above MAX_TAIL, then DGRTail.register_batch.  A pair the
+        inlier network refuses takes the safeguard (its info carries inlier_status) where `register` raises."""
+        from .matching import nn_top2_dev
+        with torch.cuda.device(self.inlier.device):
+            pre = [(self.preprocess(a), self.preprocess(b)) for a, b in pairs]
+            feats = self.fcgf.features_batch([c[2] for p in pre for c in p])
+            for b, info in enumerate(self.fcgf.last_info):
+                if info["status"] != 0:
+                    raise _ext.LidarRegError(f"lr_fcgf_extract_batch: cloud {b % 2} of pair {b // 2}: status {info['status']}")
+            idx0s, idx1s = [], []
+            for k in range(len(pairs)):
+                idx1 = nn_top2_dev(feats[2 * k], feats[2 * k + 1], want_2nd=False)[0].long()
+                if int(idx1.shape[0]) > MAX_N:
+                    raise ValueError(f"pair {k}: {int(idx1.shape[0])} correspondences: lr_dgr_inlier takes at most {MAX_N}")
+                idx0s.append(torch.arange(idx1.shape[0], device=idx1.device)); idx1s.append(idx1)
+            k0s, k1s = [p[0][0] for p in pre], [p[1][0] for p in pre]
+            x0s, x1s = [p[0][1] for p in pre], [p[1][1] for p in pre]
+            ws, statuses = self.inlier.weights_batch(k0s, k1s, idx0s, idx1s, self.voxel_size)
+            ms = [int(i.shape[0]) for i in idx0s]
+            self.last = [dict(m=m, weights=w, idx0=i0, idx1=i1, inlier_status=s) for m, w, i0, i1, s in zip(ms, ws, idx0s, idx1s, statuses)]
+            t0, t1, tw = list(idx0s), list(idx1s), list(ws)
+            for k, m in enumerate(ms):
+                if m > MAX_TAIL:
+                    tw[k], t0[k], t1[k] = drop_clipped(ws[k], self.clip_weight_thresh, idx0s[k], idx1s[k])
+                    if int(t0[k].shape[0]) > MAX_TAIL:
+                        raise ValueError(f"pair {k}: {int(t0[k].shape[0])} of {m} correspondences survive the clip: lr_dgr_refine takes at most {MAX_TAIL}")
+                self.last[k].update(m_tail=int(t0[k].shape[0]), idx0_tail=t0[k], idx1_tail=t1[k], weights_tail=tw[k], xyz0=x0s[k], xyz1=x1s[k])
+            res = self.tail.register_batch(x0s, x1s, t0, t1, tw, m_thresholds=ms, inlier_statuses=statuses)
+            for k, info in enumerate(self.tail.last):
+                self.last[k]["tail"] = info
             return res

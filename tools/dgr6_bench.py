@@ -89,15 +89,75 @@ def timed(fn, reps):
     return dict(median_ms=float(np.median(ms)), min_ms=float(min(ms)), max_ms=float(max(ms)))
 
 
+def make_batch_call(net, rows_list):
+    """One lr_dgr_inlier_batch over the pairs, on buffers made once."""
+    L = _ext.lib()
+    P = len(rows_list)
+    ns = [int(r.shape[0]) for r in rows_list]
+    dev = rows_list[0].device
+    w8 = (ctypes.c_int32 * 8)(*net.widths)
+    sc = devmem.scratch(L.lr_dgr_inlier_batch_scratch_bytes(P, sum(ns), ctypes.byref(w8)), dev)
+    res = torch.zeros(16 * P, dtype=torch.uint8, device=dev)
+    outs = [torch.zeros(n, dtype=torch.float32, device=dev) for n in ns]
+    p = _ext.DgrInlierParams(tap=0, widths=net.widths)
+    st = torch.cuda.current_stream().cuda_stream
+    blob = net.weights_blob
+    vp = lambda ts: (ctypes.c_void_p * P)(*[t.data_ptr() for t in ts])
+    coords, logit, n_arr = vp(rows_list), vp(outs), (ctypes.c_int32 * P)(*ns)
+
+    def call():
+        _ext.check(L.lr_dgr_inlier_batch(P, coords, n_arr, blob.data_ptr(), blob.numel() * 4, ctypes.byref(p), res.data_ptr(), logit, sc.data_ptr(), sc.numel(), st))
+    call()
+    block = res.cpu().numpy().view(np.int32).reshape(P, 4)
+    assert not block[:, 0].any() and block[:, 1].tolist() == ns, block.tolist()
+    return call
+
+
+def correspondences(reg, feat, net, n0, seed):
+    raw0, raw1, _ = synth.make_scan_pair(n0=n0, seed=seed)
+    k0, _, c0 = reg.preprocess(raw0)
+    k1, _, c1 = reg.preprocess(raw1)
+    idx1 = nn_top2_dev(feat.features(c0), feat.features(c1), want_2nd=False)[0].long()
+    return net.coords6(k0, k1, torch.arange(idx1.shape[0], device=idx1.device), idx1, 0.3)
+
+
+def bench_batch(reg, feat, net, reps):
+    """The rows of the one-pair table as batches: 8 distinct pairs of about 4 000 correspondences and 4 of about 30 000 (different
+    synth.make_scan_pair seeds).  (a) lr_dgr_inlier once per pair back to back on one stream, (b) ONE lr_dgr_inlier_batch; the same
+    process, the same method (`timed`)."""
+    out = []
+    for pairs, n0 in ((8, 4400), (4, 40000)):
+        rows = [correspondences(reg, feat, net, n0, 3 + s) for s in range(pairs)]
+        singles = [make_call(net, r, 0) for r in rows]
+        one = timed(lambda: [c() for c in singles], reps)
+        batch = timed(make_batch_call(net, rows), reps)
+        spread = one["max_ms"] - one["min_ms"]
+        out.append(dict(pairs=pairs, correspondences=[int(r.shape[0]) for r in rows], one_pair_calls=one, batch_call=batch,
+                        one_pair_ms_per_pair=one["median_ms"] / pairs, batch_ms_per_pair=batch["median_ms"] / pairs,
+                        ratio_one_pair_over_batch=one["median_ms"] / batch["median_ms"], one_pair_spread_ms=spread,
+                        batch_not_above_one_pair_by_more_than_its_spread=bool(batch["median_ms"] <= one["median_ms"] + spread)))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", default="4400,40000", help="raw returns per frame (about 4 000 and 30 000 correspondences)")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dgr6_bench.json"))
+    ap.add_argument("--batch", action="store_true", help="time lr_dgr_inlier_batch against the one-pair entry called per pair, and put the "
+                    "result under the key 'batch' of the line already in --out (the one-pair table there is kept)")
     a = ap.parse_args()
     feat = fcgf.FCGF.from_state_dict(fcgf_cases.make_state_dict(0, 5), 5)
     net = dgr.InlierNet.from_stages(dgr6_cpu.random_stages(dgr6_cpu.WIDTHS, seed=0))
     reg = dgr.DGR(feat, net, voxel_size=0.3)
+    if a.batch:
+        doc = json.loads(open(a.out).read()) if os.path.exists(a.out) else dict(tool="dgr6_bench")
+        doc["batch"] = dict(device=torch.cuda.get_device_name(0), widths=list(net.widths), reps=a.reps, shapes=bench_batch(reg, feat, net, a.reps))
+        line = json.dumps(doc)
+        print(json.dumps(doc["batch"]))
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+        return
     out_rows = []
     for n0 in (int(v) for v in a.points.split(",")):
         raw0, raw1, _ = synth.make_scan_pair(n0=n0, seed=3)
