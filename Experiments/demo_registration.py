@@ -1,9 +1,12 @@
 """BASELINE config #1: one synthetic 5k-point pair through the whole path (plumbing demo).
 
     python demo_registration.py --algo RANSAC --mode MMN --iters 1000
+    python demo_registration.py --descriptor fpfh --n 120000 --iters 50000
 
 The reference's demo_registration.py is a PointDSC viewer without RANSAC flags (Experiments/demo_registration.py:61-67);
 this one exercises FR() with the reference's flag names and prints the recovered motion next to the ground truth.
+--descriptor fpfh (the reference's --descriptor fpfh, :37-44,93-95) needs no descriptors and no weights: it registers two raw synthetic
+scan frames of --n points from the points alone -- fpfh.extract on both (voxel --voxel_size), fpfh.match, RANSAC on the pairs.
 """
 import argparse
 import os
@@ -25,17 +28,40 @@ def main(argv=None):
     p.add_argument("--fast_rejection", default="ELC")
     p.add_argument("--GPF_factor", type=float, default=2.0)
     p.add_argument("--GPF_grid_wid", type=int, default=10)
+    p.add_argument("--descriptor", default="synthetic", choices=["synthetic", "fpfh"])
+    p.add_argument("--voxel_size", type=float, default=0.3)
     args = p.parse_args(argv)
     import torch
     from lidarregistration_amd import metrics, synth
+    np.set_printoptions(precision=4, suppress=True)
+    if args.descriptor == "fpfh":
+        return fpfh_demo(args, metrics, synth)
     from algorithms.FR import FR
     pr = synth.make_pair(N=args.n, rho=0.5, s=0.9, seed=args.seed)
     t = torch.from_numpy
     T, elapsed, _, _, n_init, ir_init, n_filt, ir_filt = FR(t(pr["xyz0"]), t(pr["xyz1"]), t(pr["feats0"]), t(pr["feats1"]), args, pr["T_gt"])
-    np.set_printoptions(precision=4, suppress=True)
     print(f"{n_init} nn pairs ({ir_init:.3f} inliers), {n_filt} filtered pairs ({ir_filt:.3f} inliers), {elapsed*1e3:.2f} ms")
     print("estimated motion:\n", T, "\nground truth:\n", pr["T_gt"])
     print(f"RE = {metrics.rotation_error_deg(T, pr['T_gt']):.4f} deg, TE = {metrics.translation_error_cm(T, pr['T_gt']):.3f} cm")
+    return T
+
+
+def fpfh_demo(args, metrics, synth):
+    from time import time
+    from lidarregistration_amd import fpfh
+    from lidarregistration_amd.ransac import ransac_dev
+    A, B, T_gt = synth.make_scan_pair(args.n, seed=args.seed)
+    t0 = time()
+    p0, F0 = fpfh.extract(A, args.voxel_size)
+    p1, F1 = fpfh.extract(B, args.voxel_size)
+    corr = fpfh.match(F0, F1, mutual=True)
+    src, tgt = p0[corr[:, 0].to(p0.device)].float(), p1[corr[:, 1].to(p1.device)].float()
+    T, info = ransac_dev(src, tgt, args.iters, sample_size=3, use_elc=True, thr=2.0 * args.voxel_size, seed=args.seed)
+    elapsed = time() - t0
+    print(f"{p0.shape[0]} x {p1.shape[0]} points after down-sampling, {len(corr)} mutual FPFH pairs, "
+          f"{info['best_count']} inliers of the best model, {elapsed*1e3:.2f} ms")
+    print("estimated motion:\n", T, "\nground truth:\n", T_gt)
+    print(f"RE = {metrics.rotation_error_deg(T, T_gt):.4f} deg, TE = {metrics.translation_error_cm(T, T_gt):.3f} cm")
     return T
 
 

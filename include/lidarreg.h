@@ -148,7 +148,7 @@ typedef struct lr_pair_params {
 LR_API int         lr_version(void);    /* 100 * major + minor; 103: lr_workspace_clock, LR_OPT_CLOCK_PROBE, lr_debug_fake_current_device, device checks; 102: params structs start with struct_size (72 / 112 bytes), descriptors of 1..32 dimensions; 101: lr_ransac_params 64 bytes / lr_pair_params 96 bytes (round 3), lr_icp_batch */
 LR_API const char *lr_last_error(void);
 
-/* Scratch for clouds up to (max_n0, max_n1) points x dim (1 <= dim <= 32; matching.py:22-65 takes any width) and up to max_iters hypotheses. */
+/* Scratch for clouds up to (max_n0, max_n1) points x dim (1 <= dim <= 32; matching.py:22-65 takes any width: 33..128 go to lr_nn_wide, which takes no workspace) and up to max_iters hypotheses. */
 LR_API int    lr_workspace_create(lr_workspace **ws, int max_n0, int max_n1, int dim, int max_iters);
 /* The same for up to max_pairs (<= 64) pairs registered by ONE call of lr_register_batch: max_pairs arenas of identical
  * layout in one allocation.  The single-pair entry points below work on such a workspace too (they use arena 0).        */
@@ -1053,6 +1053,55 @@ LR_API int lr_dgr_refine(const float *src, const float *tgt, int m, const int32_
 LR_API int lr_dgr_refine_batch(int npairs, const float *const *src, const float *const *tgt, const int32_t *m, const int32_t *const *m_dev,
                                const float *const *weights, const double *const *T_init, const lr_dgr_params *p, lr_dgr_result *results,
                                void *scratch, size_t scratch_bytes, void *stream);
+
+/* ---- a1/a2 for descriptors of 33..128 numbers (FPFH's 33, matching.py:22-65 takes any width) -------
+ * The same contract as lr_nn_top2, at the wider dim, bit for bit oracle/oracle.c's orc_nn_top2: norm and dot are fmaf chains over
+ * k = 0..dim-1 from +0, d2 = fmaf(-2, dot, n0[i] + n1[j]), s = sqrtf(fmaxf(d2, 1e-30f)); ascending (s, j), the first minimal value wins
+ * for the first and for the second neighbour; with n1 = 1 the second is -1 / inf (n1 = 0: the first too).  fmaxf drops a NaN, so a
+ * non-finite row never puts a NaN into a comparison (its distances are 1e-15 or inf, as the oracle's).  A stand-alone entry point: it
+ * takes no workspace, and the f16 filter path behind lr_nn_top2 stays 32 wide.  Exact f32 on v_mfma_f32_32x32x2_f32, no n0 x n1 matrix.
+ * idx2 / s1 / s2 may be NULL.  Caller-owned device scratch, 256-byte aligned (lr_nn_wide_scratch_bytes: 0 when n0 or n1 is outside
+ * 0..4194304 or dim outside 33..128); its content on entry does not matter.  Refusals: LR_EINVAL before any launch and before anything
+ * is written, lr_last_error naming the argument -- dim 1..32 ("use lr_nn_top2"), dim > 128, n0 / n1 out of range, a null array, and the
+ * scratch front end's.  No host synchronisation, no allocation: graph-capturable.                                                    */
+LR_API size_t lr_nn_wide_scratch_bytes(int n0, int n1, int dim);
+LR_API int lr_nn_wide(const float *F0, int n0, const float *F1, int n1, int dim, int32_t *idx1, int32_t *idx2, float *s1, float *s2,
+                      void *scratch, size_t scratch_bytes, void *stream);
+
+/* ---- FPFH descriptors (Experiments/demo_registration.py:37-44, datasets/KITTI.py:85-93, misc/cal_fpfh.py:22-26 -> Open3D 0.13
+ * compute_fpfh_feature, not vendored: PARITY UNPINNED, the algorithm is upstream-recalled) -------------------------------------------
+ * xyz, normals: device float64 [n,3]; out_f64 / out_f32: device [n,33], either may be NULL (not both); info: device int32 [4].
+ * The contract -- fp64, every operation a single IEEE operation in the written order, no libm call beyond sqrt; tests/fpfh_cpu.py
+ * restates it and the device equals it bit for bit; out_f32 is the cast of out_f64:
+ *   F1 lists    per point its at most max_nn finite points of least (d2, index) with d2 <= fl(radius radius), in that order,
+ *               d2 = ((qx-px)^2 + (qy-py)^2) + (qz-pz)^2 (lr_normals' rule); the point itself is among them.  Entry 0 is skipped (literally,
+ *               as Open3D does -- with exact duplicates it may be the duplicate); k = len - 1; len <= 1: the row is all zeros.  A
+ *               non-finite point has no list, is in no list and gets a zero row
+ *   F2 pair     of (p1, n1), (p2, n2): d = p2 - p1, L = sqrt((dx dx + dy dy) + dz dz), a1 = ((n1x dx + n1y dy) + n1z dz) / L, a2 likewise
+ *               with n2; if |a1| < |a2|: the normals swap, d = -d, f3 = -a2, else f3 = a1 (Open3D's acos(|a1|) > acos(|a2|) on the
+ *               arguments); v = d x n1, |v| = sqrt(v.v), v = v / |v| per component; w = n1 x v; f2 = v.n2; y = w.n2, x = n1.n2 (dots and
+ *               cross products in the form (a0 b0 + a1 b1) + a2 b2 and a1 b2 - a2 b1, ...).  L == 0 or |v| == 0: bins 5, 5, 5 (the
+ *               features (0, 0, 0), still counted)
+ *   F3 bins     angle: floor(11 (atan2(y, x) + pi) / (2 pi)) clamped to 0..10, decided without the angle: with (x', y') = (-x, -y) and
+ *               the edge directions (c_e, s_e) = (cos, sin)(2 pi e / 11) as tabulated fp64 literals, e = 1..10: y < 0: #{ e <= 5 :
+ *               c_e y' - s_e x' >= 0 }; y > 0: 5 + #{ e >= 6 : the same }; y = +0, x < 0: 10; y = -0, x < 0: 0; otherwise 5.
+ *               f2, f3: #{ e in 1..10 : (11 (f + 1)) 0.5 >= e } (= the clamped floor)
+ *   F4 SPFH     integer counts per bin (the list's entries 1.., three bins each, at 0.., 11.., 22..) times (100 / k): one multiplication
+ *               (not Open3D's repeated +=: the order of the entries does not matter)
+ *   F5 FPFH     F[j] = sum over the entries 1.. in list order of spfh[entry][j] / d2(entry), a serial chain per (point, j) from +0;
+ *               entries with d2 == 0 are skipped; g = the sum of F over each 11-block in j order from +0;
+ *               out[j] = F[j] (g != 0 ? 100 / g : 0) + spfh[self][j]
+ *   F6 info     [0] 0 ok, 1 no finite point; [1] non-finite points; [2] zero rows (len <= 1, the non-finite ones included);
+ *               [3] lists that are full (len == max_nn)
+ * 2 <= max_nn <= 128, 0 <= n <= 4194304 (the grid's limit; all index arithmetic is size_t: n max_nn 4 passes 2^31), radius positive and
+ * finite.  Caller-owned device scratch, 256-byte aligned (lr_fpfh_scratch_bytes: 0 outside those ranges); its content on entry does not
+ * matter.  Refusals: LR_EINVAL before any launch, lr_last_error naming the argument.  Stages, each a kernel of its own: the 3-D grid of
+ * lr_nn3 at cell radius (1 + 2^-16), the lists (built once into scratch), SPFH, FPFH.  No host synchronisation, no allocation, no
+ * floating-point atomics: graph-capturable.  Not built: normals on the raw cloud averaged by the down-sampling (the demo's order), and
+ * several clouds per call.                                                                                                           */
+LR_API size_t lr_fpfh_scratch_bytes(int n, int max_nn);
+LR_API int lr_fpfh(const double *xyz, const double *normals, int n, double radius, int max_nn, double *out_f64, float *out_f32,
+                   int32_t *info, void *scratch, size_t scratch_bytes, void *stream);
 
 /* ---- measurement hook for bench.py: duration of the last NN distance kernel(s) on this workspace,
  * from HIP events recorded on the launch stream.  Enable, run, synchronise, then read.            */

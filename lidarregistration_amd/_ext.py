@@ -33,6 +33,7 @@ SYMBOLS = [
     "lr_dgr_scratch_bytes", "lr_dgr_refine", "lr_dgr_refine_batch",
     "lr_dgr_inlier_weights_bytes", "lr_dgr_inlier_scratch_bytes", "lr_dgr_inlier",
     "lr_dgr_inlier_batch_scratch_bytes", "lr_dgr_inlier_batch",
+    "lr_nn_wide_scratch_bytes", "lr_nn_wide", "lr_fpfh_scratch_bytes", "lr_fpfh",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -379,6 +380,10 @@ def lib():
         L.lr_dgr_inlier.argtypes = [vp, ci, vp, sz, ctypes.POINTER(DgrInlierParams), vp, vp, vp, vp, sz, vp]
         L.lr_dgr_inlier_batch_scratch_bytes.argtypes = [ci, ci, w8]
         L.lr_dgr_inlier_batch.argtypes = [ci, pp, ip, vp, sz, ctypes.POINTER(DgrInlierParams), vp, pp, vp, sz, vp]
+        L.lr_nn_wide_scratch_bytes.argtypes = [ci, ci, ci]
+        L.lr_nn_wide.argtypes = [vp, ci, vp, ci, ci, vp, vp, vp, vp, vp, sz, vp]
+        L.lr_fpfh_scratch_bytes.argtypes = [ci, ci]
+        L.lr_fpfh.argtypes = [vp, vp, ci, dp, ci, vp, vp, vp, vp, sz, vp]
         L.lr_workspace_timing_read.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
         _lib = L
     return _lib

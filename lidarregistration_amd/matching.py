@@ -11,9 +11,10 @@ from time import time
 import numpy as np
 import torch
 
-from . import _ext
+from . import _ext, devmem
 
 _WS = {}
+WIDE_MIN_DIM = 33      # descriptors this wide and wider (up to 128) go to lr_nn_wide, which takes a scratch and no workspace
 
 
 def _device():
@@ -70,6 +71,52 @@ def nn_top2_dev(F0, F1, want_2nd=True, want_dist=False):
     return idx1, idx2, s1, s2
 
 
+def nn_wide_into(F0, F1, idx1, idx2=None, s1=None, s2=None, poison=None):
+    """lr_nn_wide on device tensors: F0 [n0,d], F1 [n1,d] float32 with 33 <= d <= 128; the outputs are written in place."""
+    n0, n1, d = F0.shape[0], F1.shape[0], F0.shape[1]
+    if F1.shape[1] != d:
+        raise _ext.LidarRegError(f"lr_nn_wide: F0 is {d} wide, F1 {F1.shape[1]}")
+    if not (F0.is_cuda and F1.is_cuda and idx1.is_cuda):
+        raise _ext.LidarRegError("lr_nn_wide: nn_wide_into takes device tensors (nn_wide_dev moves its arguments)")
+    L = _ext.lib()
+    need = L.lr_nn_wide_scratch_bytes(n0, n1, d)
+    sc = devmem.scratch(need, F0.device, poison)
+    _ext.check(L.lr_nn_wide(devmem.ptr(F0, n0), n0, devmem.ptr(F1, n1), n1, d, devmem.ptr(idx1, n0), _ptr(idx2), _ptr(s1), _ptr(s2),
+                            sc.data_ptr(), need, _stream()))      # (sc goes back to the allocator of this same stream: stream-ordered)
+
+
+def nn_wide_dev(F0, F1, want_2nd=True, want_dist=False):
+    """nn_top2_dev's counterpart on lr_nn_wide (33 <= d <= 128; nn_top2_dev itself, the workspace path, keeps refusing those widths)."""
+    F0, F1 = _f32(F0), _f32(F1)
+    n0, dev = F0.shape[0], F0.device
+    idx1 = torch.empty(n0, dtype=torch.int32, device=dev)
+    idx2 = torch.empty(n0, dtype=torch.int32, device=dev) if want_2nd else None
+    s1 = torch.empty(n0, dtype=torch.float32, device=dev) if want_dist else None
+    s2 = torch.empty(n0, dtype=torch.float32, device=dev) if (want_dist and want_2nd) else None
+    nn_wide_into(F0, F1, idx1, idx2, s1, s2)
+    return idx1, idx2, s1, s2
+
+
+def _is_wide(F):
+    return torch.as_tensor(F).shape[1] >= WIDE_MIN_DIM
+
+
+def mutual_wide_dev(F0, F1, idx1, idx2=None):
+    """mutual_dev's counterpart for descriptors wider than 32 (mutual_dev itself, the workspace path, keeps refusing them):
+    nn_to_mutual's rule with the reverse NN as a second lr_nn_wide call with the operands swapped,
+    is_bb[i] = (rev[idx1[i]] == i), survivors in ascending i.  Index plumbing on the device; all arithmetic is in the kernel."""
+    F0, F1, idx1 = _f32(F0), _f32(F1), _i32(idx1)
+    idx2 = None if idx2 is None else _i32(idx2)
+    n0 = F0.shape[0]
+    rev = torch.empty(F1.shape[0], dtype=torch.int32, device=F0.device)
+    nn_wide_into(F1, F0, rev)
+    i0 = torch.arange(n0, dtype=torch.int32, device=F0.device)
+    j = idx1.long()
+    is_bb = (j >= 0) & (rev[j.clamp(min=0)] == i0) if F1.shape[0] else torch.zeros(n0, dtype=torch.bool, device=F0.device)
+    keep = torch.nonzero(is_bb).reshape(-1)
+    return is_bb.to(torch.uint8), i0[keep], idx1[keep], (idx2[keep] if idx2 is not None else None)
+
+
 def mutual_dev(F0, F1, idx1, idx2=None):
     """(is_bb uint8 [n0], out_idx0, out_idx1, out_idx2 or None) device tensors, survivors in ascending idx0."""
     F0, F1, idx1 = _f32(F0), _f32(F1), _i32(idx1)
@@ -91,8 +138,8 @@ def mutual_dev(F0, F1, idx1, idx2=None):
 # ----------------------------------------------------------------------------- reference-shaped API
 
 def find_nn(F0, F1, return_2nd=False):
-    """matching.py:22-65."""
-    idx1, idx2, _, _ = nn_top2_dev(F0, F1, want_2nd=return_2nd)
+    """matching.py:22-65 (any width up to 128: 1..32 through the workspace path, 33..128 through lr_nn_wide)."""
+    idx1, idx2, _, _ = (nn_wide_dev if _is_wide(F0) else nn_top2_dev)(F0, F1, want_2nd=return_2nd)
     corres_idx0 = torch.arange(idx1.shape[0]).long()
     corres_idx1 = idx1.long().cpu()
     if return_2nd:
@@ -109,7 +156,7 @@ def find_2nn(fcgf_feats0, fcgf_feats1):
 
 def nn_to_mutual(feats0, feats1, corres_idx0, corres_idx1, idx1_2nd=None, force_return_2nd=False):
     """matching.py:222-239 (relies, like the reference, on corres_idx0 == arange(N0))."""
-    _, o0, o1, o2 = mutual_dev(feats0, feats1, corres_idx1, idx1_2nd)
+    _, o0, o1, o2 = (mutual_wide_dev if _is_wide(feats0) else mutual_dev)(feats0, feats1, corres_idx1, idx1_2nd)
     final_corres_idx0, final_corres_idx1 = o0.long().cpu(), o1.long().cpu()
     if idx1_2nd is not None:
         return final_corres_idx0, final_corres_idx1, o2.long().cpu()
@@ -121,7 +168,7 @@ def nn_to_mutual(feats0, feats1, corres_idx0, corres_idx1, idx1_2nd=None, force_
 
 def mark_best_buddies(fcgf_feats0, fcgf_feats1, corres_idx0, corres_idx1):
     """matching.py:207-220."""
-    is_bb, _, _, _ = mutual_dev(fcgf_feats0, fcgf_feats1, corres_idx1)
+    is_bb, _, _, _ = (mutual_wide_dev if _is_wide(fcgf_feats0) else mutual_dev)(fcgf_feats0, fcgf_feats1, corres_idx1)
     is_bb = is_bb.bool().cpu().numpy()
     return is_bb, is_bb.sum()
 
