@@ -1,12 +1,13 @@
 """BASELINE config #1: one synthetic 5k-point pair through the whole path (plumbing demo).
 
     python demo_registration.py --algo RANSAC --mode MMN --iters 1000
-    python demo_registration.py --descriptor fpfh --n 120000 --iters 50000
+    python demo_registration.py --descriptor fpfh --mode GPF --n 120000 --iters 50000
 
 The reference's demo_registration.py is a PointDSC viewer without RANSAC flags (Experiments/demo_registration.py:61-67);
 this one exercises FR() with the reference's flag names and prints the recovered motion next to the ground truth.
 --descriptor fpfh (the reference's --descriptor fpfh, :37-44,93-95) needs no descriptors and no weights: it registers two raw synthetic
-scan frames of --n points from the points alone -- fpfh.extract on both (voxel --voxel_size), fpfh.match, RANSAC on the pairs.
+scan frames of --n points from the points alone -- fpfh.Extractor on both (voxel --voxel_size), then FR() on the 33-wide rows with
+--mode / --codebase as given (a wide workspace behind it).
 """
 import argparse
 import os
@@ -21,7 +22,7 @@ def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--algo", default="RANSAC", choices=["RANSAC"])
     p.add_argument("--codebase", default="GC", choices=["open3D", "GC"])
-    p.add_argument("--mode", default="MMN")
+    p.add_argument("--mode", default="MMN", choices=["MMN", "MNN", "GPF", "no_filter"])
     p.add_argument("--iters", type=int, default=1000)
     p.add_argument("--n", type=int, default=5000)
     p.add_argument("--seed", type=int, default=51)
@@ -48,18 +49,17 @@ def main(argv=None):
 
 def fpfh_demo(args, metrics, synth):
     from time import time
+    from algorithms.FR import FR
     from lidarregistration_amd import fpfh
-    from lidarregistration_amd.ransac import ransac_dev
     A, B, T_gt = synth.make_scan_pair(args.n, seed=args.seed)
     t0 = time()
-    p0, F0 = fpfh.extract(A, args.voxel_size)
-    p1, F1 = fpfh.extract(B, args.voxel_size)
-    corr = fpfh.match(F0, F1, mutual=True)
-    src, tgt = p0[corr[:, 0].to(p0.device)].float(), p1[corr[:, 1].to(p1.device)].float()
-    T, info = ransac_dev(src, tgt, args.iters, sample_size=3, use_elc=True, thr=2.0 * args.voxel_size, seed=args.seed)
-    elapsed = time() - t0
-    print(f"{p0.shape[0]} x {p1.shape[0]} points after down-sampling, {len(corr)} mutual FPFH pairs, "
-          f"{info['best_count']} inliers of the best model, {elapsed*1e3:.2f} ms")
+    ex = fpfh.Extractor(args.voxel_size)
+    p0, F0, _ = ex.extract(A)
+    p1, F1, _ = ex.extract(B)
+    extract_s = time() - t0
+    T, elapsed, _, _, n_init, ir_init, n_filt, ir_filt = FR(p0, p1, F0, F1, args, T_gt)
+    print(f"{p0.shape[0]} x {p1.shape[0]} points after down-sampling (FPFH in {extract_s*1e3:.2f} ms), {n_init} nn pairs ({ir_init:.3f} inliers), "
+          f"{n_filt} filtered pairs ({ir_filt:.3f} inliers), {elapsed*1e3:.2f} ms")
     print("estimated motion:\n", T, "\nground truth:\n", T_gt)
     print(f"RE = {metrics.rotation_error_deg(T, T_gt):.4f} deg, TE = {metrics.translation_error_cm(T, T_gt):.3f} cm")
     return T

@@ -72,6 +72,7 @@ def get_args(argv=None):
     p.add_argument("--chosen_snapshot", type=str, default="", help="--algo PointDSC: directory with config.json and models/model_best.pkl (the reference's snapshot layout)")
     p.add_argument("--solver", type=str, default="SVD", choices=["SVD", "RANSAC"], help="--algo PointDSC: SVD; RANSAC is not built and is refused")
     p.add_argument("--fcgf_weights_file", type=str, default=None, help="FCGF checkpoint (torch.load(file)['state_dict'], ResUNetBN2C): compute the descriptors from the cloud cache's raw scans on the GPU instead of reading a feature cache")
+    p.add_argument("--descriptor", type=str, default="fcgf", choices=["fcgf", "fpfh"], help="fpfh: compute 33-number FPFH descriptors from the cloud cache's raw scans on the GPU (no trained weights needed); fcgf: the feature cache or --fcgf_weights_file")
     p.add_argument("--dgr_weights", type=str, default="", help="--algo DGR: the reference's DGR checkpoint; only state_dict_inlier and, where present, config are read")
     p.add_argument("--dgr_clip_weight_thresh", type=float, default=0.05, help="--algo DGR: clip_weight_thresh (DGR/config.py)")
     # additions of this implementation
@@ -95,6 +96,12 @@ def get_args(argv=None):
         p.error("--algo DGR needs --dgr_weights FILE (the reference's DGR checkpoint: state_dict_inlier)")
     if args.fcgf_weights_file and not (os.environ.get("LIDARREG_CLOUD_CACHE") and os.environ.get("LIDARREG_BALANCED_SETS") and args.dataset != "synthetic"):
         p.error("--fcgf_weights_file computes the descriptors from raw scans and needs a cloud cache: set LIDARREG_CLOUD_CACHE and LIDARREG_BALANCED_SETS and name a list --dataset (A, B, S, K, L)")
+    if args.descriptor == "fpfh" and args.fcgf_weights_file:
+        p.error("--descriptor fpfh excludes --fcgf_weights_file")
+    if args.descriptor == "fpfh" and not (os.environ.get("LIDARREG_CLOUD_CACHE") and os.environ.get("LIDARREG_BALANCED_SETS") and args.dataset != "synthetic"):
+        p.error("--descriptor fpfh computes the descriptors from raw scans and needs a cloud cache: set LIDARREG_CLOUD_CACHE and LIDARREG_BALANCED_SETS and name a list --dataset (A, B, S, K, L)")
+    if args.descriptor == "fpfh" and args.algo in ("DGR", "PointDSC") :
+        p.error("--descriptor fpfh serves --algo RANSAC and the back ends that take correspondences; --algo %s runs a network over FCGF's 32 numbers" % args.algo)
     args.start_time, args.tmp_file_base, args.world_size, args.rank, args.do_analysis = start_time, tmp_file_base, world_size, rank, do_analysis
     from lidarregistration_amd import io_lists
     args.dataset_name = io_lists.DATASET_NAMES.get(args.dataset, args.dataset)
@@ -110,6 +117,9 @@ def make_source(args):
     if args.dataset in io_lists.DATASET_NAMES and sets:
         lst = io_lists.read_pair_list(os.path.join(sets, args.dataset_name, args.phase + ".txt"))
         clouds = os.environ.get("LIDARREG_CLOUD_CACHE")
+        if clouds and args.descriptor == "fpfh":
+            from lidarregistration_amd import fpfh
+            return harness.RefCloudSource(lst, os.path.join(clouds, args.dataset_name), None, extractor=fpfh.Extractor())
         if clouds and args.fcgf_weights_file:
             from lidarregistration_amd import fcgf
             return harness.RefCloudSource(lst, os.path.join(clouds, args.dataset_name), None, extractor=fcgf.FCGF.from_checkpoint(args.fcgf_weights_file))

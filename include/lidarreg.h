@@ -148,12 +148,26 @@ typedef struct lr_pair_params {
 LR_API int         lr_version(void);    /* 100 * major + minor; 103: lr_workspace_clock, LR_OPT_CLOCK_PROBE, lr_debug_fake_current_device, device checks; 102: params structs start with struct_size (72 / 112 bytes), descriptors of 1..32 dimensions; 101: lr_ransac_params 64 bytes / lr_pair_params 96 bytes (round 3), lr_icp_batch */
 LR_API const char *lr_last_error(void);
 
-/* Scratch for clouds up to (max_n0, max_n1) points x dim (1 <= dim <= 32; matching.py:22-65 takes any width: 33..128 go to lr_nn_wide, which takes no workspace) and up to max_iters hypotheses. */
+/* Scratch for clouds up to (max_n0, max_n1) points x dim (1 <= dim <= 32; matching.py:22-65 takes any width: 33..128 go to lr_workspace_create_wide, or to lr_nn_wide, which takes no workspace) and up to max_iters hypotheses. */
 LR_API int    lr_workspace_create(lr_workspace **ws, int max_n0, int max_n1, int dim, int max_iters);
 /* The same for up to max_pairs (<= 64) pairs registered by ONE call of lr_register_batch: max_pairs arenas of identical
  * layout in one allocation.  The single-pair entry points below work on such a workspace too (they use arena 0).        */
 LR_API int    lr_workspace_create_batch(lr_workspace **ws, int max_pairs, int max_n0, int max_n1, int dim, int max_iters);
+/* The same for descriptors of 33..128 numbers (FPFH's 33): a WIDE workspace.  Its NN stage is the exact f32 matrix-core kernel of
+ * lr_nn_wide with the pair as a grid dimension, both directions and the norms once per call (no f16 filter pass: none of its operand
+ * copies is allocated, lr_workspace_bytes says what is).  A wide workspace is a workspace: lr_nn_top2 (idx2 = NULL: the top-1 form),
+ * lr_nn_to_mutual, lr_gpf, lr_gpf_bb_first, lr_register_pair / _batch in every mode with either sampler and refit 0, 1 or 2,
+ * lr_icp_batch, the *_lists* / *_mask_at accessors, the timing events, LR_OPT_NN_SECOND_AUTO and lr_workspace_poison work on it with
+ * dim == its dim, and give what the oracle gives at that width.  Refused on it with LR_EINVAL, by name and before any launch:
+ * refit == 3, and a pair with n1 < 2 in a call that reads the second neighbour (lr_gpf*, mode GPF, the PROSAC sampler).
+ * Limits of max_pairs / max_n0 / max_n1 / max_iters as lr_workspace_create_batch; refusals are LR_EINVAL / LR_ESIZE before any HIP
+ * call, lr_last_error naming the argument; dim 1..32: "use lr_workspace_create".                                                   */
+LR_API int    lr_workspace_create_wide(lr_workspace **ws, int max_pairs, int max_n0, int max_n1, int dim, int max_iters);
 LR_API int    lr_workspace_destroy(lr_workspace *ws);
+/* Test hook (no reference counterpart): copies the reverse-NN list of pair `pair` out of the arena, as the last call with a reverse
+ * direction (lr_nn_to_mutual, lr_gpf*, lr_register_pair / _batch in mode MNN or GPF) left it: rev[j] = the nearest cloud-0 row of
+ * cloud-1 row j, -1 where no query points at j (j < n1 <= max_n1; device memory).                                                  */
+LR_API int    lr_debug_workspace_rev(lr_workspace *ws, int pair, int n1, int32_t *rev, void *stream);
 LR_API size_t lr_workspace_bytes(const lr_workspace *ws);
 /* Test hook (no reference counterpart): fill the scratch arena with one byte value; results must not depend on it. */
 LR_API int    lr_workspace_poison(lr_workspace *ws, int byte, void *stream);

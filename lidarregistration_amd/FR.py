@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _ext
-from .matching import _device, _f32, _stream, measure_inlier_ratio, workspace
+from .matching import _device, _f32, _stream, measure_inlier_ratio, workspace, workspace_for  # noqa: F401 (workspace: the tools' FR.workspace)
 from .ransac import DEFAULT_SEED, PRECHECK
 
 VOXEL_SIZE = 0.3            # FR.py:18
@@ -105,7 +105,7 @@ def register_pair_dev(xyz0, xyz1, feats0, feats1, params, out=None, ws=None, str
     """Enqueue one pair; returns the device result buffer (uint8[496]).  No synchronisation."""
     n0, n1, d = feats0.shape[0], feats1.shape[0], feats0.shape[1]
     if ws is None:
-        ws = workspace(n0, n1, params.ransac.iters, d)
+        ws = workspace_for(n0, n1, params.ransac.iters, d)
     if out is None:
         out = torch.empty(ctypes.sizeof(_ext.PairResult), dtype=torch.uint8, device=feats0.device)
     _ext.check(_ext.lib().lr_register_pair(ws.handle, xyz0.data_ptr(), xyz1.data_ptr(), feats0.data_ptr(), feats1.data_ptr(),
@@ -122,7 +122,7 @@ def register_batch_dev(pairs, params, out=None, ws=None, stream=None):
     d = pairs[0][2].shape[1]
     n0 = [int(p[2].shape[0]) for p in pairs]; n1 = [int(p[3].shape[0]) for p in pairs]
     if ws is None:
-        ws = _ext.Workspace(max(n0), max(n1), d, params.ransac.iters, max_pairs=P)
+        ws = _ext.Workspace.for_dim(max(n0), max(n1), d, params.ransac.iters, max_pairs=P)
     if out is None:
         out = torch.empty((P, ctypes.sizeof(_ext.PairResult)), dtype=torch.uint8, device=pairs[0][2].device)
     VP, IP = ctypes.c_void_p * P, ctypes.c_int32 * P
@@ -147,11 +147,11 @@ def pair_lists(ws, n0, n_corr, dev):
     return nn1.cpu().numpy(), c0[:n_corr].cpu().numpy(), c1[:n_corr].cpu().numpy()
 
 
-_SHARE = {}          # (n0, n1 rounded up to 1024, device index) -> the second neighbour's share of the forward NN time
+_SHARE = {}          # (n0, n1 rounded up to 1024, device index, wide kernel or not) -> the second neighbour's share of the forward NN time
 
 
-def share_key(n0, n1, device):
-    return ((int(n0) + 1023) // 1024, (int(n1) + 1023) // 1024, torch.device(device).index)
+def share_key(n0, n1, device, dim=32):
+    return ((int(n0) + 1023) // 1024, (int(n1) + 1023) // 1024, torch.device(device).index, int(dim) > 32)
 last_timing = {}     # of the last FR() call: whole_path_s, forward_nn_s, second_nn_share, reference_style_s (= the returned elapsed_time)
 
 
@@ -160,7 +160,7 @@ def second_nn_share(f0, f1, ws, reps=3):
     (FR.py:117).  Here the forward NN runs once per call; its second-neighbour share is measured once per cloud-size class with the
     same two calls (device events) and applied to the forward-NN time of each call."""
     n0, n1 = int(f0.shape[0]), int(f1.shape[0])
-    key = share_key(n0, n1, f0.device)
+    key = share_key(n0, n1, f0.device, f0.shape[1])
     if key not in _SHARE:
         i1 = torch.empty(n0, dtype=torch.int32, device=f0.device); i2 = torch.empty_like(i1)
         st = torch.cuda.current_stream(f0.device)
@@ -192,7 +192,7 @@ def FR(A, B, A_feat, B_feat, args, T_gt):
     params = pair_params(args)
     params.icp = 0                     # FR() returns the registration only (FR.py:119); ICP is the harness' stage (test.py:183-189)
     n0, n1 = f0.shape[0], f1.shape[0]
-    ws = workspace(n0, n1, params.ransac.iters, f0.shape[1])
+    ws = workspace_for(n0, n1, params.ransac.iters, f0.shape[1])
 
     share = second_nn_share(f0, f1, ws)
     ws.timing(True)

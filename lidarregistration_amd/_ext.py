@@ -33,7 +33,7 @@ SYMBOLS = [
     "lr_dgr_scratch_bytes", "lr_dgr_refine", "lr_dgr_refine_batch",
     "lr_dgr_inlier_weights_bytes", "lr_dgr_inlier_scratch_bytes", "lr_dgr_inlier",
     "lr_dgr_inlier_batch_scratch_bytes", "lr_dgr_inlier_batch",
-    "lr_nn_wide_scratch_bytes", "lr_nn_wide", "lr_fpfh_scratch_bytes", "lr_fpfh",
+    "lr_nn_wide_scratch_bytes", "lr_nn_wide", "lr_fpfh_scratch_bytes", "lr_fpfh", "lr_workspace_create_wide", "lr_debug_workspace_rev",
 ]
 
 # lr_workspace_option ids (include/lidarreg.h).  DEFAULT_OPTIONS is applied to every Workspace this module creates (a hook for
@@ -319,6 +319,8 @@ def lib():
         L.lr_voxel_dedup_scratch_bytes.argtypes = [ci]
         L.lr_voxel_dedup.argtypes = [vp, ci, vp, vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_workspace_create_batch.argtypes = [ctypes.POINTER(ctypes.c_void_p), ci, ci, ci, ci, ci]
+        L.lr_workspace_create_wide.argtypes = [ctypes.POINTER(ctypes.c_void_p), ci, ci, ci, ci, ci]
+        L.lr_debug_workspace_rev.argtypes = [vp, ci, ci, vp, vp]
         pp, ip = ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int32)
         L.lr_register_batch.argtypes = [vp, ci, pp, pp, pp, pp, ip, ip, ci, ctypes.POINTER(PairParams), vp, vp]
         L.lr_workspace_option.argtypes = [vp, ci, ci]
@@ -398,13 +400,25 @@ class Workspace:
     """Owns one lr_workspace: device scratch for one in-flight pair, or -- max_pairs > 1 -- for one in-flight batch of pairs
     registered by a single lr_register_batch call."""
 
-    def __init__(self, max_n0, max_n1, dim=32, max_iters=50000, max_pairs=1):
+    def __init__(self, max_n0, max_n1, dim=32, max_iters=50000, max_pairs=1, _wide=False):
         self._h = ctypes.c_void_p()
         self.max_n0, self.max_n1, self.dim, self.max_iters = int(max_n0), int(max_n1), int(dim), int(max_iters)
         self.max_pairs = int(max_pairs)
-        check(lib().lr_workspace_create_batch(ctypes.byref(self._h), self.max_pairs, self.max_n0, self.max_n1, self.dim, self.max_iters))
+        self.is_wide = bool(_wide)
+        create = lib().lr_workspace_create_wide if self.is_wide else lib().lr_workspace_create_batch
+        check(create(ctypes.byref(self._h), self.max_pairs, self.max_n0, self.max_n1, self.dim, self.max_iters))
         for name, value in DEFAULT_OPTIONS.items():
             self.set_option(name, value)
+
+    @classmethod
+    def wide(cls, max_n0, max_n1, dim, max_iters=50000, max_pairs=1):
+        """A wide workspace (lr_workspace_create_wide): descriptors of 33..128 numbers.  Workspace(dim=33) itself keeps refusing."""
+        return cls(max_n0, max_n1, dim, max_iters, max_pairs, _wide=True)
+
+    @classmethod
+    def for_dim(cls, max_n0, max_n1, dim, max_iters=50000, max_pairs=1):
+        """The workspace kind that serves descriptors `dim` wide: narrow up to 32, wide from 33."""
+        return cls(max_n0, max_n1, dim, max_iters, max_pairs, _wide=int(dim) > 32)
 
     def set_option(self, name, value):
         """Tuning option of this workspace (OPTIONS; none changes a result)."""
@@ -432,7 +446,7 @@ class Workspace:
         return self._h
 
     def fits(self, n0, n1, dim, iters):
-        return n0 <= self.max_n0 and n1 <= self.max_n1 and dim == self.dim and iters <= self.max_iters
+        return n0 <= self.max_n0 and n1 <= self.max_n1 and dim == self.dim and iters <= self.max_iters and (dim > 32) == self.is_wide
 
     @property
     def nbytes(self):

@@ -123,6 +123,14 @@ void carve(lr_workspace *ws, Carver &c)
 {
     const size_t n0 = ws->max_n0, n1 = ws->max_n1, n = ws->max_n, it = ws->max_iters;
     ws->nrm0 = c.take<float>(n0); ws->nrm1 = c.take<float>(n1);
+    if (ws->wide) {
+        // (a wide workspace: the exact f32 NN of lr_nnw_ws.hip -- partials, the reverse direction's flags and row list; none of the f16
+        // operand copies, padded copies, thresholds or candidate stores of the narrow path below)
+        ws->nnw_part_cap = lr_nnw_part_entries((int)n);
+        ws->nnw_parts = reinterpret_cast<nnw_part *>(c.take<char>(ws->nnw_part_cap * 16));
+        ws->nnw_flag = c.take<uint8_t>(n1); ws->nnw_list = c.take<int32_t>(n1); ws->nnw_blk = c.take<int32_t>(n1 / 256 + 2);
+        ws->counters = c.take<int32_t>(LR_CNT_TOTAL);
+    } else {
     ws->H0 = c.take<_Float16>(n0 * 32); ws->H1 = c.take<_Float16>(n1 * 32);
     if (ws->dim != LR_FEAT_DIM) { ws->P0 = c.take<float>(n0 * 32); ws->P1 = c.take<float>(n1 * 32); }
     ws->tau = c.take<float>(n);
@@ -138,6 +146,7 @@ void carve(lr_workspace *ws, Carver &c)
     ws->rev_cols = c.take<int32_t>(n0); ws->rev_s1 = c.take<float>(n0); ws->rev_pos = c.take<int32_t>(n0);
     ws->rev_tmin = c.take<float>(n0 / 32 + 2); ws->rev_hist = c.take<int32_t>(2 * 4096);
     ws->Hs = c.take<_Float16>(n0 * 32); ws->nrms = c.take<float>(n0);
+    }
     ws->nn_idx1 = c.take<int32_t>(n0); ws->nn_idx2 = c.take<int32_t>(n0);
     ws->nn_s1 = c.take<float>(n0); ws->nn_s2 = c.take<float>(n0);
     ws->rev_idx1 = c.take<int32_t>(n1);
@@ -175,6 +184,8 @@ void carve(lr_workspace *ws, Carver &c)
 }
 }  // namespace
 
+static int workspace_build(lr_workspace **out, int max_pairs, int max_n0, int max_n1, int dim, int max_iters, int wide);
+
 extern "C" int lr_workspace_create(lr_workspace **out, int max_n0, int max_n1, int dim, int max_iters)
 {
     return lr_workspace_create_batch(out, 1, max_n0, max_n1, dim, max_iters);
@@ -187,6 +198,27 @@ extern "C" int lr_workspace_create_batch(lr_workspace **out, int max_pairs, int 
     LR_REQUIRE(max_n0 > 0 && max_n1 > 0 && max_iters >= 0, LR_EINVAL, "lr_workspace_create: sizes must be positive");
     LR_REQUIRE(dim >= 1 && dim <= LR_FEAT_DIM, LR_EINVAL, "lr_workspace_create: descriptors of 1 to 32 dimensions are supported");
     LR_REQUIRE(max_n0 < (1 << 22) && max_n1 < (1 << 22), LR_ESIZE, "lr_workspace_create: clouds are limited to 2^22 points");
+    return workspace_build(out, max_pairs, max_n0, max_n1, dim, max_iters, 0);
+}
+
+// Descriptors of 33..128 numbers (FPFH's 33): the same workspace with the exact f32 NN of lr_nnw_ws.hip as its NN stage.  Every check
+// comes before the first HIP call.
+extern "C" int lr_workspace_create_wide(lr_workspace **out, int max_pairs, int max_n0, int max_n1, int dim, int max_iters)
+{
+    LR_REQUIRE(out, LR_EINVAL, "lr_workspace_create_wide: null output (ws)");
+    LR_REQUIRE(max_pairs >= 1 && max_pairs <= LR_MAX_BATCH, LR_EINVAL, "lr_workspace_create_wide: max_pairs must be in [1, 64]");
+    LR_REQUIRE(max_n0 > 0, LR_EINVAL, "lr_workspace_create_wide: max_n0 must be positive");
+    LR_REQUIRE(max_n1 > 0, LR_EINVAL, "lr_workspace_create_wide: max_n1 must be positive");
+    LR_REQUIRE(max_iters >= 0, LR_EINVAL, "lr_workspace_create_wide: max_iters must be >= 0");
+    LR_REQUIRE(dim < 1 || dim > LR_FEAT_DIM, LR_EINVAL, "lr_workspace_create_wide: dim must lie in 33..128: for 1..32 use lr_workspace_create");
+    LR_REQUIRE(dim >= 33 && dim <= 128, LR_EINVAL, "lr_workspace_create_wide: dim must lie in 33..128");
+    LR_REQUIRE(max_n0 < (1 << 22), LR_ESIZE, "lr_workspace_create_wide: max_n0: clouds are limited to 2^22 points");
+    LR_REQUIRE(max_n1 < (1 << 22), LR_ESIZE, "lr_workspace_create_wide: max_n1: clouds are limited to 2^22 points");
+    return workspace_build(out, max_pairs, max_n0, max_n1, dim, max_iters, 1);
+}
+
+static int workspace_build(lr_workspace **out, int max_pairs, int max_n0, int max_n1, int dim, int max_iters, int wide)
+{
     int dev = -1;
     LR_HIP(hipGetDevice(&dev));
     const lr_device_info *di = nullptr;
@@ -200,7 +232,7 @@ extern "C" int lr_workspace_create_batch(lr_workspace **out, int max_pairs, int 
     memset(ws, 0, sizeof(*ws));
     ws->device = dev; ws->n_cus = di->cus;
     ws->max_n0 = max_n0; ws->max_n1 = max_n1; ws->max_n = max_n0 > max_n1 ? max_n0 : max_n1;
-    ws->dim = dim; ws->max_iters = max_iters > 0 ? max_iters : 1;
+    ws->dim = dim; ws->max_iters = max_iters > 0 ? max_iters : 1; ws->wide = wide;
     ws->max_pairs = max_pairs;
     // tuning defaults (lr_workspace_option changes them; no environment variable is read anywhere in this library)
     ws->nn_blocks_target = 3 * ws->n_cus;      // 3 blocks per CU = every block of a single pair's filter pass resident at once (768 on an MI355X)
@@ -224,7 +256,8 @@ extern "C" int lr_workspace_create_batch(lr_workspace **out, int max_pairs, int 
     ws->descs = reinterpret_cast<lr_pair_desc *>(ws->base + desc_off);
     ws->clk_dev = reinterpret_cast<unsigned long long *>(ws->base + clk_off);
     // (optional: without it every call launches both forms of the filter pass, as batched calls always do)
-    if (hipHostMalloc(reinterpret_cast<void **>(&ws->form_host), 2 * sizeof(int32_t), hipHostMallocMapped) == hipSuccess) {
+    if (wide) ws->form_host = ws->form_dev = nullptr;      // (the form hint belongs to the narrow filter pass)
+    else if (hipHostMalloc(reinterpret_cast<void **>(&ws->form_host), 2 * sizeof(int32_t), hipHostMallocMapped) == hipSuccess) {
         ws->form_host[0] = ws->form_host[1] = 0;
         if (hipHostGetDevicePointer(reinterpret_cast<void **>(&ws->form_dev), ws->form_host, 0) != hipSuccess) { (void)hipHostFree(ws->form_host); ws->form_host = ws->form_dev = nullptr; }
     } else { (void)hipGetLastError(); ws->form_host = ws->form_dev = nullptr; }
@@ -304,6 +337,20 @@ extern "C" int lr_workspace_lists_at(lr_workspace *ws, int pair, int n0, int32_t
     if (nn_idx2) LR_HIP(hipMemcpyAsync(nn_idx2, at(ws->nn_idx2), nb, hipMemcpyDeviceToDevice, st));
     if (corr_idx0) LR_HIP(hipMemcpyAsync(corr_idx0, at(ws->corr_idx0), nb, hipMemcpyDeviceToDevice, st));
     if (corr_idx1) LR_HIP(hipMemcpyAsync(corr_idx1, at(ws->corr_idx1), nb, hipMemcpyDeviceToDevice, st));
+    return LR_OK;
+}
+
+// Test hook (no reference counterpart): the reverse-NN list of pair `pair` as the last call that ran a reverse direction left it in the
+// arena -- rev[j] = nearest cloud-0 row of cloud-1 row j, or -1 where no query points at j.  The pipeline itself reads it only through
+// lr_mutual_run; the copy-out lets a test hold the -1 rule on the untargeted rows.
+extern "C" int lr_debug_workspace_rev(lr_workspace *ws, int pair, int n1, int32_t *rev, void *stream)
+{
+    LR_CHECK_DEVICE(ws, stream, "lr_debug_workspace_rev");
+    LR_REQUIRE(rev, LR_EINVAL, "lr_debug_workspace_rev: null output");
+    LR_REQUIRE(pair >= 0 && pair < ws->max_pairs, LR_EINVAL, "lr_debug_workspace_rev: pair outside the workspace");
+    LR_REQUIRE(n1 > 0 && n1 <= ws->max_n1, LR_ESIZE, "lr_debug_workspace_rev: n1 exceeds the workspace");
+    LR_HIP(hipMemcpyAsync(rev, reinterpret_cast<const char *>(ws->rev_idx1) + (size_t)pair * ws->stride, sizeof(int32_t) * (size_t)n1,
+                          hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return LR_OK;
 }
 
@@ -498,9 +545,20 @@ static int operator_prep(lr_workspace *ws, const float *&F0, int n0, const float
     forget_last_batch(ws);
     LR_REQUIRE(required, LR_EINVAL, required_msg);
     *call = lr_call_single(ws, stream);
+    if (ws->wide) return lr_nnw_prep(*call, F0, n0, F1, n1, dim);
     pad_if_narrow(*call, F0, n0, F1, n1, dim);
     return lr_nn16_prep(*call, F0, n0, F1, n1);
 }
+
+// the reverse NN of the workspace's kind
+static int reverse_nn(const lr_call &c, const float *F0, int n0, const float *F1, int n1, int dim, const int32_t *fwd_idx1, int32_t *rev, bool seeded = false)
+{
+    if (c.ws->wide) return lr_nnw_reverse(c, F0, n0, F1, n1, dim, fwd_idx1, rev);
+    return lr_nn16_reverse(c, F0, n0, F1, n1, fwd_idx1, rev, seeded);
+}
+// A wide workspace has no rule for a missing second neighbour (idx2 = -1 at n1 = 1 would index F1 out of bounds in the ratio): refused
+#define LR_WIDE_NEEDS_SECOND(ws, n1, who) LR_REQUIRE(!((ws) && (ws)->wide && (n1) < 2), LR_EINVAL, who ": n1 < 2 on a wide workspace: this call reads the second neighbour")
+
 
 // ------------------------------------------------------------------ a1/a2
 extern "C" int lr_nn_top2(lr_workspace *ws, const float *F0, int n0, const float *F1, int n1, int dim,
@@ -508,6 +566,7 @@ extern "C" int lr_nn_top2(lr_workspace *ws, const float *F0, int n0, const float
 {
     lr_call c;
     LR_TRY(operator_prep(ws, F0, n0, F1, n1, dim, stream, "lr_nn_top2", idx1, "lr_nn_top2: idx1 is required", &c));
+    if (ws->wide) return lr_nnw_run(c, F0, n0, F1, n1, dim, idx1, idx2, s1, s2);
     return lr_nn16_run(c, F0, n0, F1, n1, idx1, idx2, s1, s2);
 }
 
@@ -520,7 +579,7 @@ extern "C" int lr_nn_to_mutual(lr_workspace *ws, const float *F0, int n0, const 
 {
     lr_call c;
     LR_TRY(operator_prep(ws, F0, n0, F1, n1, dim, stream, "lr_nn_to_mutual", idx1, "lr_nn_to_mutual: idx1 is required", &c));
-    LR_TRY(lr_nn16_reverse(c, F0, n0, F1, n1, idx1, ws->rev_idx1));
+    LR_TRY(reverse_nn(c, F0, n0, F1, n1, dim, idx1, ws->rev_idx1));
     return lr_mutual_run(c, n0, idx1, idx2, ws->rev_idx1, is_bb, o0, o1, o2, n_out);
 }
 
@@ -530,8 +589,9 @@ extern "C" int lr_gpf(lr_workspace *ws, const float *F0, int n0, const float *F1
                       int32_t *o0, int32_t *o1, int32_t *o2, float *oscore, int32_t *n_out, void *stream)
 {
     lr_call c;
+    LR_WIDE_NEEDS_SECOND(ws, n1, "lr_gpf");
     LR_TRY(operator_prep(ws, F0, n0, F1, n1, dim, stream, "lr_gpf", idx1 && idx2 && xyz0 && o0 && o1, "lr_gpf: null pointer", &c));
-    LR_TRY(lr_nn16_reverse(c, F0, n0, F1, n1, idx1, ws->rev_idx1));
+    LR_TRY(reverse_nn(c, F0, n0, F1, n1, dim, idx1, ws->rev_idx1));
     LR_TRY(lr_mutual_run(c, n0, idx1, nullptr, ws->rev_idx1, ws->is_bb, nullptr, nullptr, nullptr, nullptr));
     return lr_gpf_run(c, F0, n0, F1, dim, idx1, idx2, ws->is_bb, xyz0, grid_wid, factor, o0, o1, o2, oscore, n_out);
 }
@@ -543,10 +603,11 @@ extern "C" int lr_gpf_bb_first(lr_workspace *ws, const float *F0, int n0, const 
                                void *stream)
 {
     lr_call c;
+    LR_WIDE_NEEDS_SECOND(ws, n1, "lr_gpf_bb_first");
     LR_TRY(operator_prep(ws, F0, n0, F1, n1, dim, stream, "lr_gpf_bb_first", idx1 && idx2 && xyz0 && o0 && o1 && o2 && n_out && has_score,
                          "lr_gpf_bb_first: null pointer", &c));
     int32_t *mb_dev = ws->counters + LR_CNT_NCORR;
-    LR_TRY(lr_nn16_reverse(c, F0, n0, F1, n1, idx1, ws->rev_idx1));
+    LR_TRY(reverse_nn(c, F0, n0, F1, n1, dim, idx1, ws->rev_idx1));
     LR_TRY(lr_mutual_run(c, n0, idx1, idx2, ws->rev_idx1, ws->is_bb, ws->corr_idx0, ws->corr_idx1, ws->corr_idx2, mb_dev));
     const lr_gpf_subset sub = { mb_dev, ws->corr_idx0, has_score, max_matches };
     return lr_gpf_run(c, F0, n0, F1, dim, ws->corr_idx1, ws->corr_idx2, nullptr, xyz0, grid_wid, 0.0, o0, o1, o2, oscore, n_out, nullptr, nullptr, &sub);
@@ -684,9 +745,11 @@ static int register_stages(const lr_call &c, const float *xyz0, const float *xyz
     lr_workspace *ws = c.ws;
     int32_t *m_dev = ws->counters + LR_CNT_NCORR;
     int32_t *n_refit = ws->counters + LR_CNT_NREFIT;
-    pad_if_narrow(c, F0, n0, F1, n1, dim);
+    const bool wide = ws->wide != 0;
+    if (!wide) pad_if_narrow(c, F0, n0, F1, n1, dim);
     // 1. coarse correspondences (FR.py:38): first + second NN of every cloud-0 descriptor
-    LR_TRY(lr_nn16_prep(c, F0, n0, F1, n1, true));         // (the prep kernel clears the counter block itself)
+    if (wide) LR_TRY(lr_nnw_prep(c, F0, n0, F1, n1, dim, true));
+    else LR_TRY(lr_nn16_prep(c, F0, n0, F1, n1, true));         // (the prep kernel clears the counter block itself)
     const bool fuse_seed = p->mode != LR_MODE_NO_FILTER;   // the forward exact kernel seeds the reverse pass
     LR_TRY_HIP(lr_timer_mark(c, LR_EV_CALL_BEGIN));
     // The second neighbour (find_2nn, FR.py:38) feeds the feature-distance ratio only: GPF (matching.py:116) and the PROSAC
@@ -695,14 +758,15 @@ static int register_stages(const lr_call &c, const float *xyz0, const float *xyz
     // candidate lists of the forward pass are half as long (and the reverse pass prunes less: not a gain on its own).
     const bool want2 = !(ws->nn_second_auto && p->mode != LR_MODE_GPF && p->ransac.sampler == 0);
     int32_t *idx2 = want2 ? ws->nn_idx2 : nullptr;
-    LR_TRY(lr_nn16_run(c, F0, n0, F1, n1, ws->nn_idx1, idx2, ws->nn_s1, ws->nn_s2, fuse_seed));
+    if (wide) LR_TRY(lr_nnw_run(c, F0, n0, F1, n1, dim, ws->nn_idx1, idx2, ws->nn_s1, ws->nn_s2));
+    else LR_TRY(lr_nn16_run(c, F0, n0, F1, n1, ws->nn_idx1, idx2, ws->nn_s1, ws->nn_s2, fuse_seed));
     LR_TRY_HIP(lr_timer_mark(c, LR_EV_FWD_NN_DONE));
     // 2. filter (FR.py:48-56)
     if (p->mode == LR_MODE_NO_FILTER) {
         LR_TRY(lr_identity_corr(c, n0, ws->nn_idx1, idx2, ws->corr_idx0, ws->corr_idx1, idx2 ? ws->corr_idx2 : nullptr, m_dev));
     } else {
         // seeded by the forward pairs: only columns some query points at are resolved (others get -1)
-        LR_TRY(lr_nn16_reverse(c, F0, n0, F1, n1, ws->nn_idx1, ws->rev_idx1, fuse_seed));
+        LR_TRY(reverse_nn(c, F0, n0, F1, n1, dim, ws->nn_idx1, ws->rev_idx1, fuse_seed));
         LR_TRY_HIP(lr_timer_mark(c, LR_EV_REV_NN_DONE));
         if (p->mode == LR_MODE_MNN) {
             LR_TRY(lr_mutual_run(c, n0, ws->nn_idx1, idx2, ws->rev_idx1, ws->is_bb, ws->corr_idx0, ws->corr_idx1,
@@ -746,6 +810,19 @@ static int register_stages(const lr_call &c, const float *xyz0, const float *xyz
     return LR_OK;
 }
 
+// What a wide workspace refuses of a pair-pipeline call, by name and before any launch: the weighted refit of the DGR caller (32 floats
+// per row, lr_refit.hip) and a cloud 1 without a second neighbour when GPF or the PROSAC quality would read it
+static int check_wide_call(const lr_workspace *ws, const lr_pair_params *p, int n1, const char *who)
+{
+    if (!ws->wide) return LR_OK;
+    if (p->refit == 3) { lr_set_error("%s: refit == 3 (the weighted refit over 32-wide descriptors) is not available on a wide workspace", who); return LR_EINVAL; }
+    if (n1 < 2 && (p->mode == LR_MODE_GPF || p->ransac.sampler == 1)) {
+        lr_set_error("%s: n1 < 2 on a wide workspace: GPF and the PROSAC sampler read the second neighbour", who);
+        return LR_EINVAL;
+    }
+    return LR_OK;
+}
+
 extern "C" int lr_register_pair(lr_workspace *ws, const float *xyz0, const float *xyz1, const float *F0, const float *F1,
                                 int n0, int n1, int dim, const lr_pair_params *p, lr_pair_result *out, void *stream)
 {
@@ -755,6 +832,7 @@ extern "C" int lr_register_pair(lr_workspace *ws, const float *xyz0, const float
     LR_CHECK_DEVICE(ws, stream, "lr_register_pair");
     LR_REQUIRE(p->mode == LR_MODE_NO_FILTER || p->mode == LR_MODE_MNN || p->mode == LR_MODE_GPF, LR_EINVAL,
                "lr_register_pair: unknown mode");
+    LR_TRY(check_wide_call(ws, p, n1, "lr_register_pair"));
     ws->last_npairs = 1; ws->last_batch = 0;
     return register_stages(lr_call_single(ws, stream), xyz0, xyz1, F0, F1, n0, n1, dim, p, out);
 }
@@ -781,6 +859,7 @@ extern "C" int lr_register_batch(lr_workspace *ws, int npairs, const float *cons
     for (int k = 0; k < npairs; ++k) {
         LR_REQUIRE(xyz0[k] && xyz1[k], LR_EINVAL, "lr_register_batch: null pointer");
         LR_TRY(check_nn_args(ws, F0[k], n0[k], F1[k], n1[k], dim, "lr_register_batch"));
+        LR_TRY(check_wide_call(ws, p, n1[k], "lr_register_batch"));
         t.d[k] = lr_pair_desc{ xyz0[k], xyz1[k], F0[k], F1[k], n0[k], n1[k] };
         mx0 = n0[k] > mx0 ? n0[k] : mx0; mx1 = n1[k] > mx1 ? n1[k] : mx1;
     }

@@ -208,6 +208,13 @@ struct lr_workspace {
     float *icp_pts;              // [max_n1][4] target points in bucket order: x y z index-bits
     double *icp_state, *icp_part;
     lr_stage_timer timer;
+    // --- wide workspace (lr_workspace_create_wide, dim 33..128): the NN stage is lr_nnw_ws.hip's and none of the narrow NN scratch above exists ---
+    int wide;
+    struct nnw_part *nnw_parts;  // [strips][rows] per-strip top-2 of the NN kernel in flight, either direction (nnw_part_cap entries)
+    size_t nnw_part_cap;
+    uint8_t *nnw_flag;           // [max_n1] 1: some query points at this cloud-1 row
+    int32_t *nnw_list;           // [max_n1] those rows in ascending order (live length: counters[LR_CNT_NREV])
+    int32_t *nnw_blk;            // [max_n1/256+2] per-256-row counts of the list's compaction
 };
 
 // ---- call context ----------------------------------------------------------------------------------------------------
@@ -283,6 +290,12 @@ int lr_nn16_prep(const lr_call &c, const float *F0, int n0, const float *F1, int
 int lr_nn16_run(const lr_call &c, const float *F0, int n0, const float *F1, int n1,
                 int32_t *idx1, int32_t *idx2, float *s1, float *s2, bool seed_reverse = false);
 int lr_nn16_reverse(const lr_call &c, const float *F0, int n0, const float *F1, int n1, const int32_t *fwd_idx1, int32_t *rev, bool seeded = false);
+
+// lr_nnw_ws.hip: the same three for a wide workspace (exact f32 on the matrix cores, no filter pass); entries of nnw_parts an arena needs
+int lr_nnw_prep(const lr_call &c, const float *F0, int n0, const float *F1, int n1, int dim, bool zero_counters = false);
+int lr_nnw_run(const lr_call &c, const float *F0, int n0, const float *F1, int n1, int dim, int32_t *idx1, int32_t *idx2, float *s1, float *s2);
+int lr_nnw_reverse(const lr_call &c, const float *F0, int n0, const float *F1, int n1, int dim, const int32_t *fwd_idx1, int32_t *rev);
+size_t lr_nnw_part_entries(int max_n);
 
 // lr_filter.hip
 int lr_mutual_run(const lr_call &c, int n0, const int32_t *idx1, const int32_t *idx2, const int32_t *rev,

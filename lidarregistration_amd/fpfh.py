@@ -53,6 +53,24 @@ def extract(raw_xyz, voxel_size):
     return pts, F
 
 
+class Extractor:
+    """extract() behind the interface harness.RefCloudSource(extractor=...) takes (the CLI's --descriptor fpfh): the raw scan
+    down-sampled, its 33-number rows normalised as datasets/KITTI.py:52-53 does before matching.  One cloud per call."""
+
+    def __init__(self, voxel_size=0.3):
+        self.voxel_size = float(voxel_size)
+
+    def extract(self, raw, voxel_size=None):
+        """(xyz [n,3] float32, feats [n,33] float32, info) -- device tensors -- of one raw scan [N,3]."""
+        v = self.voxel_size if voxel_size is None else float(voxel_size)
+        pts, F = extract(raw, v)
+        return pts.to(torch.float32), normalise(F).contiguous(), dict(n=int(pts.shape[0]), voxel_size=v)
+
+    def extract_batch(self, raws, voxel_size=None):
+        """extract() of every scan in turn (lr_fpfh takes one cloud per call)."""
+        return [self.extract(raw, voxel_size) for raw in raws]
+
+
 def normalise(F):
     """datasets/KITTI.py:52-53: every row divided by (its L2 norm + 1e-6), float32 in and out (torch tensor, on the device it is on)."""
     F = torch.as_tensor(F).to(torch.float32)

@@ -358,7 +358,7 @@ def slot_workspace(wss, i, n0, n1, dim, iters, headroom=1.0, max_pairs=1, sync=N
         if sync is not None:
             torch.cuda.synchronize(sync)
         wss[i].close()
-    wss[i] = _ext.Workspace(int(n0 * headroom), int(n1 * headroom), dim, iters, max_pairs=max_pairs)
+    wss[i] = _ext.Workspace.for_dim(int(n0 * headroom), int(n1 * headroom), dim, iters, max_pairs=max_pairs)
     return True
 
 
@@ -432,7 +432,7 @@ def eval_pairs(source, indices, args, device=None, batch=32, in_flight=6, nstrea
                 if slot_workspace(wss, i, max(n0s), max(n1s), d, params.ransac.iters, headroom=1.25 if ragged else 1.0, max_pairs=batch):
                     seen[i] = None
                 k_big = int(np.argmax(n0s))
-                fresh = fr.share_key(n0s[k_big], n1s[k_big], dev) not in fr._SHARE
+                fresh = fr.share_key(n0s[k_big], n1s[k_big], dev, d) not in fr._SHARE
                 share = fr.second_nn_share(gp[k_big]["feats0"], gp[k_big]["feats1"], wss[i])      # (the GPU is idle here: calibrated once per size class)
                 if fresh or seen[i] is None:
                     torch.cuda.synchronize(dev)
@@ -594,7 +594,7 @@ def eval_pairs_serial(source, indices, args, device=None, in_flight=4, verbose=F
             x0, x1, f0, f1 = p["xyz0"], p["xyz1"], p["feats0"], p["feats1"]
             # the second neighbour's share of the forward NN for clouds of this size (measured once per size class with a few
             # timed NN calls on this workspace, which is idle here); the stage events are (re)armed afterwards
-            fresh = fr.share_key(n0, n1, dev) not in fr._SHARE
+            fresh = fr.share_key(n0, n1, dev, d) not in fr._SHARE
             if fresh:
                 torch.cuda.synchronize(dev)               # calibrate on an idle GPU
             share = fr.second_nn_share(f0, f1, wss[s])

@@ -14,7 +14,8 @@ import torch
 from . import _ext, devmem
 
 _WS = {}
-WIDE_MIN_DIM = 33      # descriptors this wide and wider (up to 128) go to lr_nn_wide, which takes a scratch and no workspace
+_WS_WIDE = {}
+WIDE_MIN_DIM = 33      # descriptors this wide and wider (up to 128) go to a wide workspace, or to lr_nn_wide, which takes a scratch and no workspace
 
 
 def _device():
@@ -27,19 +28,33 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-def workspace(n0, n1, iters=0, dim=32):
-    """Cached per-device workspace large enough for (n0, n1, iters)."""
+def _cached_workspace(cache, make, n0, n1, iters, dim):
     dev = torch.cuda.current_device()
-    ws = _WS.get(dev)
+    ws = cache.get(dev)
     if ws is None or not ws.handle or not ws.fits(n0, n1, dim, iters):
         grow = (ws.max_n0, ws.max_n1, ws.max_iters) if ws is not None else (0, 0, 0)
         if ws is not None:
-            _WS.pop(dev, None)
+            cache.pop(dev, None)
             torch.cuda.synchronize()
             ws.close()
-        ws = _ext.Workspace(max(n0, grow[0]), max(n1, grow[1]), dim, max(iters, grow[2], 1))
-        _WS[dev] = ws
+        ws = make(max(n0, grow[0]), max(n1, grow[1]), dim, max(iters, grow[2], 1))
+        cache[dev] = ws
     return ws
+
+
+def workspace(n0, n1, iters=0, dim=32):
+    """Cached per-device workspace large enough for (n0, n1, iters); descriptors of 1..32 numbers (wider ones are refused here)."""
+    return _cached_workspace(_WS, _ext.Workspace, n0, n1, iters, dim)
+
+
+def workspace_wide(n0, n1, iters=0, dim=WIDE_MIN_DIM):
+    """The same for descriptors of 33..128 numbers: a cached wide workspace, kept next to the narrow one."""
+    return _cached_workspace(_WS_WIDE, _ext.Workspace.wide, n0, n1, iters, dim)
+
+
+def workspace_for(n0, n1, iters, dim):
+    """The cached workspace of the kind that serves descriptors `dim` wide."""
+    return (workspace_wide if dim >= WIDE_MIN_DIM else workspace)(n0, n1, iters, dim)
 
 
 def _f32(t):
@@ -189,7 +204,7 @@ def Grid_Prioritized_Filter(fcgf_feats0, fcgf_feats1, corres_idx0, corres_idx1, 
     i1, i2 = _i32(corres_idx1), _i32(idx1_2nd)
     xyz = _f32(xyz0)
     n0, n1, d = F0.shape[0], F1.shape[0], F0.shape[1]
-    ws = workspace(n0, n1, dim=d)
+    ws = workspace_for(n0, n1, 0, d)
     dev = F0.device
     o0 = torch.empty(n0, dtype=torch.int32, device=dev); o1 = torch.empty_like(o0); o2 = torch.empty_like(o0)
     sc = torch.empty(n0, dtype=torch.float32, device=dev)

@@ -78,7 +78,7 @@ def TEASER(A_pcd, B_pcd, A_feats, B_feats, A_tensor, args):
     dev = torch.device("cuda", torch.cuda.current_device())
     xyz0, xyz1 = _f32(pts(A_pcd)), _f32(pts(B_pcd))
     F0, F1 = _f32(A_feats), _f32(B_feats)
-    ws = _ext.Workspace(F0.shape[0], F1.shape[0], F0.shape[1], 1)
+    ws = _ext.Workspace.for_dim(F0.shape[0], F1.shape[0], F0.shape[1], 1)
     try:
         o0, o1, cnt = correspondences_dev(xyz0, xyz1, F0, F1, args, ws, _stream())
         m = int(cnt[0].item())
