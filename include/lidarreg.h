@@ -631,6 +631,71 @@ LR_API size_t lr_normals_scratch_bytes(int n);
  * neighbours, 0 }.  radius positive and finite, max_nn in 1..32.                                                                  */
 LR_API int lr_normals(const double *xyz, int n, double radius, int max_nn, double *normals_out, int32_t *info, void *scratch,
                       size_t scratch_bytes, void *stream);
+/* lr_normals and, where n_nb_out (device int32 [n], nullable) is given, the number of neighbours every point took: 0 .. max_nn, the point
+ * itself included, 0 for a non-finite point.  A default (0, 0, 1) cannot be told from a true one without it.  Same kernels, normals, info
+ * and scratch (lr_normals_scratch_bytes) as lr_normals.                                                                            */
+LR_API int lr_normals2(const double *xyz, int n, double radius, int max_nn, double *normals_out, int32_t *n_nb_out, int32_t *info,
+                       void *scratch, size_t scratch_bytes, void *stream);
+
+/* ---- f9: symmetric ICP on the exact nearest neighbour (f8 is the balanced-set selection below) -----------------------------------------
+ * lr_symicp is the third refinement of FCGF_FAST/net/refinement_tester.py:75-93.  The reference shells out to trimesh2's mesh_align
+ * (net/symmetric_icp.py:47-82), a binary outside its tree: [upstream-recalled, parity unpinned].  The contract is the algorithm of the
+ * paper behind that binary (Rusinkiewicz, A Symmetric Objective Function for ICP, 2019), restated in tests/symicp_cpu.py; DESIGN.md §23.
+ * All arithmetic is fp64, no fused multiply-add, only + - x / sqrt; products, M.v and u.v associate as in f7; the cross product is
+ * (u x v)_x = u_y v_z - u_z v_y, cyclically.  A is fixed, B moves.  (W, t) starts at the identity, or at the upper 3 x 4 of T_init.
+ * For iteration k = 0 .. n_iter - 1:
+ *  Y1 B'_j = (W.B_j) + t, nB'_j = W.nB_j.
+ *  Y2 f = N(A, B'), r = N(B', A) by contract N of lr_nn3.  Forward candidates (i, f_i) for every i with f_i >= 0; backward candidates
+ *     (r_j, j) for every j with r_j >= 0 and f[r_j] != j (a mutual pair counts once).
+ *  Y3 a candidate (i, j), p = B'_j, q = A_i, d = p - q, dot = nA_i.nB'_j, is accepted iff p, q, nA_i, nB'_j are finite,
+ *     d.d <= fl(max_dist max_dist) and |dot| >= min_cos.  s = -1 if dot < 0, else +1; n = nA_i + s nB'_j; row c = [(p + q) x n ; n],
+ *     b = -(d.n).
+ *  Y4 28 sums and an integer count: c_a c_b (a <= b, row-major), c_a b, b b; a rejected or absent candidate is +0.0.  Order: the index
+ *     space in runs of 1024; in a run lane l = 0 .. 63 adds its 16 consecutive terms in order from +0.0; the lanes fold
+ *     v[l] = v[l] + v[l + h] for h = 32, 16, 8, 4, 2, 1; the run sums are added in run order from +0.0; the forward total over i and the
+ *     backward total over j separately, total = fwd + bwd.
+ *  Y5 fewer than 6 accepted pairs: status 1, stop, the pose stays.  Cholesky H = L L^T, j ascending: d_j = H_jj - L_j0^2 - .. (k
+ *     ascending); unless d_j > piv_eps H_jj (a NaN fails): status 2 (singular), stop, the pose stays.  L_jj = sqrt(d_j),
+ *     L_ij = (H_ij - L_i0 L_j0 - ..) / L_jj; y_i = (g_i - L_i0 y_0 - ..) / L_ii; x_i = (y_i - L_(i+1)i x_(i+1) - .. - L_5i x_5) / L_ii,
+ *     i descending.  x = (a, tt).  A non-finite x: status 3, stop, the pose stays.
+ *  Y6 c = 1 / sqrt(1 + a.a); R[u][v] = (D_uv + c S_uv) + (c c / (1 + c)) (a_u a_v), D = c I, S = [0 -a2 a1; a2 0 -a0; -a1 a0 0];
+ *     dW = R R; dt = R.(c tt); W = dW W; t = (dW.t) + dt.  No re-orthonormalisation.
+ *  Y7 log row k = (n_pairs, S(b b) / n_pairs (0 without a pair), a.a, dt.dt, 0, 0, 0, 0) (a.a and dt.dt 0 on a status stop).  If
+ *     a.a <= fl(eps_rot eps_rot) and dt.dt <= fl(eps_trans eps_trans): converged = 1, stop.  Rows past iters_run are +0.0.
+ *  Result: B_to_A = [W t; 0 1] of the last pose, T = [W^T, -(W^T.t); 0 1], iters_run (the stopping iteration included), converged,
+ *     status, the last n_pairs and mean square.  The same bits on every run, whatever the scratch held; no floating-point atomics; no
+ *     host synchronisation: graph-capturable.
+ *  Refusals, all LR_EINVAL before any launch, lr_last_error naming the argument: wrong struct_size; n_iter outside 1..1000; max_dist,
+ *     piv_eps, eps_rot, eps_trans not positive and finite; min_cos outside [0, 1]; cell negative or not finite; n0 / n1 outside
+ *     0..4194304; null pointers where n > 0 (scratch and result always needed); short or misaligned (256 bytes) scratch; scratch that
+ *     is not memory of the current gfx950 device, or a stream of another device.  n0 == 0 or n1 == 0 is legal (status 1).          */
+typedef struct lr_symicp_params {
+    uint32_t struct_size;        /* = sizeof(lr_symicp_params)                                                                      */
+    int32_t  n_iter;             /* 30; 1..1000                                                                                     */
+    double   max_dist;           /* two voxels: 0.6 at the refinement tester's 0.3                                                  */
+    double   min_cos;            /* 0.7; [0, 1]                                                                                     */
+    double   eps_rot, eps_trans; /* 1e-5 (tan of the half step's angle), 1e-4 (m)                                                   */
+    double   piv_eps;            /* 1e-9                                                                                            */
+    double   cell;               /* 0 = automatic (N6)                                                                              */
+    const double *T_init;        /* device, fp64, row-major 4x4, nullable: the start B -> A                                         */
+} lr_symicp_params;
+
+/* Written to device memory by lr_symicp (280 bytes). */
+typedef struct lr_symicp_result {
+    double   T[16];              /* A -> B, row-major                                                                               */
+    double   B_to_A[16];
+    int32_t  status;             /* 0 ok, 1 = fewer than 6 pairs, 2 = singular normal equations, 3 = a non-finite step              */
+    int32_t  iters_run;          /* log rows written, the stopping one included                                                     */
+    int32_t  converged;
+    int32_t  n_pairs;            /* of the last iteration                                                                           */
+    double   mean_sq;            /* S(b b) / n_pairs of the last iteration                                                          */
+} lr_symicp_result;
+
+/* Caller-owned device scratch (0 when n0 / n1 is outside 0..4194304). */
+LR_API size_t lr_symicp_scratch_bytes(int n0, int n1);
+/* xyzA, nrmA [n0,3], xyzB, nrmB [n1,3]: device float64; result: device block; log: device float64 [n_iter, 8], nullable.           */
+LR_API int lr_symicp(const double *xyzA, const double *nrmA, int n0, const double *xyzB, const double *nrmB, int n1,
+                     const lr_symicp_params *params, lr_symicp_result *result, double *log, void *scratch, size_t scratch_bytes, void *stream);
 
 /* ---- f8: balanced-set selection -----------------------------------------------------------------------------------------------------
  * lr_balanced_select replaces the rejection loop of BalancedDatasetGenerator/GenerateBalancedSet.py (select_balanced_set :544-562 around

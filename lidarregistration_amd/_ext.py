@@ -24,7 +24,7 @@ SYMBOLS = [
     "lr_sm_scratch_bytes", "lr_sm", "lr_sm_batch",
     "lr_voxel_mean_scratch_bytes", "lr_voxel_mean", "lr_overlap_scratch_bytes", "lr_overlap", "lr_overlap_batch",
     "lr_nn3_scratch_bytes", "lr_nn3", "lr_refine_z_scratch_bytes", "lr_refine_z",
-    "lr_bbrf_scratch_bytes", "lr_bbrf", "lr_normals_scratch_bytes", "lr_normals",
+    "lr_bbrf_scratch_bytes", "lr_bbrf", "lr_normals_scratch_bytes", "lr_normals", "lr_normals2", "lr_symicp_scratch_bytes", "lr_symicp",
     "lr_balanced_select_scratch_bytes", "lr_balanced_select",
     "lr_pdsc_weights_bytes", "lr_pdsc_scratch_bytes", "lr_pdsc_encode", "lr_pdsc_encode_batch",
     "lr_pdsc_solve_scratch_bytes", "lr_pdsc_solve", "lr_pdsc_solve_batch",
@@ -170,6 +170,20 @@ class BbrfResult(ctypes.Structure):
                 ("best_loss", ctypes.c_double), ("n_pairs_best", ctypes.c_int32), ("iters_run", ctypes.c_int32)]
 
 
+class SymicpParams(KeywordParams):
+    """lr_symicp_params; max_dist is two of the refinement tester's voxels, the rest as chosen in DESIGN.md §23; struct_size is filled in.
+    T_init: the address of a device float64 4x4, or None."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_iter", ctypes.c_int32), ("max_dist", ctypes.c_double), ("min_cos", ctypes.c_double),
+                ("eps_rot", ctypes.c_double), ("eps_trans", ctypes.c_double), ("piv_eps", ctypes.c_double), ("cell", ctypes.c_double),
+                ("T_init", ctypes.c_void_p)]
+    DEFAULTS = dict(n_iter=30, max_dist=0.6, min_cos=0.7, eps_rot=1e-5, eps_trans=1e-4, piv_eps=1e-9, cell=0.0, T_init=None)
+
+
+class SymicpResult(ctypes.Structure):
+    _fields_ = [("T", ctypes.c_double * 16), ("B_to_A", ctypes.c_double * 16), ("status", ctypes.c_int32), ("iters_run", ctypes.c_int32),
+                ("converged", ctypes.c_int32), ("n_pairs", ctypes.c_int32), ("mean_sq", ctypes.c_double)]
+
+
 class SelectParams(KeywordParams):
     """lr_select_params with the reference's threshold (GenerateBalancedSet.py:474) as default; struct_size is filled in."""
     _fields_ = [("struct_size", ctypes.c_uint32), ("n_request", ctypes.c_int32), ("thresh", ctypes.c_double), ("resume", ctypes.c_int32),
@@ -256,6 +270,7 @@ assert ctypes.sizeof(PdscSolveParams) == 64 and ctypes.sizeof(PdscSolveResult) =
 assert ctypes.sizeof(PdscParams) == 16 and ctypes.sizeof(PdscResult) == 16
 assert ctypes.sizeof(SelectParams) == 24 and ctypes.sizeof(SelectResult) == 136
 assert ctypes.sizeof(BbrfParams) == 56 and ctypes.sizeof(BbrfResult) == 280
+assert ctypes.sizeof(SymicpParams) == 64 and ctypes.sizeof(SymicpResult) == 280
 assert ctypes.sizeof(Nn3Params) == 16 and ctypes.sizeof(RefineZParams) == 32 and ctypes.sizeof(RefineZResult) == 40
 assert ctypes.sizeof(OverlapParams) == 24 and ctypes.sizeof(OverlapResult) == 40
 assert ctypes.sizeof(TeaserParams) == 72 and ctypes.sizeof(TeaserResult) == 176
@@ -350,6 +365,9 @@ def lib():
         L.lr_bbrf.argtypes = [vp, vp, ci, vp, vp, ci, ctypes.POINTER(BbrfParams), vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_normals_scratch_bytes.argtypes = [ci]
         L.lr_normals.argtypes = [vp, ci, dp, ci, vp, vp, vp, ctypes.c_size_t, vp]
+        L.lr_normals2.argtypes = [vp, ci, dp, ci, vp, vp, vp, vp, ctypes.c_size_t, vp]
+        L.lr_symicp_scratch_bytes.argtypes = [ci, ci]
+        L.lr_symicp.argtypes = [vp, vp, ci, vp, vp, ci, ctypes.POINTER(SymicpParams), vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_balanced_select_scratch_bytes.argtypes = [ci]
         L.lr_balanced_select.argtypes = [vp, vp, vp, ci, ci, vp, ctypes.c_longlong, ctypes.POINTER(SelectParams), vp, vp, vp, vp, vp, ctypes.c_size_t, vp]
         L.lr_pdsc_weights_bytes.restype = ctypes.c_size_t

@@ -88,11 +88,12 @@ def calc_errors(T_pred, T_gt, rot_thresh, trans_thresh, eps=1e-16):
     return np.array([rte < trans_thresh and rre < rot_thresh, rte, rre])
 
 
-def refinement_sample(gt_motion, init_motion, PC0, PC1, rot_thresh, trans_thresh, voxel_size=REFINE_VOXEL):
+def refinement_sample(gt_motion, init_motion, PC0, PC1, rot_thresh, trans_thresh, voxel_size=REFINE_VOXEL, symmetric=False):
     """refinement_tester.py:75-90: the twelve result columns [ICP recall, te, re, time, BBR recall, te, re, time, symmetric-ICP recall,
     te, re, time] of one pair: both clouds down-sampled at voxel_size, cloud 0 moved by the coarse motion, the ground truth taken
-    relative to it, then ICP (lr_icp at 2 voxel_size, exactly overlap.refine_motion's) and BBR-F.  The symmetric ICP is an external
-    binary of the reference's and is not built: its columns are NaN."""
+    relative to it, then ICP (lr_icp at 2 voxel_size, exactly overlap.refine_motion's), BBR-F and, with symmetric=True, the symmetric
+    ICP (symicp.symmetric_icp at 2 voxel_size: lr_symicp, upstream-recalled, parity unpinned -- the reference calls an external binary).
+    symmetric=False, the default, leaves columns 8-11 NaN."""
     from .ransac import icp_dev
     init = np.ascontiguousarray(init_motion, np.float64).reshape(4, 4)
     a = voxel_down_sample(PC0, voxel_size); b = voxel_down_sample(PC1, voxel_size)
@@ -104,5 +105,10 @@ def refinement_sample(gt_motion, init_motion, PC0, PC1, rot_thresh, trans_thresh
     ICP_time = time() - t0
     BBR_M, BBR_time = BBR_F(a.cpu().numpy(), b.cpu().numpy())
     nan = float("nan")
+    sym = [nan, nan, nan, nan]
+    if symmetric:
+        from .symicp import symmetric_icp
+        SYM_M, SYM_time = symmetric_icp(a, b, max_dist=2.0 * float(voxel_size))
+        sym = [*calc_errors(SYM_M, gt, rot_thresh, trans_thresh), SYM_time]
     return np.array([*calc_errors(ICP_M, gt, rot_thresh, trans_thresh), ICP_time, *calc_errors(BBR_M, gt, rot_thresh, trans_thresh), BBR_time,
-                     nan, nan, nan, nan])
+                     *sym])

@@ -1,4 +1,4 @@
-// Best-Buddies refinement (lr_bbrf) and hybrid-search point normals (lr_normals) on the grid of the exact nearest neighbour, on gfx950.
+// Best-Buddies refinement (lr_bbrf) and hybrid-search point normals (lr_normals, lr_normals2: the same with the neighbour counts) on the grid of the exact nearest neighbour, on gfx950.
 //
 // Replaces FCGF_FAST/net/BBR_F.py:267-322 (BBR_F: 100 Adam steps over the mutual nearest neighbours of two clouds under a symmetric
 // point-to-plane loss) and its calc_normals (:236-241).  Contract B and the normals contract: include/lidarreg.h; restated
@@ -308,6 +308,7 @@ struct nm_args {
     double r2;
     double *out;
     int32_t *info;
+    int32_t *n_nb;                                           // nullable (lr_normals2): the neighbours every point took
 };
 
 // one Jacobi rotation on (p, q), r the third index
@@ -339,6 +340,7 @@ __global__ void __launch_bounds__(256) nm_kernel(nm_args a)
     const int i = blockIdx.x * 256 + threadIdx.x;
     bool bad = false, few = false;
     if (i < a.n) {
+        int taken = 0;
         const double q[3] = { a.xyz[3 * (size_t)i], a.xyz[3 * (size_t)i + 1], a.xyz[3 * (size_t)i + 2] };
         double nrm[3] = { 0.0, 0.0, 1.0 };
         bad = !(isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]));
@@ -374,6 +376,7 @@ __global__ void __launch_bounds__(256) nm_kernel(nm_args a)
                 S[6] += bp[1] * bp[1]; S[7] += bp[1] * bp[2]; S[8] += bp[2] * bp[2];
             }
             few = k < 3;
+            taken = k;
             if (!few) {
                 const double kn = (double)k;
                 double E[9];
@@ -393,6 +396,7 @@ __global__ void __launch_bounds__(256) nm_kernel(nm_args a)
             }
         }
         a.out[3 * (size_t)i] = nrm[0]; a.out[3 * (size_t)i + 1] = nrm[1]; a.out[3 * (size_t)i + 2] = nrm[2];
+        if (a.n_nb) a.n_nb[i] = taken;
     }
     const unsigned long long nbad = __ballot(bad), nfew = __ballot(few);
     if ((threadIdx.x & 63) == 0) {
@@ -474,10 +478,9 @@ extern "C" int lr_bbrf(const double *xyzA, const double *nrmA, int n0, const dou
     return LR_OK;
 }
 
-extern "C" int lr_normals(const double *xyz, int n, double radius, int max_nn, double *normals_out, int32_t *info, void *scratch,
-                          size_t scratch_bytes, void *stream)
+static int nm_run(const char *who, const double *xyz, int n, double radius, int max_nn, double *normals_out, int32_t *n_nb_out, int32_t *info,
+                  void *scratch, size_t scratch_bytes, void *stream)
 {
-    const char *who = "lr_normals";
     LR_REFUSE_UNLESS(radius > 0.0 && isfinite(radius) && isfinite(radius * radius), LR_EINVAL, "radius must be positive and finite");
     LR_REFUSE_UNLESS(max_nn >= 1 && max_nn <= BB_MAX_NN, LR_EINVAL, "max_nn must lie in 1..32");
     LR_REFUSE_UNLESS(n >= 0 && n <= NN_MAX_N, LR_EINVAL, "n must lie in 0..4194304");
@@ -490,7 +493,7 @@ extern "C" int lr_normals(const double *xyz, int n, double radius, int max_nn, d
     // rounding of the cell quotients (below 2^-29 of a cell at up to 2^22 cells per axis)
     nn_set_args(&a.nn, scratch, xyz, n, xyz, n, radius * (1.0 + 1.0 / 65536.0), nullptr, nullptr);
     LR_TRY_HIP(lr_check_scratch(who, scratch, scratch_bytes, a.nn.stride, "lr_normals_scratch_bytes(n)", LR_EINVAL, stream, nullptr));
-    a.xyz = xyz; a.n = n; a.max_nn = max_nn; a.r2 = radius * radius; a.out = normals_out; a.info = info;
+    a.xyz = xyz; a.n = n; a.max_nn = max_nn; a.r2 = radius * radius; a.out = normals_out; a.info = info; a.n_nb = n_nb_out;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(nm_info_kernel, dim3(1), dim3(64), 0, st, a, 0);
     nn_launch_grid(a.nn, st);
@@ -498,4 +501,16 @@ extern "C" int lr_normals(const double *xyz, int n, double radius, int max_nn, d
     hipLaunchKernelGGL(nm_info_kernel, dim3(1), dim3(64), 0, st, a, 1);
     LR_LAUNCH_CHECK();
     return LR_OK;
+}
+
+extern "C" int lr_normals(const double *xyz, int n, double radius, int max_nn, double *normals_out, int32_t *info, void *scratch,
+                          size_t scratch_bytes, void *stream)
+{
+    return nm_run("lr_normals", xyz, n, radius, max_nn, normals_out, nullptr, info, scratch, scratch_bytes, stream);
+}
+
+extern "C" int lr_normals2(const double *xyz, int n, double radius, int max_nn, double *normals_out, int32_t *n_nb_out, int32_t *info,
+                           void *scratch, size_t scratch_bytes, void *stream)
+{
+    return nm_run("lr_normals2", xyz, n, radius, max_nn, normals_out, n_nb_out, info, scratch, scratch_bytes, stream);
 }

@@ -1,5 +1,5 @@
 // The grid and the search launches of the exact 3-D nearest neighbour (lr_nn3.hip), for the translation units that run them inside a
-// sequence of their own (lr_bbrf.hip).  Internal: not part of the ABI.  The layout and the control block are what lr_nn3 / lr_refine_z
+// sequence of their own (lr_bbrf.hip, lr_symicp.hip).  Internal: not part of the ABI.  The layout and the control block are what lr_nn3 / lr_refine_z
 // use; *_scratch_bytes of either must not move when this file changes.  Needs lr_scratch.h alone (lr_al, lr_ptr): nothing of the
 // correspondence-set front end.
 #pragma once
@@ -37,7 +37,7 @@ struct nn_args {
     double gate, min_change;
     int32_t max_repeats;
     lr_refine_z_result *res;
-    const int32_t *stop;                     // nullable: a non-zero word here makes every grid / search kernel return at once (lr_bbrf's loop)
+    const int32_t *stop;                     // nullable: a non-zero word here makes every grid / search kernel return at once (lr_bbrf's and lr_symicp's loops)
 };
 
 static size_t nn_cells_max(size_t n1) { return 4 * n1 > 4096 ? 4 * n1 : 4096; }

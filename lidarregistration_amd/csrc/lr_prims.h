@@ -1,4 +1,4 @@
-// The building blocks the cloud-level kernels share (lr_filter.hip, lr_icp.hip, lr_voxel.hip, lr_overlap.hip, lr_nn3.hip, lr_bbrf.hip,
+// The building blocks the cloud-level kernels share (lr_filter.hip, lr_icp.hip, lr_voxel.hip, lr_overlap.hip, lr_nn3.hip, lr_bbrf.hip, lr_symicp.hip,
 // lr_sm.hip, lr_teaser.hip, lr_pdsc.hip, lr_pdsc_solve.hip, lr_dgr.hip; not part of the ABI): wave and block scans, flag counting and
 // ordered compaction, the fixed summation tree over a block and its wave levels, the total order of the doubles as integers, the
 // three-term dot product, the 64-bit mix hash.  Device only, inlined, no state; a wave is 64 lanes.  The NN files (lr_nn16*.hip) and the RANSAC files (lr_ransac.hip, lr_score.hip, lr_lo.hip) keep their own spellings: the helper re-schedules their kernels.
@@ -121,6 +121,16 @@ __device__ __forceinline__ double lr_ord_dec(unsigned long long e)
 }
 // u . v of three doubles; the association (u0 v0 + u1 v1) + u2 v2 is what the fp64 restatements evaluate
 __device__ __forceinline__ double lr_dot3(const double *u, const double *v) { return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2]; }
+// row a of M.v and the product P Q of 3 x 3 row-major matrices under the same association (lr_symicp.hip; lr_bbrf.hip keeps its own
+// spellings of the two, bb_row / bb_mat3: the source of its loop kernels is left as it was)
+__device__ __forceinline__ double lr_row3(const double *M, int a, double x, double y, double z) { return (M[3 * a] * x + M[3 * a + 1] * y) + M[3 * a + 2] * z; }
+__device__ __forceinline__ void lr_mat3(const double *P, const double *Q, double *R)
+{
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) R[3 * a + b] = (P[3 * a] * Q[b] + P[3 * a + 1] * Q[3 + b]) + P[3 * a + 2] * Q[6 + b];
+}
 // 64-bit finaliser mix (MurmurHash3's fmix64): every input bit reaches every output bit
 __device__ __forceinline__ unsigned long long lr_mix64(unsigned long long k)
 {
